@@ -216,6 +216,26 @@ def run_region(xch, launch, t_first, count):
     return xch.collectives - c0, xch.steps_sent - s0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write the outputs of the last timed step as out_dir/<name>.npy (float32, or float64 where the kernel writes f64).
+    Every array is indexed by env on its first axis; past DUMP_LIMIT_BYTES in all, the same seeded sample of env rows is
+    kept of each (and written as env_index.npy), so that two builds dump the same rows."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in arrays.values())
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * n) // (row_bytes + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -245,6 +265,9 @@ def main():
                     help="GPU busy time on a scratch handle before the warm-up steps (raises the clock from idle; 0 = off)")
     ap.add_argument("--time-every", type=int, default=25,
                     help="HIP events bracket every other group of k consecutive launches of the timed region (an event pair costs ~8 us of stream time, so k is kept large)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (obs, reward, done, "
+                         "complete, terminal_obs of rank 0's envs) as DIR/<name>.npy, to compare two builds output for output")
     args = ap.parse_args()
 
     import torch
@@ -383,6 +406,10 @@ def main():
         kt = env.kernel_times_ms()
         env.set_timing(0)
     c1 = env.counters()
+    if args.dump_outputs and rank == 0:   # before the fused-rollout leg below overwrites the env's output buffers
+        dump_outputs(args.dump_outputs, {"obs": env.obs.cpu().numpy(), "reward": env.reward.cpu().numpy(),
+                                         "done": env.done.cpu().numpy(), "complete": env.complete.cpu().numpy(),
+                                         "terminal_obs": env.terminal_obs.cpu().numpy()})
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

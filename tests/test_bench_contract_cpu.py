@@ -116,3 +116,33 @@ def test_profile_summaries_refuse_a_stale_or_foreign_library(tmp_path, monkeypat
     s = json.load(open(os.path.join(ROOT, "profiles", "r04_summary.json")))
     assert len(s["source"]["source_sha256"]) == 64 and s["source"]["library_older_than_sources"] is False
     assert s["source"]["library_built_from"] == s["source"]["source_sha256"] and s["source"]["git_head"]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_the_same_rows_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    bench = _load_bench()
+    n = 1000
+    arrays = {"obs": np.arange(n * 18, dtype=np.float32).reshape(n, 18), "reward": np.linspace(-1, 1, n),
+              "done": (np.arange(n) % 3 == 0).astype(np.uint8)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == (np.float64 if k == "reward" else np.float32) and np.array_equal(got, a)
+    assert not (tmp_path / "all" / "env_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["done.npy", "env_index.npy", "obs.npy", "reward.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size - 128 for f in files) <= 20000
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), arrays["obs"][idx])
+
+
+def test_bench_has_the_dump_outputs_option():
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--dump-outputs"' in src and "dump_outputs(args.dump_outputs" in src

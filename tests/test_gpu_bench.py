@@ -81,3 +81,21 @@ def test_two_rank_launch_as_the_driver_starts_it_gloo_rehearsal_on_one_gpu():
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["scaling"] == "strong" and line["config"]["n_envs_per_gpu"] == 2048 and line["config"]["n_envs_total"] == 4096
+
+
+def test_dump_outputs_are_the_last_timed_step_and_identical_across_runs(tmp_path):
+    """--dump-outputs: the arrays the last timed step returned (obs / reward / done / complete / terminal_obs of every env),
+    bit-identical from one run to the next with the same arguments; --steps sets the timed step count."""
+    import numpy as np
+    args = ["--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--envs", "1024"]
+    lines = [_bench(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 30 and line["ms_per_step"] > 0
+    names = {"obs": ((1024, 18), np.float32), "reward": ((1024,), np.float64), "done": ((1024,), np.float32),
+             "complete": ((1024,), np.float32), "terminal_obs": ((1024, 18), np.float32)}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(k + ".npy" for k in names)
+    for k, (shape, dtype) in names.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.shape == shape and a.dtype == dtype and np.array_equal(a, b), k
+    done = np.load(tmp_path / "a" / "done.npy")
+    assert set(np.unique(done)) <= {0.0, 1.0}
