@@ -485,6 +485,56 @@ int meshenv_step_actor(MeshEnv *h, MeshActor *a, const float *actions_dev, float
                        float *actions_next_dev, float *eps_out_dev);
 
 /*
+ * Fused PPO / A2C / TD3 / DDPG policies (csrc/meshenv_policy.h) -- the rollout side of the reference's other algorithms
+ * (rl/baselines/RL_Mesh.py:113-228), not part of the environment.  One MLP of two hidden layers on obs[18]:
+ *   kind 0 (actor-critic, SB3 ActorCriticPolicy: PPO, A2C): pi tower -> action_net = mean, vf tower -> value_net = value;
+ *          std = exp(log_std) (a state-independent [3] parameter), buffer_action = mean + std * eps,
+ *          action = clamp(buffer_action, low, high), log_prob = sum over the 3 components of Normal(mean, std).log_prob
+ *   kind 1 (deterministic, SB3 TD3Policy: actor.mu): scaled = tanh(mu(latent)); with noise
+ *          scaled = clamp(scaled + sigma * eps, -1, 1); buffer_action = scaled, action = low + 0.5 (scaled + 1) (high - low)
+ * hidden 64, 128 or 256 (both layers), activation 0 ReLU or 1 Tanh; any other shape fails with MESHENV_E_ARG and a message
+ * naming the supported ones.  Weights: host pointers, torch.nn.Linear layout ([out][in], row-major), float32: the pi (or
+ * actor) tower's two layers, its head (action_net [3][hidden] or mu [3][hidden]), the vf tower's two layers and value_net
+ * [1][hidden] (NULL for kind 1), log_std (kind 0) or sigma (kind 1, nullable: no action noise), low and high [3].
+ */
+typedef struct MeshPolicy MeshPolicy;
+int meshenv_policy_create(int device, void *stream, MeshPolicy **out);
+void meshenv_policy_destroy(MeshPolicy *p);
+int meshenv_policy_set_stream(MeshPolicy *p, void *stream);
+const char *meshenv_policy_last_error(const MeshPolicy *p);   /* message of the handle's last failure */
+int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, const float *pi_w1, const float *pi_b1,
+                        const float *pi_w2, const float *pi_b2, const float *head_w, const float *head_b, const float *vf_w1,
+                        const float *vf_b1, const float *vf_w2, const float *vf_b2, const float *value_w, const float *value_b,
+                        const float *log_std_or_sigma, const float *low, const float *high);
+/*
+ * One launch.  eps: noise_dev [n][3] (explicit N(0,1) draws), or sample != 0 (Philox4x32-10 keyed by seed, counter
+ * (env, counter) -- the same stream as the SAC actor's sample entry point), or neither (eps = 0: the deterministic action).
+ * Outputs, each nullable: actions_dev / buffer_actions_dev / eps_out_dev [n][3], log_prob_dev / value_dev [n] (kind 0 only:
+ * kind 1 fails with MESHENV_E_ARG when they are given).  value_dev alone is the value-only mode: the vf tower by itself.
+ * eps_out_dev fed back as noise_dev reproduces the outputs bit for bit.
+ */
+int meshenv_policy_forward(MeshPolicy *p, int n, const float *obs_dev, const float *noise_dev, int sample, uint64_t seed,
+                           uint64_t counter, float *actions_dev, float *buffer_actions_dev, float *log_prob_dev, float *value_dev,
+                           float *eps_out_dev);
+/*
+ * T vector steps of the closed loop in one call, no host synchronisation: for t < T the policy on obs_t (noise counter
+ * counter + t when sample != 0, eps = 0 otherwise) and a step of every env on its actions; then the values of obs_T.
+ *   obs_dev [T+1][n][18]: slice 0 = the current observation (input); slice t + 1 = the observation after step t
+ *   actions_dev, buffer_actions_dev (nullable), eps_dev (nullable) [T][n][3]; log_prob_dev, value_dev [T][n] (nullable)
+ *   reward_dev [T][n] float64, done_dev, complete_dev [T][n] uint8, terminal_obs_dev [T][n][18] (nullable): as the
+ *       single step writes them
+ *   terminal_value_dev [T][n] (nullable, needs terminal_obs_dev): V(terminal obs of step t) where done && !complete, else
+ *       0 -- the bootstrap value of a truncated episode
+ *   last_value_dev [n] (nullable): V(obs_T)
+ * log_prob / value / terminal_value / last_value must be NULL for kind 1.  Bit-identical to T pairs of policy forward + step
+ * on the same slices.  Env and policy must share device and stream (MESHENV_E_STATE otherwise).
+ */
+int meshenv_step_policy_multi(MeshEnv *h, MeshPolicy *p, int T, float *obs_dev, int sample, uint64_t seed, uint64_t counter,
+                              float *actions_dev, float *buffer_actions_dev, float *log_prob_dev, float *value_dev, float *eps_dev,
+                              double *reward_dev, uint8_t *done_dev, uint8_t *complete_dev, float *terminal_obs_dev,
+                              float *terminal_value_dev, float *last_value_dev, int auto_reset);
+
+/*
  * MeshGeneration.extract_samples_2(meshes, n_neighbor, n_radius, radius, index, quality_threshold), general/mesh.py:1438-1489
  * (the data-preparation step of the ANN scripts: general/EBRD.py:414, 579 with (2, 3, radius 4, index 1) and
  * general/post_processing.py:532 with (3, 3, radius 6, index 5)) for the generated mesh of EVERY env in one launch

@@ -6,7 +6,7 @@ ZhuoQiuMcgill/ReinforcementLearning4MeshGeneration as hand-written HIP kernels b
 from .domains import boundary, domain_constants, generate_polygon, random_domain, read_polygon  # noqa: F401
 
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
-           "random_domain", "MeshEnvError", "FusedActor"]
+           "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -25,4 +25,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name == "FusedActor":
         from .actor import FusedActor
         return FusedActor
+    if name == "FusedPolicy":
+        from .policy import FusedPolicy
+        return FusedPolicy
     raise AttributeError(name)

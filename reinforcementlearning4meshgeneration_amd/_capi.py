@@ -46,6 +46,8 @@ EXPORTS = [
     "meshenv_create_random", "meshenv_get_domain", "meshenv_smooth", "meshenv_smooth_final", "meshenv_get_not_valid_ids", "meshenv_step_actor",
     "meshenv_libm_exact", "meshenv_create_random_density", "meshenv_density_rings",
     "meshenv_step_actor_multi", "meshenv_extract_samples", "meshenv_atan2_exact", "meshenv_quad_quality",
+    "meshenv_policy_create", "meshenv_policy_destroy", "meshenv_policy_set_stream", "meshenv_policy_load",
+    "meshenv_policy_forward", "meshenv_step_policy_multi", "meshenv_policy_last_error",
 ]
 
 
@@ -145,6 +147,18 @@ def load():
     L.meshenv_actor_load.argtypes = [vp] + [vp] * 12
     L.meshenv_actor_forward.argtypes = [vp, C.c_int, vp, vp, vp]
     L.meshenv_actor_sample.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp]
+    L.meshenv_policy_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
+    L.meshenv_policy_destroy.argtypes = [vp]
+    L.meshenv_policy_destroy.restype = None
+    L.meshenv_policy_set_stream.argtypes = [vp, vp]
+    L.meshenv_policy_last_error.argtypes = [vp]
+    L.meshenv_policy_last_error.restype = C.c_char_p
+    L.meshenv_policy_load.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 15
+    L.meshenv_policy_forward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
+    L.meshenv_step_policy_multi.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 11 + [C.c_int]
+    for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
+                 "meshenv_step_policy_multi"):
+        getattr(L, name).restype = C.c_int
     for name in ("meshenv_actor_create", "meshenv_actor_set_stream", "meshenv_actor_load", "meshenv_actor_forward",
                  "meshenv_actor_sample"):
         getattr(L, name).restype = C.c_int

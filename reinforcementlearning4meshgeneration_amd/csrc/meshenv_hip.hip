@@ -23,6 +23,7 @@
 #include "meshenv_smooth.h"
 #include "meshenv_samples.h"
 #include "meshenv_fused.h"
+#include "meshenv_policy.h"
 
 using namespace meshenv;
 
@@ -1930,5 +1931,262 @@ int meshenv_dev_set_tsteps_dbg(unsigned long long *buf_dev)
     return MESHENV_OK;
 }
 #endif
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ fused PPO / A2C / TD3 policies
+struct MeshPolicy {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    float *buf = nullptr;  // all weights of the loaded policy, one allocation
+    PolicyWeights W{};
+    int kind = -1, hidden = 0, activation = 0;
+    bool loaded = false;
+    std::string err;
+};
+
+namespace {
+
+typedef void (*PolicyKernel)(PolicyWeights, PolicyArgs);
+
+// the twelve instantiations: [kind][hidden 64 / 128 / 256][activation]
+PolicyKernel policy_kernel(int kind, int hidden, int activation)
+{
+    static const PolicyKernel table[2][3][2] = {
+        {{k_policy_forward<64, kPolicyReLU, kPolicyActorCritic>, k_policy_forward<64, kPolicyTanh, kPolicyActorCritic>},
+         {k_policy_forward<128, kPolicyReLU, kPolicyActorCritic>, k_policy_forward<128, kPolicyTanh, kPolicyActorCritic>},
+         {k_policy_forward<256, kPolicyReLU, kPolicyActorCritic>, k_policy_forward<256, kPolicyTanh, kPolicyActorCritic>}},
+        {{k_policy_forward<64, kPolicyReLU, kPolicyDeterministic>, k_policy_forward<64, kPolicyTanh, kPolicyDeterministic>},
+         {k_policy_forward<128, kPolicyReLU, kPolicyDeterministic>, k_policy_forward<128, kPolicyTanh, kPolicyDeterministic>},
+         {k_policy_forward<256, kPolicyReLU, kPolicyDeterministic>, k_policy_forward<256, kPolicyTanh, kPolicyDeterministic>}}};
+    return table[kind][hidden == 64 ? 0 : hidden == 128 ? 1 : 2][activation];
+}
+
+const char *kPolicyShapes = "supported policies: kind 0 (actor-critic: pi and vf towers) or 1 (deterministic tanh actor), two hidden "
+                            "layers of width 64, 128 or 256, activation 0 (ReLU) or 1 (Tanh), 18 inputs, 3 actions";
+
+// One launch of k_policy_forward.  The pi workgroups run when an action output is asked for, the vf workgroups when a value
+// (or a bootstrap terminal value) is.  Arguments are checked by the callers.
+int policy_launch(MeshPolicy *p, const char *fn, const PolicyArgs &A)
+{
+    const bool pi = A.actions || A.buffer_actions || A.log_prob || A.eps_out;
+    const bool vf = p->kind == kPolicyActorCritic && (A.value || A.tvalue);
+    if (!pi && !vf) return MESHENV_OK;
+    PolicyArgs a = A;
+    a.tower0 = pi ? 0 : 1;
+    const dim3 grid((A.n + kPolEnvs - 1) / kPolEnvs, (pi ? 1 : 0) + (vf ? 1 : 0));
+    DeviceGuard guard(p->device);
+    if (guard.err != hipSuccess) {
+        p->err = std::string(fn) + ": hipSetDevice failed";
+        return MESHENV_E_HIP;
+    }
+    hipLaunchKernelGGL(policy_kernel(p->kind, p->hidden, p->activation), grid, dim3(4 * p->hidden), 0, p->stream, p->W, a);
+    if (hipGetLastError() != hipSuccess) {
+        p->err = std::string(fn) + ": launch failed";
+        return MESHENV_E_HIP;
+    }
+    return MESHENV_OK;
+}
+
+int policy_fail(MeshPolicy *p, int rc, const std::string &msg)
+{
+    p->err = msg;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_policy_create(int device, void *stream, MeshPolicy **out)
+{
+    if (!out) return MESHENV_E_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        g_create_error = "meshenv_policy_create: no such HIP device";
+        return MESHENV_E_HIP;
+    }
+    MeshPolicy *p = new MeshPolicy();
+    p->device = device;
+    p->stream = (hipStream_t)stream;
+    *out = p;
+    return MESHENV_OK;
+}
+
+void meshenv_policy_destroy(MeshPolicy *p)
+{
+    if (!p) return;
+    DeviceGuard guard(p->device);
+    (void)hipStreamSynchronize(p->stream);
+    if (p->buf) (void)hipFree(p->buf);
+    delete p;
+}
+
+const char *meshenv_policy_last_error(const MeshPolicy *p) { return p ? p->err.c_str() : g_create_error.c_str(); }
+
+int meshenv_policy_set_stream(MeshPolicy *p, void *stream)
+{
+    if (!p) return MESHENV_E_ARG;
+    p->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+// weights in torch.nn.Linear layout ([out][in], row-major), host pointers
+int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, const float *pi_w1, const float *pi_b1,
+                        const float *pi_w2, const float *pi_b2, const float *head_w, const float *head_b, const float *vf_w1,
+                        const float *vf_b1, const float *vf_w2, const float *vf_b2, const float *value_w, const float *value_b,
+                        const float *log_std_or_sigma, const float *low, const float *high)
+{
+    if (!p) return MESHENV_E_ARG;
+    if ((kind != kPolicyActorCritic && kind != kPolicyDeterministic) || (hidden != 64 && hidden != 128 && hidden != 256) ||
+        (activation != kPolicyReLU && activation != kPolicyTanh))
+        return policy_fail(p, MESHENV_E_ARG, std::string("meshenv_policy_load: unsupported shape; ") + kPolicyShapes);
+    const bool ac = kind == kPolicyActorCritic;
+    if (!pi_w1 || !pi_b1 || !pi_w2 || !pi_b2 || !head_w || !head_b || !low || !high || (ac && !log_std_or_sigma))
+        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_load: null weight pointer");
+    if (ac && (!vf_w1 || !vf_b1 || !vf_w2 || !vf_b2 || !value_w || !value_b))
+        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_load: the actor-critic kind needs the vf tower and value_net");
+    if (!ac && (vf_w1 || vf_b1 || vf_w2 || vf_b2 || value_w || value_b))
+        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_load: the deterministic kind has no vf tower (pass NULL)");
+    const int H = hidden;
+    std::vector<float> h;
+    // torch [out][in] -> the per-lane MFMA B-operand order of meshenv_policy.h: [tile][K/16][lane][4]
+    auto packed = [&](const float *w, int out, int in, int k_pad, int tiles) {
+        const size_t off = h.size();
+        const int groups = k_pad / 16;
+        h.resize(off + (size_t)tiles * groups * 64 * 4, 0.0f);
+        for (int tile = 0; tile < tiles; tile++)
+            for (int g = 0; g < groups; g++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int j = 0; j < 4; j++) {
+                        const int k = 4 * (4 * g + j) + (lane >> 4), n = 16 * tile + (lane & 15);
+                        if (k < in && n < out) h[off + (((size_t)tile * groups + g) * 64 + lane) * 4 + j] = w[(size_t)n * in + k];
+                    }
+        return off;
+    };
+    auto plain = [&](const float *b, int n, int pad) {
+        const size_t off = h.size();
+        h.resize(off + pad, 0.0f);
+        for (int i = 0; i < n; i++) h[off + i] = b[i];
+        return off;
+    };
+    struct Offs { size_t w1, b1, w2, b2, wh, bh; };
+    auto tower = [&](const float *w1, const float *b1, const float *w2, const float *b2, const float *wh, const float *bh, int n_out) {
+        Offs o;
+        o.w1 = packed(w1, H, kObsDim, kPolInPad, H / 16); o.b1 = plain(b1, H, H);
+        o.w2 = packed(w2, H, H, H, H / 16); o.b2 = plain(b2, H, H);
+        o.wh = packed(wh, n_out, H, H, 1); o.bh = plain(bh, n_out, 16);
+        return o;
+    };
+    const Offs pi = tower(pi_w1, pi_b1, pi_w2, pi_b2, head_w, head_b, 3);
+    Offs vf{};
+    if (ac) vf = tower(vf_w1, vf_b1, vf_w2, vf_b2, value_w, value_b, 1);
+    const size_t o_aux = h.size();
+    h.resize(o_aux + 16, 0.0f);
+    for (int i = 0; i < 3; i++) {
+        h[o_aux + i] = log_std_or_sigma ? log_std_or_sigma[i] : 0.0f;
+        h[o_aux + 3 + i] = low[i];
+        h[o_aux + 6 + i] = high[i];
+    }
+    DeviceGuard guard(p->device);
+    if (guard.err != hipSuccess) return policy_fail(p, MESHENV_E_HIP, "meshenv_policy_load: hipSetDevice failed");
+    (void)hipStreamSynchronize(p->stream);   // the previous weights may still be in use
+    if (p->buf) (void)hipFree(p->buf);
+    p->buf = nullptr;
+    p->loaded = false;
+    if (hipMalloc((void **)&p->buf, h.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(p->buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return policy_fail(p, MESHENV_E_HIP, "meshenv_policy_load: upload failed");
+    auto bind = [&](PolicyTower &T, const Offs &o) {
+        T.w1p = p->buf + o.w1; T.b1 = p->buf + o.b1;
+        T.w2p = p->buf + o.w2; T.b2 = p->buf + o.b2;
+        T.whp = p->buf + o.wh; T.bh = p->buf + o.bh;
+    };
+    bind(p->W.pi, pi);
+    if (ac) bind(p->W.vf, vf);
+    else p->W.vf = p->W.pi;   // never read
+    p->W.aux = p->buf + o_aux;
+    p->kind = kind; p->hidden = hidden; p->activation = activation;
+    p->loaded = true;
+    return MESHENV_OK;
+}
+
+int meshenv_policy_forward(MeshPolicy *p, int n, const float *obs_dev, const float *noise_dev, int sample, uint64_t seed,
+                           uint64_t counter, float *actions_dev, float *buffer_actions_dev, float *log_prob_dev, float *value_dev,
+                           float *eps_out_dev)
+{
+    if (!p) return MESHENV_E_ARG;
+    if (!p->loaded) return policy_fail(p, MESHENV_E_STATE, "meshenv_policy_forward: no weights loaded");
+    if (n <= 0 || !obs_dev) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: n > 0 and obs_dev are required");
+    if (noise_dev && sample) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: explicit noise and sample are exclusive");
+    if (p->kind == kPolicyDeterministic && (log_prob_dev || value_dev))
+        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: the deterministic kind has no log_prob / value (pass NULL)");
+    if (eps_out_dev && !sample && !noise_dev)
+        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: eps_out_dev without noise");
+    const bool pi = actions_dev || buffer_actions_dev || log_prob_dev || eps_out_dev;
+    if (!pi && !value_dev) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: no output requested");
+    if (!pi && (noise_dev || sample)) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: noise without an action output");
+    PolicyArgs A{};
+    A.n = n; A.obs = obs_dev; A.noise = noise_dev; A.sample = sample ? 1 : 0; A.seed = seed; A.counter = counter;
+    A.actions = actions_dev; A.buffer_actions = buffer_actions_dev; A.log_prob = log_prob_dev; A.value = value_dev;
+    A.eps_out = eps_out_dev;
+    return policy_launch(p, "meshenv_policy_forward", A);
+}
+
+int meshenv_step_policy_multi(MeshEnv *h, MeshPolicy *p, int T, float *obs_dev, int sample, uint64_t seed, uint64_t counter,
+                              float *actions_dev, float *buffer_actions_dev, float *log_prob_dev, float *value_dev, float *eps_dev,
+                              double *reward_dev, uint8_t *done_dev, uint8_t *complete_dev, float *terminal_obs_dev,
+                              float *terminal_value_dev, float *last_value_dev, int auto_reset)
+{
+    if (!h || !p) return MESHENV_E_ARG;
+    if (T <= 0 || !obs_dev || !actions_dev || !reward_dev || !done_dev || !complete_dev)
+        return fail_arg(h, "meshenv_step_policy_multi: T > 0 and non-null obs, actions, reward, done and complete are required");
+    if (!p->loaded) {
+        h->err = "meshenv_step_policy_multi: the policy has no weights loaded";
+        return MESHENV_E_STATE;
+    }
+    if (p->device != h->device || p->stream != h->stream) {   // the policy and step launches are ordered by the stream alone
+        h->err = "meshenv_step_policy_multi: env and policy must be on the same device and stream (meshenv_set_stream / "
+                 "meshenv_policy_set_stream)";
+        return MESHENV_E_STATE;
+    }
+    if (p->kind == kPolicyDeterministic && (log_prob_dev || value_dev || terminal_value_dev || last_value_dev))
+        return fail_arg(h, "meshenv_step_policy_multi: the deterministic kind has no log_prob / value outputs (pass NULL)");
+    if (eps_dev && !sample) return fail_arg(h, "meshenv_step_policy_multi: eps_dev without sample");
+    if (terminal_value_dev && !terminal_obs_dev) return fail_arg(h, "meshenv_step_policy_multi: terminal_value_dev needs terminal_obs_dev");
+    MESHENV_ON_DEVICE(h);
+    const size_t n = (size_t)h->n_envs;
+    PolicyArgs A{};
+    A.n = (int)n; A.sample = sample ? 1 : 0; A.seed = seed;
+    for (int t = 0; t <= T; t++) {
+        // the policy on obs_t (t == T: values only), with the terminal values of step t - 1 in the vf workgroups
+        A.obs = obs_dev + (size_t)t * n * kObsDim;
+        A.counter = counter + (uint64_t)t;
+        const bool last = t == T;
+        A.actions = last ? nullptr : actions_dev + (size_t)t * n * 3;
+        A.buffer_actions = last || !buffer_actions_dev ? nullptr : buffer_actions_dev + (size_t)t * n * 3;
+        A.log_prob = last || !log_prob_dev ? nullptr : log_prob_dev + (size_t)t * n;
+        A.eps_out = last || !eps_dev ? nullptr : eps_dev + (size_t)t * n * 3;
+        A.value = last ? last_value_dev : value_dev ? value_dev + (size_t)t * n : nullptr;
+        A.sample = last ? 0 : (sample ? 1 : 0);
+        const bool boot = t > 0 && terminal_value_dev;
+        A.tobs = boot ? terminal_obs_dev + (size_t)(t - 1) * n * kObsDim : nullptr;
+        A.tdone = boot ? done_dev + (size_t)(t - 1) * n : nullptr;
+        A.tcomplete = boot ? complete_dev + (size_t)(t - 1) * n : nullptr;
+        A.tvalue = boot ? terminal_value_dev + (size_t)(t - 1) * n : nullptr;
+        const int ra = policy_launch(p, "meshenv_step_policy_multi", A);
+        if (ra != MESHENV_OK) {
+            h->err = p->err;
+            return ra;
+        }
+        if (last) break;
+        const int rc = launch_step(h, 1, A.actions, obs_dev + (size_t)(t + 1) * n * kObsDim, reward_dev + (size_t)t * n,
+                                   done_dev + (size_t)t * n, complete_dev + (size_t)t * n,
+                                   terminal_obs_dev ? terminal_obs_dev + (size_t)t * n * kObsDim : nullptr, auto_reset);
+        if (rc != MESHENV_OK) return rc;
+    }
+    return MESHENV_OK;
+}
 
 }  // extern "C"

@@ -553,6 +553,47 @@ class MeshVecEnv:
         self.reward.copy_(out["reward"][T - 1]); self.done.copy_(out["done"][T - 1]); self.complete.copy_(out["complete"][T - 1])
         return out
 
+    def collect_rollout(self, policy, T: int, seed: int = 0, counter: int = 0, deterministic: bool = False):
+        """T vector steps of the closed loop with a FusedPolicy (PPO / A2C / TD3 kinds) in one C call
+        (meshenv_step_policy_multi: a policy launch and a step launch per vector step, no host synchronisation).  The
+        policy of step t samples with noise counter counter + t (Philox, as FusedPolicy.sample), or takes eps = 0 when
+        deterministic.  Returns a dict of CUDA histories: obs [T, n, 18] (what each action was chosen on), actions /
+        buffer_actions [T, n, 3], eps [T, n, 3] (stochastic only), reward [T, n] float64, done / complete [T, n] uint8,
+        terminal_obs [T, n, 18] (zeros where not done); actor-critic kind also log_prob / value [T, n], terminal_value
+        [T, n] (V(terminal obs) where done and not complete -- SB3's TimeLimit.truncated bootstrap -- else 0) and last_value
+        [n] (V of the observation after step T - 1).  env.obs / reward / done / complete end as after T single steps."""
+        t = self._torch
+        n, T = self.num_envs, int(T)
+        if T <= 0:
+            raise ValueError("T must be positive")
+        if policy.device != self.device:
+            raise ValueError(f"policy is on {policy.device}, the envs on {self.device}")
+        f32 = dict(dtype=t.float32, device=self.device)
+        obs = t.empty((T + 1, n, _capi.OBS_DIM), **f32)
+        obs[0].copy_(self.obs)
+        out = dict(obs=obs[:T], actions=t.empty((T, n, 3), **f32), buffer_actions=t.empty((T, n, 3), **f32),
+                   reward=t.empty((T, n), dtype=t.float64, device=self.device),
+                   done=t.empty((T, n), dtype=t.uint8, device=self.device),
+                   complete=t.empty((T, n), dtype=t.uint8, device=self.device),
+                   terminal_obs=t.zeros((T, n, _capi.OBS_DIM), **f32))
+        if not deterministic:
+            out["eps"] = t.empty((T, n, 3), **f32)
+        if policy.kind == "actor_critic":
+            out.update(log_prob=t.empty((T, n), **f32), value=t.empty((T, n), **f32),
+                       terminal_value=t.empty((T, n), **f32), last_value=t.empty(n, **f32))
+        ptr = lambda k: out[k].data_ptr() if k in out else None   # noqa: E731
+        self._bind_stream()
+        policy._bind_stream()
+        rc = self._L.meshenv_step_policy_multi(self._handle, policy._h, T, obs.data_ptr(), 0 if deterministic else 1,
+                                               C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(counter & (2 ** 64 - 1)),
+                                               ptr("actions"), ptr("buffer_actions"), ptr("log_prob"), ptr("value"), ptr("eps"),
+                                               ptr("reward"), ptr("done"), ptr("complete"), ptr("terminal_obs"),
+                                               ptr("terminal_value"), ptr("last_value"), 1 if self.auto_reset else 0)
+        self._check(rc, "meshenv_step_policy_multi")
+        self.obs.copy_(obs[T])      # the env's current observation / flags, as after T single steps
+        self.reward.copy_(out["reward"][T - 1]); self.done.copy_(out["done"][T - 1]); self.complete.copy_(out["complete"][T - 1])
+        return out
+
     def extract_samples(self, n_neighbor: int = 2, n_radius: int = 3, radius: float = 4.0, index: int = 1,
                         quality_threshold: float = 0.7, which: str = "current", mask=None):
         """MeshGeneration.extract_samples_2 (general/mesh.py:1438-1489) for the generated mesh of every env, on the device
