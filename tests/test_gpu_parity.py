@@ -296,35 +296,87 @@ def test_speculative_group_kernel_variant(torch_cuda, monkeypatch):
     assert st["valid"] > 0.1 * n * T and st["obs_mismatch"] <= 1e-6 * st["obs_total"]
 
 
-def test_record_first_staging_equals_full_staging(torch_cuda, monkeypatch):
-    """Throughput regime (>= 8192 envs): a step whose rule -1 / +1 quad is memoised as rejected is answered from the
-    64-byte record alone, without staging the ring (MESHENV_LAZY overrides the size rule).  Outputs and state must be
-    bit-identical to the full path, step by step, including the 100-failure truncations that path has to leave alone."""
-    torch = torch_cuda
-    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, boundary, random_domain
-    doms = [boundary(0), boundary(-1)] + [random_domain(300 + k) for k in range(6)]
-    n, T = 16384, 260          # long enough for envs to reach failed_num = 100
-    env_domain = (np.arange(n) % len(doms)).astype(np.int32)
+def _staging_ab(torch, monkeypatch, doms, env_domain, T, want_full, want_lazy, seed, shadow=64):
+    """Two handles of the same batch, one built under MESHENV_LAZY=0 / MESHENV_LIGHT=0 (full staging), one under =1 / =1
+    (record-first, key-less staging): meshenv_create reads the variables once, so they are set before each handle is
+    built.  Outputs and state bit-identical step by step.  Then `shadow` envs (half of them among those that were
+    truncated, if any) are replayed by the CPU oracle on the recorded actions: done / complete exact, obs / reward within
+    TOL.  Returns (truncations, truncations among the shadowed envs)."""
+    from oracle.ref_lib import RefBatch, RefEnv
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    n = len(env_domain)
+    monkeypatch.setenv("MESHENV_LAZY", "0")
+    monkeypatch.setenv("MESHENV_LIGHT", "0")
     full = MeshVecEnv(doms, env_domain=env_domain)
+    monkeypatch.setenv("MESHENV_LAZY", "1")
+    monkeypatch.setenv("MESHENV_LIGHT", "1")       # ... and the ring staged without its candidate keys / stamps
     lazy = MeshVecEnv(doms, env_domain=env_domain)
-    assert full.step_kernel.startswith("meshenv::k_step<false, true, false")
-    g = torch.Generator(device="cuda"); g.manual_seed(5)
+    monkeypatch.delenv("MESHENV_LAZY")
+    monkeypatch.delenv("MESHENV_LIGHT")
+    assert full.step_kernel == want_full and lazy.step_kernel == want_lazy
+    assert full.auto_reset and lazy.auto_reset
+    obs0 = lazy.obs.cpu().numpy()
+    g = torch.Generator(device="cuda"); g.manual_seed(seed)
     lo = torch.tensor([-1.0, -1.5, 0.0], device="cuda"); hi = torch.tensor([1.0, 1.5, 1.5], device="cuda")
+    hist = dict(a=[], o=[], r=[], d=[], c=[])
     truncated = 0
     for t in range(T):
         a = (lo + (hi - lo) * torch.rand((n, 3), device="cuda", generator=g)).contiguous()
-        monkeypatch.setenv("MESHENV_LAZY", "0")
-        monkeypatch.setenv("MESHENV_LIGHT", "0")
         o1, r1, d1, c1 = [x.clone() for x in full.step(a)]
-        monkeypatch.setenv("MESHENV_LAZY", "1")
-        monkeypatch.setenv("MESHENV_LIGHT", "1")       # ... and the ring staged without its candidate keys / stamps
-        o2, r2, d2, c2 = lazy.step(a)
+        o2, r2, d2, c2 = [x.clone() for x in lazy.step(a)]
         assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2) and torch.equal(c1, c2), t
         truncated += int(((d1 != 0) & (c1 == 0)).sum())
-    assert truncated > 0
+        for k, v in zip("aordc", (a, o2, r2, d2, c2)):
+            hist[k].append(v)
     c_full, c_lazy = full.counters(), lazy.counters()
     assert c_full == c_lazy and c_full["valid"] > 0
     for k in range(0, n, 997):
         s1, s2 = full.get_state(k), lazy.get_state(k)
         assert s1["failed_num"] == s2["failed_num"] and np.array_equal(s1["ring_ids"], s2["ring_ids"]) and s1["n_elem"] == s2["n_elem"]
     full.close(); lazy.close()
+    # the oracle leg
+    d_all, c_all = torch.stack(hist["d"]).cpu().numpy(), torch.stack(hist["c"]).cpu().numpy()
+    trunc_env = np.flatnonzero(((d_all != 0) & (c_all == 0)).any(axis=0))
+    pick = [int(k) for k in np.unique(trunc_env[np.linspace(0, len(trunc_env) - 1, shadow // 2).astype(np.int64)])] if len(trunc_env) else []
+    pick += [k for k in np.unique(np.linspace(0, n - 1, shadow).astype(np.int64)).tolist() if k not in pick][:shadow - len(pick)]
+    pick = np.array(pick, dtype=np.int64)
+    assert len(pick) == shadow and len(np.intersect1d(pick, trunc_env)) >= min(shadow // 2, len(trunc_env))
+    idx = torch.from_numpy(pick).cuda()
+    batch = RefBatch([RefEnv.from_points(doms[env_domain[k]], cap_new=64) for k in pick])
+    assert np.array_equal(obs0[pick], batch.reset())
+    shadow_truncated = 0
+    for t in range(T):
+        o_ref, r_ref, d_ref, c_ref = batch.step(hist["a"][t][idx].cpu().numpy(), auto_reset=True, threads=16)
+        assert np.array_equal(d_all[t][pick], d_ref) and np.array_equal(c_all[t][pick], c_ref), t
+        assert np.abs(hist["o"][t][idx].cpu().numpy().astype(np.float64) - o_ref).max() <= TOL, t
+        assert np.abs(hist["r"][t][idx].cpu().numpy() - r_ref).max() <= TOL, t
+        shadow_truncated += int(((d_ref != 0) & (c_ref == 0)).sum())
+    return truncated, shadow_truncated
+
+
+def test_record_first_staging_equals_full_staging(torch_cuda, monkeypatch):
+    """Throughput regime (>= 8192 envs): a step whose rule -1 / +1 quad is memoised as rejected is answered from the
+    64-byte record alone, without staging the ring (MESHENV_LAZY overrides the size rule).  Outputs and state must be
+    bit-identical to the full path, step by step, including the 100-failure truncations that path has to leave alone;
+    64 envs shadowed by the oracle through those truncations."""
+    from reinforcementlearning4meshgeneration_amd import boundary, random_domain
+    doms = [boundary(0), boundary(-1)] + [random_domain(300 + k) for k in range(6)]
+    n, T = 16384, 260          # long enough for envs to reach failed_num = 100
+    env_domain = (np.arange(n) % len(doms)).astype(np.int32)
+    truncated, shadow_truncated = _staging_ab(torch_cuda, monkeypatch, doms, env_domain, T,
+                                              "meshenv::k_step<false, true, false, false, false>",
+                                              "meshenv::k_step<false, true, false, false, true>", 5)
+    print("record-first staging (mixed): truncations", truncated, "in the oracle shadow", shadow_truncated)
+    assert truncated > 0 and shadow_truncated > 0
+
+
+def test_record_first_staging_equals_full_staging_small_rings(torch_cuda, monkeypatch):
+    """The same A/B with every ring <= 64 (16384 x boundary(0)): the kSmall instantiations, k_step<false, true, false,
+    true, false> against k_step<false, true, false, true, true>."""
+    from reinforcementlearning4meshgeneration_amd import boundary
+    n, T = 16384, 260
+    truncated, shadow_truncated = _staging_ab(torch_cuda, monkeypatch, [boundary(0)], np.zeros(n, np.int32), T,
+                                              "meshenv::k_step<false, true, false, true, false>",
+                                              "meshenv::k_step<false, true, false, true, true>", 6)
+    print("record-first staging (small rings): truncations", truncated, "in the oracle shadow", shadow_truncated)
+    assert truncated > 0 and shadow_truncated > 0
