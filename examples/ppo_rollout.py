@@ -2,12 +2,14 @@
 """PPO rollout collection on the device: the reference's PPO recipe (rl/baselines/RL_Mesh.py:113-228: MlpPolicy, ReLU,
 net_arch dict(pi=[128, 128], vf=[128, 128])) as a FusedPolicy, T = 128 vector steps on 4096 envs in one
 MeshVecEnv.collect_rollout call, then SB3's bootstrap of truncated episodes and GAE (RolloutBuffer.compute_returns_and_advantage)
-in torch on the returned histories.
+on the device in the same call (collect_rollout(..., gamma=0.99): one k_gae launch on the rollout's stream).  --torch-gae also
+runs the eager torch loop below on the same histories and prints its largest difference from the device result (0: the
+kernel is bit-identical to it).
 
 With Stable-Baselines3 installed the policy is SB3's own (``PPO("MlpPolicy", ...).policy`` through FusedPolicy.from_sb3);
 without it -- or with --dry-run -- the same torch modules are built by hand, so the rollout path runs either way.
 
-    python examples/ppo_rollout.py [--envs 4096] [--T 128] [--domain boundary0] [--dry-run]
+    python examples/ppo_rollout.py [--envs 4096] [--T 128] [--domain boundary0] [--dry-run] [--torch-gae]
 """
 import argparse
 import json
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--T", type=int, default=128)
     ap.add_argument("--domain", default="boundary0")
     ap.add_argument("--dry-run", action="store_true", help="no SB3: the same policy built from plain torch modules")
+    ap.add_argument("--torch-gae", action="store_true", help="also run the torch GAE loop and print its difference")
     args = ap.parse_args()
     import torch
 
@@ -74,20 +77,24 @@ def main():
         pi, vf, action_net, value_net, log_std = torch_policy(torch)
         policy, source = FusedPolicy.actor_critic(pi, vf, action_net, value_net, log_std, activation="relu"), "torch modules"
     env.reset_tensor()
-    out = env.collect_rollout(policy, args.T, seed=999, counter=0)      # warm-up (and the first rollout)
+    out = env.collect_rollout(policy, args.T, seed=999, counter=0, gamma=0.99)      # warm-up (and the first rollout)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = env.collect_rollout(policy, args.T, seed=999, counter=args.T)
+    out = env.collect_rollout(policy, args.T, seed=999, counter=args.T, gamma=0.99, gae_lambda=0.95)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    adv, returns = gae(torch, out)
+    adv, returns = out["advantages"], out["returns"]
+    extra = {}
+    if args.torch_gae:
+        t_adv, t_ret = gae(torch, out, 0.99, 0.95)
+        extra["max_abs_diff_vs_torch_gae"] = max(float((adv - t_adv).abs().max()), float((returns - t_ret).abs().max()))
     done = out["done"].bool()
     truncated = done & (out["complete"] == 0)
     print(json.dumps(dict(policy=source, envs=args.envs, T=args.T, us_per_vector_step=round(1e6 * dt / args.T, 2),
                           env_steps_per_s=round(args.envs * args.T / dt), episodes_ended=int(done.sum()),
                           truncated=int(truncated.sum()), mean_reward=float(out["reward"].mean()),
                           mean_log_prob=float(out["log_prob"].mean()), mean_value=float(out["value"].mean()),
-                          advantage_std=float(adv.std()), mean_return=float(returns.mean()))))
+                          advantage_std=float(adv.std()), mean_return=float(returns.mean()), **extra)))
     policy.close()
     env.close()
 

@@ -535,6 +535,24 @@ int meshenv_step_policy_multi(MeshEnv *h, MeshPolicy *p, int T, float *obs_dev, 
                               float *terminal_value_dev, float *last_value_dev, int auto_reset);
 
 /*
+ * Generalised advantage estimation over T rows of rollout histories (csrc/meshenv_gae.h): SB3's
+ * RolloutBuffer.compute_returns_and_advantage (GAE, SB3 2.x) with collect_rollouts' TimeLimit.truncated bootstrap
+ * (rewards += gamma * V(terminal obs)) in front -- what examples/ppo_rollout.py::gae does in torch, bit-identical to that
+ * float32 loop (g = (float)gamma, gl = (float)(gamma * gae_lambda), no fused multiply-add, denormals kept):
+ *   r = (float)reward[t] (+ g * terminal_value[t] where terminal_value_dev is given), nnt = 1 - (done[t] != 0),
+ *   delta = (r + (g * next_value) * nnt) - value[t] with next_value = value[t + 1], or last_value at t = T - 1,
+ *   last = delta + (gl * nnt) * last, from t = T - 1 down to 0 with last = 0 after T - 1.
+ * Every history is [T][n_envs] row-major, as meshenv_step_policy_multi writes it: reward_dev float64, value_dev float32,
+ * done_dev uint8, terminal_value_dev float32 (nullable), last_value_dev [n_envs].  Outputs: advantage_dev = last,
+ * return_dev = last + value[t] and buffer_reward_dev = r (the bootstrapped float32 reward the buffer stores; both nullable),
+ * none of which may overlap an input or each other.  One launch on the handle's stream, no host synchronisation.
+ * MESHENV_E_ARG for T < 1, a NULL required pointer, overlapping outputs, or a gamma / gae_lambda outside [0, 1] (NaN included).
+ */
+int meshenv_gae(MeshEnv *h, int T, const double *reward_dev, const float *value_dev, const uint8_t *done_dev,
+                const float *terminal_value_dev, const float *last_value_dev, double gamma, double gae_lambda,
+                float *advantage_dev, float *return_dev, float *buffer_reward_dev);
+
+/*
  * MeshGeneration.extract_samples_2(meshes, n_neighbor, n_radius, radius, index, quality_threshold), general/mesh.py:1438-1489
  * (the data-preparation step of the ANN scripts: general/EBRD.py:414, 579 with (2, 3, radius 4, index 1) and
  * general/post_processing.py:532 with (3, 3, radius 6, index 5)) for the generated mesh of EVERY env in one launch

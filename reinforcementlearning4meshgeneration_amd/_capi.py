@@ -47,7 +47,7 @@ EXPORTS = [
     "meshenv_libm_exact", "meshenv_create_random_density", "meshenv_density_rings",
     "meshenv_step_actor_multi", "meshenv_extract_samples", "meshenv_atan2_exact", "meshenv_quad_quality",
     "meshenv_policy_create", "meshenv_policy_destroy", "meshenv_policy_set_stream", "meshenv_policy_load",
-    "meshenv_policy_forward", "meshenv_step_policy_multi", "meshenv_policy_last_error",
+    "meshenv_policy_forward", "meshenv_step_policy_multi", "meshenv_policy_last_error", "meshenv_gae",
 ]
 
 
@@ -156,6 +156,8 @@ def load():
     L.meshenv_policy_load.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 15
     L.meshenv_policy_forward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
     L.meshenv_step_policy_multi.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 11 + [C.c_int]
+    L.meshenv_gae.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
+    L.meshenv_gae.restype = C.c_int
     for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
                  "meshenv_step_policy_multi"):
         getattr(L, name).restype = C.c_int

@@ -24,6 +24,7 @@
 #include "meshenv_samples.h"
 #include "meshenv_fused.h"
 #include "meshenv_policy.h"
+#include "meshenv_gae.h"
 
 using namespace meshenv;
 
@@ -2186,6 +2187,44 @@ int meshenv_step_policy_multi(MeshEnv *h, MeshPolicy *p, int T, float *obs_dev, 
                                    terminal_obs_dev ? terminal_obs_dev + (size_t)t * n * kObsDim : nullptr, auto_reset);
         if (rc != MESHENV_OK) return rc;
     }
+    return MESHENV_OK;
+}
+
+int meshenv_gae(MeshEnv *h, int T, const double *reward_dev, const float *value_dev, const uint8_t *done_dev,
+                const float *terminal_value_dev, const float *last_value_dev, double gamma, double gae_lambda,
+                float *advantage_dev, float *return_dev, float *buffer_reward_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (T < 1) return fail_arg(h, "meshenv_gae: T >= 1 is required");
+    if (!reward_dev || !value_dev || !done_dev || !last_value_dev || !advantage_dev)
+        return fail_arg(h, "meshenv_gae: reward, value, done, last_value and advantage are required");
+    if (!(gamma >= 0.0 && gamma <= 1.0) || !(gae_lambda >= 0.0 && gae_lambda <= 1.0))
+        return fail_arg(h, "meshenv_gae: gamma and gae_lambda must be finite and in [0, 1]");
+    const size_t n = (size_t)h->n_envs, tn = (size_t)T * n;
+    struct Range { const void *p; size_t bytes; };
+    const Range in[] = {{reward_dev, tn * 8}, {value_dev, tn * 4}, {done_dev, tn}, {terminal_value_dev, tn * 4},
+                        {last_value_dev, n * 4}};
+    const Range out[] = {{advantage_dev, tn * 4}, {return_dev, tn * 4}, {buffer_reward_dev, tn * 4}};
+    auto overlap = [](const Range &x, const Range &y) {
+        const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+        return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+    };
+    for (int i = 0; i < 3; i++) {
+        for (const Range &r : in)
+            if (overlap(out[i], r)) return fail_arg(h, "meshenv_gae: an output overlaps an input");
+        for (int j = 0; j < i; j++)
+            if (overlap(out[i], out[j])) return fail_arg(h, "meshenv_gae: two outputs overlap");
+    }
+    MESHENV_ON_DEVICE(h);
+    GaeArgs A{};
+    A.T = T; A.n = h->n_envs;
+    A.g = (float)gamma; A.gl = (float)(gamma * gae_lambda);
+    A.reward = reward_dev; A.value = value_dev; A.done = done_dev; A.tvalue = terminal_value_dev; A.last_value = last_value_dev;
+    A.adv = advantage_dev; A.ret = return_dev; A.brew = buffer_reward_dev;
+    const bool long_t = T > kGaeShortT;   // the two workgroup shapes of meshenv_gae.h
+    hipLaunchKernelGGL(long_t ? k_gae<512> : k_gae<256>, dim3((unsigned)((n + kGaeEnvs - 1) / kGaeEnvs)), dim3(long_t ? 512 : 256),
+                       0, h->stream, A);
+    HIP_TRY(h, hipGetLastError());
     return MESHENV_OK;
 }
 

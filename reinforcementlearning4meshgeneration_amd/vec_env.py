@@ -74,6 +74,12 @@ def smoothing_log_capacity(ring_len: int, want: int = 4096) -> int:
     return int(max(16, min(want, by_interior, by_front, by_final, 65535 - cap)))
 
 
+def _check_gae_coefficients(gamma, gae_lambda):
+    for name, v in (("gamma", gamma), ("gae_lambda", gae_lambda)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{name} must be a finite number in [0, 1], got {v!r}")
+
+
 def make_spaces():
     """(observation_space, action_space) with the reference's bounds; real gymnasium/gym Boxes if available."""
     box = None
@@ -553,7 +559,8 @@ class MeshVecEnv:
         self.reward.copy_(out["reward"][T - 1]); self.done.copy_(out["done"][T - 1]); self.complete.copy_(out["complete"][T - 1])
         return out
 
-    def collect_rollout(self, policy, T: int, seed: int = 0, counter: int = 0, deterministic: bool = False):
+    def collect_rollout(self, policy, T: int, seed: int = 0, counter: int = 0, deterministic: bool = False,
+                        gamma: Optional[float] = None, gae_lambda: float = 0.95):
         """T vector steps of the closed loop with a FusedPolicy (PPO / A2C / TD3 kinds) in one C call
         (meshenv_step_policy_multi: a policy launch and a step launch per vector step, no host synchronisation).  The
         policy of step t samples with noise counter counter + t (Philox, as FusedPolicy.sample), or takes eps = 0 when
@@ -561,13 +568,20 @@ class MeshVecEnv:
         buffer_actions [T, n, 3], eps [T, n, 3] (stochastic only), reward [T, n] float64, done / complete [T, n] uint8,
         terminal_obs [T, n, 18] (zeros where not done); actor-critic kind also log_prob / value [T, n], terminal_value
         [T, n] (V(terminal obs) where done and not complete -- SB3's TimeLimit.truncated bootstrap -- else 0) and last_value
-        [n] (V of the observation after step T - 1).  env.obs / reward / done / complete end as after T single steps."""
+        [n] (V of the observation after step T - 1).  env.obs / reward / done / complete end as after T single steps.
+        With a gamma (actor-critic kind only) the same stream then runs compute_gae(gamma, gae_lambda) on these histories,
+        and the dict also holds its advantages / returns / rewards [T, n] float32 and episode_starts [T, n] float32 (row 0
+        the env's done before the call, row t done[t - 1]): what SB3's RolloutBuffer stores."""
         t = self._torch
         n, T = self.num_envs, int(T)
         if T <= 0:
             raise ValueError("T must be positive")
         if policy.device != self.device:
             raise ValueError(f"policy is on {policy.device}, the envs on {self.device}")
+        if gamma is not None:
+            if policy.kind != "actor_critic":
+                raise ValueError(f"gamma needs the values of an actor-critic policy; this one is {policy.kind}")
+            _check_gae_coefficients(gamma, gae_lambda)
         f32 = dict(dtype=t.float32, device=self.device)
         obs = t.empty((T + 1, n, _capi.OBS_DIM), **f32)
         obs[0].copy_(self.obs)
@@ -584,6 +598,9 @@ class MeshVecEnv:
         ptr = lambda k: out[k].data_ptr() if k in out else None   # noqa: E731
         self._bind_stream()
         policy._bind_stream()
+        if gamma is not None:
+            starts = t.empty((T, n), **f32)
+            starts[0].copy_(self.done)
         rc = self._L.meshenv_step_policy_multi(self._handle, policy._h, T, obs.data_ptr(), 0 if deterministic else 1,
                                                C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(counter & (2 ** 64 - 1)),
                                                ptr("actions"), ptr("buffer_actions"), ptr("log_prob"), ptr("value"), ptr("eps"),
@@ -592,6 +609,52 @@ class MeshVecEnv:
         self._check(rc, "meshenv_step_policy_multi")
         self.obs.copy_(obs[T])      # the env's current observation / flags, as after T single steps
         self.reward.copy_(out["reward"][T - 1]); self.done.copy_(out["done"][T - 1]); self.complete.copy_(out["complete"][T - 1])
+        if gamma is not None:
+            starts[1:].copy_(out["done"][:T - 1])
+            out.update(self._gae(out["reward"], out["value"], out["done"], out["last_value"], out["terminal_value"], gamma,
+                                 gae_lambda), episode_starts=starts)
+        return out
+
+    def compute_gae(self, reward, value, done, last_value, terminal_value=None, gamma: float = 0.99,
+                    gae_lambda: float = 0.95):
+        """SB3's RolloutBuffer.compute_returns_and_advantage (GAE) with collect_rollouts' bootstrap of truncated episodes
+        (rewards += gamma * terminal_value) in front, in one launch on the device (meshenv_gae, csrc/meshenv_gae.h),
+        bit-identical to that float32 loop (examples/ppo_rollout.py::gae).  reward [T, n] float64, value [T, n] float32,
+        done [T, n] uint8, terminal_value [T, n] float32 or None, last_value [n] float32: contiguous CUDA tensors on the
+        envs' device, [T][n] as collect_rollout returns them (histories of several calls concatenated along T work too).
+        Returns dict(advantages, returns, rewards) [T, n] float32; rewards is the bootstrapped reward SB3 stores."""
+        t = self._torch
+        _check_gae_coefficients(gamma, gae_lambda)
+        n = self.num_envs
+        if not (hasattr(reward, "dim") and reward.dim() == 2 and reward.shape[0] >= 1):
+            raise ValueError("reward must be a [T, n] tensor with T >= 1")
+        T = reward.shape[0]
+        want = dict(reward=(reward, (T, n), t.float64), value=(value, (T, n), t.float32), done=(done, (T, n), t.uint8),
+                    last_value=(last_value, (n,), t.float32))
+        if terminal_value is not None:
+            want["terminal_value"] = (terminal_value, (T, n), t.float32)
+        for name, (x, shape, dtype) in want.items():
+            if not hasattr(x, "dtype") or x.dtype != dtype:
+                raise ValueError(f"{name} must be a {dtype} tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+            if tuple(x.shape) != shape:
+                raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {shape} (num_envs = {n})")
+            if x.device != self.device:
+                raise ValueError(f"{name} is on {x.device}, the envs on {self.device}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        return self._gae(reward, value, done, last_value, terminal_value, gamma, gae_lambda)
+
+    def _gae(self, reward, value, done, last_value, terminal_value, gamma, gae_lambda):
+        t = self._torch
+        T, n = reward.shape
+        f32 = dict(dtype=t.float32, device=self.device)
+        out = dict(advantages=t.empty((T, n), **f32), returns=t.empty((T, n), **f32), rewards=t.empty((T, n), **f32))
+        self._bind_stream()
+        rc = self._L.meshenv_gae(self._handle, T, reward.data_ptr(), value.data_ptr(), done.data_ptr(),
+                                 terminal_value.data_ptr() if terminal_value is not None else None, last_value.data_ptr(),
+                                 float(gamma), float(gae_lambda), out["advantages"].data_ptr(), out["returns"].data_ptr(),
+                                 out["rewards"].data_ptr())
+        self._check(rc, "meshenv_gae")
         return out
 
     def extract_samples(self, n_neighbor: int = 2, n_radius: int = 3, radius: float = 4.0, index: int = 1,
