@@ -27,9 +27,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--domain", default="d1", choices=["d1", "boundary0"])
     ap.add_argument("--deterministic", action="store_true")
-    ap.add_argument("--chunk", type=int, default=32, help="t-steps: vector steps per launch")
+    ap.add_argument("--chunk", type=int, default=32, help="t-steps: vector steps per call")
     ap.add_argument("--actor", default="fused", choices=["t-steps", "one-launch", "fused", "fused-ext-noise", "graph", "eager"],
-                    help="t-steps = --chunk vector steps of the closed loop per launch (meshenv_step_actor_multi); "
+                    help="t-steps = --chunk vector steps of the closed loop per call (meshenv_step_actor_multi); "
                          "one-launch = env step + actor forward in ONE kernel per vector step (meshenv_step_actor); "
                          "fused = the hand-written HIP actor kernel, exploration noise drawn inside it (one launch); "
                          "fused-ext-noise = same kernel fed by torch's normal_() (two launches); graph = the torch MLP captured as one HIP "

@@ -169,8 +169,8 @@ int meshenv_max_ring(const MeshEnv *h);
  * k_step_group<G> (chosen at creation from n_envs, see meshenv_create in csrc/meshenv_hip.hip). */
 int meshenv_group_size(const MeshEnv *h);
 /* Which single-step kernel meshenv_step launches: 0 = k_step<false> (one wave per workgroup), 1 = k_step_group<G>
- * (checks, workgroup barrier, updates dealt over the SIMDs), 2 = k_step_spec<G> (no barrier: an action that survives the
- * cheap exact tests is extracted speculatively by an idle wavefront while its checks finish).
+ * (checks, workgroup barrier, updates dealt over the SIMDs).  2 is retired (it named a speculative CU-group kernel that
+ * measured slower and was removed); the other codes keep their numbers.
  * 3 = k_step<false, ., true>: after a front smoothing (meshenv_smooth with interior = 0, or a meshenv_move that went through
  * smooth_pave) and until the next reset of ALL envs rings may hold vertices off the 1e-4 lattice, whose clockwise angles
  * can sit exactly on a rounding boundary; steps then run the one-wave-per-env kernel in the instantiation that decides
@@ -180,8 +180,7 @@ int meshenv_group_size(const MeshEnv *h);
  * batches whose ring stride is at most 64 slots (every ring pass is one 64-lane pass, no chunk loops).
  * 6 = k_step<false, true, false, true>: the one-wave-per-env kernel of such batches (default geometry constants).
  * 7 / 8 = k_step<false, true, false, false | true, true>: the throughput-regime forms of 0 / 6 (batches staged record-first,
- * from 8192 envs): a rule-0 quad with a corner that cannot be valid is rejected before the point-in-polygon pass.
- * (2 exists in -DMESHENV_DEV builds of the library only.) */
+ * from 8192 envs): a rule-0 quad with a corner that cannot be valid is rejected before the point-in-polygon pass. */
 int meshenv_step_kernel(const MeshEnv *h);
 /* The smoothing kernels evaluate `x ** 2` like the reference's libm (CPython's float ** 2 is pow(x, 2.0), which glibc does
  * not round correctly: it differs from x * x in 0.085 % of the arguments) through a restatement of glibc's pow
@@ -572,16 +571,14 @@ int meshenv_extract_samples(MeshEnv *h, int which, const uint8_t *mask_dev, int 
                             double quality_threshold, int64_t *count_dev, uint8_t *status_dev, const int64_t *offsets_dev,
                             double *samples_dev, double *outputs_dev, double *types_dev);
 
-/* T vector steps of the closed loop in ONE launch (csrc/meshenv_fused.h, k_step_group_actor_T): the workgroups of the
- * fused kernel never talk to each other, so each loops [step its 16 envs -> actor forward] T times on its own -- one launch
- * ramp per T steps, and the workgroups drift apart instead of waiting, every step, for the CU with the most extractions.
+/* T vector steps of the closed loop in one call: T x meshenv_step_actor on slices of [T]-shaped histories (one launch for
+ * all T steps measured slower).
  *   actions_dev   [T+1][n][3]  slice 0 = the actions of the first step (input); slice t + 1 = the policy's actions on
  *                              the observations of step t (output: slice T feeds the next call)
  *   obs_dev [T][n][18], reward_dev [T][n], done_dev [T][n], complete_dev [T][n], terminal_obs_dev [T][n][18] (nullable),
  *   eps_out_dev [T][n][3] (nullable): slice t = what meshenv_step_actor would have written at step t; the noise counter of
  *   step t is counter + t.
- * Bit-identical to T calls of meshenv_step_actor(counter + t) on the slices (that is also what runs when the batch is not
- * on the fused kernel: T x the one- or two-launch path).  The reference has no counterpart: its loop is SB3's
+ * Bit-identical to T calls of meshenv_step_actor(counter + t) on the slices.  The reference has no counterpart: its loop is SB3's
  * collect_rollouts calling policy and env.step() alternately (rl/baselines/RL_Mesh.py:186-228). */
 int meshenv_step_actor_multi(MeshEnv *h, MeshActor *a, int T, float *actions_dev, float *obs_dev, double *reward_dev, uint8_t *done_dev,
                          uint8_t *complete_dev, float *terminal_obs_dev, int auto_reset, int sample, uint64_t seed, uint64_t counter,

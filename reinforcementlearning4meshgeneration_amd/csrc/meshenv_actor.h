@@ -149,7 +149,7 @@ __device__ __forceinline__ void actor_forward_tile(const ActorWeights &W, ActorH
                                                    float *__restrict__ eps_out, float *lds, int t, int n_threads)
 {
     float *bufA = lds, *bufB = lds + kActEnvs * kActStride, *eps_lds = lds + 2 * kActEnvs * kActStride;
-    const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);   // (k_step_group_actor_T passes an opaque thread id)
+    const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);   // (t >> 6 is wave-uniform: keep it in an SGPR)
     const bool worker = wave < kActWaves;
     LayerRegs<2> &r1 = hd.r1;
     LayerRegs<8> &r2 = hd.r2;

@@ -130,7 +130,6 @@ struct MeshEnv {
     bool default_params = true;  // geometry constants are the reference's: literal-constant kernel instantiations
     size_t lds = 0;
     int n_cu = 256;       // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-    bool spec = false;    // single-step kernel = k_step_spec (speculative extraction, no workgroup barrier)
     int group = 1;        // environments (wavefronts) per workgroup of the single-step kernel
     size_t group_lds = 0;
     int2 *env_lds = nullptr;   // ragged LDS packing of the CU-group kernel: [n_envs] (byte offset in the workgroup, ring slots), or null
@@ -153,7 +152,6 @@ struct MeshEnv {
     bool front_moved = false;          // a front smoother ran since the last full reset: rings may hold off-lattice vertices
     bool smooth_final_ready = false;
     bool fused_ready = false;          // k_step_group_actor's LDS attribute set
-    bool fused_T_ready = false;        // k_step_group_actor_T's (-DMESHENV_DEV build only)
     int stage_bits = 0;                // bits 1 | 2 of k_step's auto_reset argument: record-first / key-less staging (set at creation)
     bool samples_ready = false;        // k_extract_samples' LDS attribute set
     // move() API state, allocated by the first meshenv_move: not_valid_points per env
@@ -372,13 +370,7 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
             while (g * 2 <= n_envs / n_cu && g * 2 <= 16) g *= 2;
             want = g >= 8 ? g : 1;
         }
-        // (G = 4, the speculative kernel and the T-step closed-loop kernel are measured-slower experiments: they exist in the
-        // -DMESHENV_DEV build that tools/ and tests/test_gpu_variants.py compile, not in the shipped library)
-#ifdef MESHENV_DEV
-        for (int g : {16, 8, 4})
-#else
         for (int g : {16, 8})
-#endif
             if (g <= want && group_lds_bytes(cap, g) <= 150 * 1024) { G = g; break; }
         if (!force && (G < 8 || n_envs > n_cu * G)) G = 1;  // LDS forced a smaller group: more than one workgroup per CU
         // Ragged packing: sixteen rings of the LONGEST stride do not fit, sixteen rings of their own lengths may (mixed
@@ -413,15 +405,6 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
         if (!h->default_params) h->env_lds_host.clear();
         h->group = G;
         h->group_lds = h->env_lds_host.empty() ? group_lds_bytes(cap, G) : (size_t)h->ho_off + 16 * sizeof(Handoff);
-        // The speculative form of the CU-group kernel (k_step_spec: two ring buffers per env, no workgroup barrier) is
-        // opt-in, MESHENV_SPEC=1: measured on MI355X at 4096 x boundary() it takes 16.7 us per launch against 15.5 us
-        // for the barrier + deal form (rocprofv3; DESIGN.md section 5 says why), so the default stays k_step_group.
-#ifdef MESHENV_DEV
-        const char *spec_env = getenv("MESHENV_SPEC");
-        h->spec = h->env_lds_host.empty() && (G == 16 || G == 8) && spec_lds_bytes(cap, G) <= 150 * 1024 && spec_env && atoi(spec_env) == 1;
-#else
-        h->spec = false;
-#endif
         // staging mode of the one-wave-per-env step kernel (bits 1, 2 of its auto_reset argument), decided once per handle:
         // record-first staging (memoised rejections never load their ring) -- measured never slower from 8192 envs up,
         // +9..15 % at 32 768+; the ring staged without candidate keys / stamps -- +0..3 % from 32 768 envs, -2 % at 8192.
@@ -433,23 +416,11 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
             const bool light = lt ? atoi(lt) != 0 : (lazy && n_envs >= 16384);
             h->stage_bits = (lazy ? 2 : 0) | (light ? 4 : 0);
         }
-#ifdef MESHENV_DEV
-        if (h->spec) {
-            h->group_lds = spec_lds_bytes(cap, G);
-            if (h->group_lds > 64 * 1024) {
-                const void *fn = G == 16 ? (const void *)k_step_spec<16, true> : (const void *)k_step_spec<8, true>;
-                CREATE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-            }
-        } else
-#endif
         if (G > 1 && h->group_lds > 64 * 1024) {
             const bool ragged = !h->env_lds_host.empty();
             const void *fn = ragged ? (const void *)k_step_group<16, true, true>
                              : G == 16 ? (const void *)k_step_group<16, true> : (const void *)k_step_group<8, true>;
             if (!ragged && cap <= 64) fn = G == 16 ? (const void *)k_step_group<16, true, false, true> : (const void *)k_step_group<8, true, false, true>;
-#ifdef MESHENV_DEV
-            if (G == 4) fn = (const void *)k_step_group<4, true>;
-#endif
             CREATE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
         }
     }
@@ -859,11 +830,7 @@ int meshenv_step_kernel(const MeshEnv *h)
         const bool pre = h->default_params && (h->stage_bits & 2);
         return h->default_params && h->cap <= 64 ? (pre ? 8 : 6) : (pre ? 7 : 0);
     }
-    if (h->spec) return 2;
     if (h->env_lds) return 4;
-#ifdef MESHENV_DEV
-    if (h->group == 4) return 1;
-#endif
     return h->cap <= 64 ? 5 : 1;
 }
 int meshenv_libm_exact(const MeshEnv *h) { return h ? h->libm_exact : MESHENV_E_ARG; }
@@ -1216,12 +1183,6 @@ static int launch_step(MeshEnv *h, int n_steps, const float *actions_dev, float 
         A.env_lds = h->env_lds;
         A.ho_off = h->ho_off;
         A.pad = 0;
-#ifdef MESHENV_DEV
-        if (h->spec && G == 16) hipLaunchKernelGGL((k_step_spec<16, true>), grid, block, h->group_lds, h->stream, A);
-        else if (h->spec && G == 8) hipLaunchKernelGGL((k_step_spec<8, true>), grid, block, h->group_lds, h->stream, A);
-        else if (G == 4) hipLaunchKernelGGL((k_step_group<4, true>), grid, block, h->group_lds, h->stream, A);
-        else
-#endif
         if (h->env_lds) hipLaunchKernelGGL((k_step_group<16, true, true>), grid, block, h->group_lds, h->stream, A);   // ragged: G == 16 only
         else if (h->cap <= 64 && G == 16) hipLaunchKernelGGL((k_step_group<16, true, false, true>), grid, block, h->group_lds, h->stream, A);
         else if (h->cap <= 64) hipLaunchKernelGGL((k_step_group<8, true, false, true>), grid, block, h->group_lds, h->stream, A);
@@ -1458,23 +1419,6 @@ int meshenv_counters(MeshEnv *h, uint64_t *out_host)
     out_host[3] = sv;
     return MESHENV_OK;
 }
-
-#ifdef MESHENV_SPEC_STATS
-// diagnostic build only: k_step_spec event counts / timestamps (reset = 1 clears them)
-int meshenv_debug_spec_stats(MeshEnv *h, uint64_t *count_host, uint64_t *time_host, int n_envs, int reset)
-{
-    if (!h) return MESHENV_E_ARG;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (count_host) HIP_TRY(h, hipMemcpyFromSymbol(count_host, HIP_SYMBOL(g_spec_count), sizeof(uint64_t) * 16));
-    if (time_host) HIP_TRY(h, hipMemcpyFromSymbol(time_host, HIP_SYMBOL(g_spec_time), sizeof(uint64_t) * 12 * (size_t)n_envs));
-    if (reset) {
-        static uint64_t zeros[65536 * 12];
-        HIP_TRY(h, hipMemcpyToSymbol(HIP_SYMBOL(g_spec_count), zeros, sizeof(uint64_t) * 16));
-        HIP_TRY(h, hipMemcpyToSymbol(HIP_SYMBOL(g_spec_time), zeros, sizeof(uint64_t) * 12 * 65536));
-    }
-    return MESHENV_OK;
-}
-#endif
 
 #ifdef MESHENV_STAMPS
 // diagnostic build only: raw per-env counter records (see k_step)
@@ -1777,7 +1721,7 @@ int meshenv_step_actor(MeshEnv *h, MeshActor *a, const float *actions_dev, float
         h->err = "meshenv_step_actor: env and actor must be on the same device and stream (meshenv_set_stream / meshenv_actor_set_stream)";
         return MESHENV_E_STATE;
     }
-    const bool fusable = h->group == 16 && !h->spec && h->default_params && !h->front_moved && !h->env_lds &&
+    const bool fusable = h->group == 16 && h->default_params && !h->front_moved && !h->env_lds &&
                          h->timing == 0 && !h->reselect_pending && group_actor_lds_bytes(h->cap) <= 160 * 1024;
     if (!fusable) {   // same results by two launches (other batch sizes / ring lengths, timing armed, the
                       // step after meshenv_smooth whose parked re-selection changes the observation the policy reads)
@@ -1854,10 +1798,6 @@ int meshenv_extract_samples(MeshEnv *h, int which, const uint8_t *mask_dev, int 
     return MESHENV_OK;
 }
 
-#ifdef MESHENV_DEV
-static unsigned long long *g_tsteps_dbg = nullptr;
-#endif
-
 int meshenv_step_actor_multi(MeshEnv *h, MeshActor *a, int T, float *actions_dev, float *obs_dev, double *reward_dev, uint8_t *done_dev,
                          uint8_t *complete_dev, float *terminal_obs_dev, int auto_reset, int sample, uint64_t seed, uint64_t counter,
                          float *eps_out_dev)
@@ -1874,64 +1814,17 @@ int meshenv_step_actor_multi(MeshEnv *h, MeshActor *a, int T, float *actions_dev
         return MESHENV_E_STATE;
     }
     const size_t n = (size_t)h->n_envs;
-    // One launch for all T steps (k_step_group_actor_T) measured SLOWER than T fused single-step launches (DESIGN.md section 5,
-    // round 3: 95 spilled VGPRs, 384 B of scratch per lane): that kernel is compiled in the -DMESHENV_DEV build only, where
-    // tools/tsteps_timeline.py and tests/test_gpu_variants.py drive it; the shipped library always takes the step-by-step form.
-#ifdef MESHENV_DEV
-    const bool fusable = h->group == 16 && !h->spec && h->default_params && !h->front_moved && !h->env_lds && h->timing == 0 && !h->reselect_pending &&
-                         group_actor_lds_bytes(h->cap) <= 160 * 1024 && !h->S.msg;
-#else
-    const bool fusable = false;
-#endif
-    if (!fusable || T == 1) {   // the same results step by step
-        for (int t = 0; t < T; t++) {
-            const int rc = meshenv_step_actor(h, a, actions_dev + (size_t)t * n * 3, obs_dev + (size_t)t * n * kObsDim, reward_dev + (size_t)t * n,
-                                              done_dev + (size_t)t * n, complete_dev + (size_t)t * n,
-                                              terminal_obs_dev ? terminal_obs_dev + (size_t)t * n * kObsDim : nullptr, auto_reset, sample, seed,
-                                              counter + (uint64_t)t, actions_dev + (size_t)(t + 1) * n * 3,
-                                              eps_out_dev ? eps_out_dev + (size_t)t * n * 3 : nullptr);
-            if (rc != MESHENV_OK) return rc;
-        }
-        return MESHENV_OK;
+    // step by step: one launch for all T steps measured slower
+    for (int t = 0; t < T; t++) {
+        const int rc = meshenv_step_actor(h, a, actions_dev + (size_t)t * n * 3, obs_dev + (size_t)t * n * kObsDim, reward_dev + (size_t)t * n,
+                                          done_dev + (size_t)t * n, complete_dev + (size_t)t * n,
+                                          terminal_obs_dev ? terminal_obs_dev + (size_t)t * n * kObsDim : nullptr, auto_reset, sample, seed,
+                                          counter + (uint64_t)t, actions_dev + (size_t)(t + 1) * n * 3,
+                                          eps_out_dev ? eps_out_dev + (size_t)t * n * 3 : nullptr);
+        if (rc != MESHENV_OK) return rc;
     }
-#ifdef MESHENV_DEV
-    MESHENV_ON_DEVICE(h);
-    if (!h->fused_T_ready) {
-        HIP_TRY(h, hipFuncSetAttribute((const void *)k_step_group_actor_T<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        h->fused_T_ready = true;
-    }
-    GroupActorArgsT GA;
-    GA.g.S = h->S;
-    GA.g.outs.obs_out = obs_dev; GA.g.outs.reward = reward_dev; GA.g.outs.done = done_dev; GA.g.outs.complete = complete_dev;
-    GA.g.outs.term_obs = terminal_obs_dev;
-    GA.g.actions = actions_dev;
-    GA.g.step0 = (unsigned long long)h->steps_done;
-    GA.g.cap = h->cap;
-    GA.g.env_lds = nullptr; GA.g.ho_off = 0; GA.g.pad = 0;
-    GA.g.auto_reset = auto_reset;
-    GA.W = a->W;
-    GA.eps_out = eps_out_dev;
-    GA.seed = seed; GA.counter = counter;
-    GA.sample = sample ? 1 : 0;
-    GA.T = T;
-    GA.dbg = nullptr;
-    GA.dbg = g_tsteps_dbg;   // nullptr unless tools/tsteps_timeline.py set a stamp buffer (meshenv_dev_set_tsteps_dbg)
-    hipLaunchKernelGGL((k_step_group_actor_T<true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, GA);
-    HIP_TRY(h, hipGetLastError());
-    h->steps_done += (uint64_t)T;
-#endif
     return MESHENV_OK;
 }
-
-#ifdef MESHENV_DEV
-// Dev build only (tools/tsteps_timeline.py): a device buffer of at least grid * T * 4 u64 words that the next
-// meshenv_step_actor_multi launches stamp; nullptr switches the stamps off.  Not part of include/meshenv.h.
-int meshenv_dev_set_tsteps_dbg(unsigned long long *buf_dev)
-{
-    g_tsteps_dbg = buf_dev;
-    return MESHENV_OK;
-}
-#endif
 
 }  // extern "C"
 

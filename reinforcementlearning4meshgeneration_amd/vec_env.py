@@ -372,7 +372,6 @@ class MeshVecEnv:
         (`k_step<false, true, true>`) between a front smoothing and the next reset of all envs."""
         return {0: "meshenv::k_step<false, true, false, false, false>", 6: "meshenv::k_step<false, true, false, true, false>",
                 7: "meshenv::k_step<false, true, false, false, true>", 8: "meshenv::k_step<false, true, false, true, true>", 1: f"meshenv::k_step_group<{self.group_size}, true, false, false>",
-                2: f"meshenv::k_step_spec<{self.group_size}, true>",
                 3: "meshenv::k_step<false, true, true, false, false>",
                 4: "meshenv::k_step_group<16, true, true, false>",
                 5: f"meshenv::k_step_group<{self.group_size}, true, false, true>"}[self._L.meshenv_step_kernel(self._handle)]
@@ -526,9 +525,8 @@ class MeshVecEnv:
 
     def step_actor_T(self, actor, actions0, T: int, seed: int = 0, counter: int = 0, sample: bool = True,
                      want_terminal_obs: bool = False, want_eps: bool = False):
-        """T vector steps of the closed loop (env step + policy) in ONE launch where the batch runs on the fused CU-group
-        kernel (meshenv_step_actor_multi; T x step_actor otherwise, identical results).  actions0: [n, 3] actions of the first
-        step.  Returns a dict of histories: actions [T+1, n, 3] (slice t + 1 = the policy's answer to the observations of
+        """T vector steps of the closed loop (env step + policy) in one call: meshenv_step_actor_multi, which runs T x
+        step_actor on slices of the histories.  actions0: [n, 3] actions of the first step.  Returns a dict of histories: actions [T+1, n, 3] (slice t + 1 = the policy's answer to the observations of
         step t; pass actions[T] as the next call's actions0), obs [T, n, 18], reward [T, n], done [T, n], complete [T, n],
         and terminal_obs [T, n, 18] / eps [T, n, 3] when asked for.  The noise counter of step t is counter + t."""
         t = self._torch

@@ -120,10 +120,10 @@ def test_fused_step_and_actor_equals_the_two_launch_path():
 
 
 def test_t_steps_per_launch_equals_single_step_launches():
-    """meshenv_step_actor_multi: T vector steps of the closed loop (env step + SAC actor) in ONE launch -- every workgroup loops
-    over its own 16 envs -- against T calls of meshenv_step_actor on a second, identical batch: every slice of the
+    """meshenv_step_actor_multi: T vector steps of the closed loop (env step + SAC actor) in one call, into [T]-shaped
+    histories -- against T calls of meshenv_step_actor on a second, identical batch: every slice of the
     observation / reward / flag / terminal-observation / noise histories and of the action history bit-identical, work
-    counters equal; 4096 d1 envs (the fused kernel) over 4 x 24 steps, 4096 boundary() envs, and the step-by-step fallback
+    counters equal; 4096 d1 envs (the fused kernel) over 4 x 24 steps, 4096 boundary() envs, and the two-launch path
     (2048 envs: not the CU-group size)."""
     import os
     import torch
