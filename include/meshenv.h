@@ -552,6 +552,79 @@ int meshenv_gae(MeshEnv *h, int T, const double *reward_dev, const float *value_
                 float *advantage_dev, float *return_dev, float *buffer_reward_dev);
 
 /*
+ * Policy evaluation on the device (csrc/meshenv_eval.h): SB3 2.x's evaluate_policy loop (non-Monitor branch) -- the loop
+ * the reference's evaluation callers run with a deterministic model.predict:
+ *   rl/baselines/CustomizeCallback.py:27-141   every 1000 training steps, to pick best_model
+ *   rl/baselines/testbed.py:150-212            per domain: is_complete, len(generated_meshes), get_quality(e, 4)
+ *   v2/src/mesh_rl/evaluation/eval_loop.py:80-103   {"completed": [...], "n_elements": [...]}
+ * plus the quality report of every finished mesh, taken while it is still archived (meshenv_get_last_episode: one
+ * archived episode per env, replaced when the env's next episode ends).
+ *
+ * MeshEvalBuffers: caller-owned DEVICE memory.  Per env [n_envs]: target (episodes to record, >= 0, unchanged during an
+ * evaluation), offset (first record slot: the exclusive prefix sum of target), and the accumulators count, length, seen,
+ * return, return_raw; short_dev [1] = envs with count < target.  Per episode [sum of target], slot offset[env] + k holding
+ * the env's k-th recorded episode:
+ *   ep_env, ep_domain, ep_step (0-based vector step at which the episode ended), ep_length,
+ *   ep_return      float64 sum of (double)(float)reward: SB3's value (SB3MeshVecEnv hands float32 rewards to
+ *                  evaluate_policy, which adds them into np.zeros(n_envs))
+ *   ep_return_raw  float64 sum of the float64 rewards
+ *   ep_flags       bit 0 is_complete, bit 1 the element log overflowed log_capacity
+ *   ep_n_elements  len(generated_meshes); 0 for an episode that ended without an element (reset_from_domain does not
+ *                  archive it: the archive still holds an older episode, which is not scored); -1 with log_capacity = 0
+ *   ep_archive     nullable: meshenv_get_last_episode's `episodes` value of the archived mesh (0: none), so that a caller
+ *                  can tell whether the archive still holds that episode
+ *   ep_quality     nullable [.][MESHENV_QUALITY_DIM][4]: meshenv_element_quality(which = 1) statistics of the finished mesh,
+ *                  bit for bit as that call would return them right after the step (zeros where n_elements is 0); needs
+ *                  log_capacity > 0 (MESHENV_E_STATE)
+ * obs_dev [n][18], reward_dev [n], done_dev, complete_dev [n] (nullable, all or none): meshenv_evaluate's step buffers --
+ * NULL uses buffers of the handle (allocated by the first call).  Envs past their target keep stepping and are not
+ * recorded, as in SB3.
+ */
+typedef struct MeshEvalBuffers {
+    int32_t struct_size;  /* sizeof(MeshEvalBuffers), for ABI checking */
+    int32_t reserved;
+    const int32_t *target_dev, *offset_dev;
+    int32_t *count_dev, *length_dev, *seen_dev;
+    double *return_dev, *return_raw_dev;
+    int32_t *short_dev;
+    int32_t *ep_env_dev, *ep_domain_dev, *ep_step_dev, *ep_length_dev, *ep_flags_dev, *ep_n_elements_dev, *ep_archive_dev;
+    double *ep_return_dev, *ep_return_raw_dev, *ep_quality_dev;
+    float *obs_dev;
+    double *reward_dev;
+    uint8_t *done_dev, *complete_dev;
+} MeshEvalBuffers;
+
+/* Start of an evaluation, one launch: count / length / return accumulators cleared, seen = the archive counter of every
+ * env, short = envs with target > 0.  Call after the reset that starts the episodes (meshenv_evaluate does both). */
+int meshenv_eval_begin(MeshEnv *h, const MeshEvalBuffers *bufs);
+
+/* One launch after a vector step (meshenv_step, meshenv_step_actor, a step of meshenv_step_policy_multi -- any call whose
+ * reward / done / complete of that step are passed here): adds the rewards, records the episodes that ended (slot
+ * offset + count while count < target), scores their finished meshes when ep_quality_dev is given, and decrements
+ * short_dev when an env reaches its target.  `step` is stored as ep_step.  Stream-ordered, no host synchronisation. */
+int meshenv_eval_tally(MeshEnv *h, const MeshEvalBuffers *bufs, int step, const double *reward_dev, const uint8_t *done_dev,
+                       const uint8_t *complete_dev);
+
+/*
+ * The whole loop in one call: resets every env (evaluate_policy's env.reset()), meshenv_eval_begin, then per vector step t
+ *   policy (exactly one of policy / actor is given, the other NULL):
+ *     meshenv_policy_forward(obs, noise counter counter + t when sample != 0, eps = 0 otherwise), meshenv_step (auto-reset on),
+ *     meshenv_eval_tally(t)  --  = collect_rollout(T, seed, counter) after a reset: meshenv_step_policy_multi(counter)
+ *   actor: the actions of step 0 come from meshenv_actor_sample / _forward on the reset observation with counter, then
+ *     meshenv_step_actor(counter + t + 1), meshenv_eval_tally(t)  --  = actor(obs0, counter) followed by
+ *     meshenv_step_actor_multi(counter + 1)
+ * so the actions of vector step t are always drawn with noise counter counter + t.  Every check_every steps (and after the
+ * last) the short counter is copied to a pinned host word of the handle and the stream is synchronised; the loop stops when
+ * it is 0 or after max_steps steps.  The records do not depend on check_every (envs past their target are not recorded).
+ * *steps_out = vector steps run, *short_out = envs still short of their target (0: finished).  max_steps is required: the
+ * reference's loop has no cap, and an episode of rule-0 extractions alone need not end.
+ * SYNCHRONISES the stream and is NOT graph-capturable.  Env and policy / actor must share device and stream
+ * (MESHENV_E_STATE); MESHENV_E_ARG for both or neither of policy / actor, max_steps or check_every < 1, a missing buffer.
+ */
+int meshenv_evaluate(MeshEnv *h, MeshPolicy *policy, MeshActor *actor, int sample, uint64_t seed, uint64_t counter, int max_steps,
+                     int check_every, const MeshEvalBuffers *bufs, int32_t *steps_out, int32_t *short_out);
+
+/*
  * MeshGeneration.extract_samples_2(meshes, n_neighbor, n_radius, radius, index, quality_threshold), general/mesh.py:1438-1489
  * (the data-preparation step of the ANN scripts: general/EBRD.py:414, 579 with (2, 3, radius 4, index 1) and
  * general/post_processing.py:532 with (3, 3, radius 6, index 5)) for the generated mesh of EVERY env in one launch

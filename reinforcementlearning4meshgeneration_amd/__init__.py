@@ -6,7 +6,7 @@ ZhuoQiuMcgill/ReinforcementLearning4MeshGeneration as hand-written HIP kernels b
 from .domains import boundary, domain_constants, generate_polygon, random_domain, read_polygon  # noqa: F401
 
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
-           "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy"]
+           "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -28,4 +28,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name == "FusedPolicy":
         from .policy import FusedPolicy
         return FusedPolicy
+    if name in ("EvalResult", "evaluate_policy"):
+        from . import evaluation
+        return getattr(evaluation, name)
     raise AttributeError(name)

@@ -28,6 +28,16 @@ class MeshEnvParams(C.Structure):
     ]
 
 
+class MeshEvalBuffers(C.Structure):
+    """include/meshenv.h MeshEvalBuffers: device pointers (torch data_ptr()), NULL = None."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32)] + [
+        (name, C.c_void_p) for name in (
+            "target_dev", "offset_dev", "count_dev", "length_dev", "seen_dev", "return_dev", "return_raw_dev", "short_dev",
+            "ep_env_dev", "ep_domain_dev", "ep_step_dev", "ep_length_dev", "ep_flags_dev", "ep_n_elements_dev",
+            "ep_archive_dev", "ep_return_dev", "ep_return_raw_dev", "ep_quality_dev", "obs_dev", "reward_dev", "done_dev",
+            "complete_dev")]
+
+
 class MeshEnvError(RuntimeError):
     pass
 
@@ -48,6 +58,7 @@ EXPORTS = [
     "meshenv_step_actor_multi", "meshenv_extract_samples", "meshenv_atan2_exact", "meshenv_quad_quality",
     "meshenv_policy_create", "meshenv_policy_destroy", "meshenv_policy_set_stream", "meshenv_policy_load",
     "meshenv_policy_forward", "meshenv_step_policy_multi", "meshenv_policy_last_error", "meshenv_gae",
+    "meshenv_eval_begin", "meshenv_eval_tally", "meshenv_evaluate",
 ]
 
 
@@ -158,6 +169,13 @@ def load():
     L.meshenv_step_policy_multi.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 11 + [C.c_int]
     L.meshenv_gae.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     L.meshenv_gae.restype = C.c_int
+    evp = C.POINTER(MeshEvalBuffers)
+    L.meshenv_eval_begin.argtypes = [vp, evp]
+    L.meshenv_eval_begin.restype = C.c_int
+    L.meshenv_eval_tally.argtypes = [vp, evp, C.c_int, vp, vp, vp]
+    L.meshenv_eval_tally.restype = C.c_int
+    L.meshenv_evaluate.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, evp, i32p, i32p]
+    L.meshenv_evaluate.restype = C.c_int
     for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
                  "meshenv_step_policy_multi"):
         getattr(L, name).restype = C.c_int

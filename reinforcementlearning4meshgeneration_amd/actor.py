@@ -45,6 +45,30 @@ class FusedActor:
             raise _capi.MeshEnvError(f"meshenv_actor_load failed ({rc})")
         return self
 
+    @classmethod
+    def from_sb3(cls, policy, device: int = 0, low=ACTION_LOW, high=ACTION_HIGH):
+        """An SB3 2.x SAC model, SACPolicy or Actor (duck-typed, SB3 is not imported): the modules INTEGRATION.md section 3
+        passes to from_torch by hand -- actor.latent_pi[0, 2, 4] (Linear, ReLU x 3, net_arch [128, 128, 128]), actor.mu,
+        actor.log_std.  gSDE actors and other architectures are refused."""
+        actor = policy
+        if not hasattr(actor, "latent_pi"):
+            if not hasattr(actor, "actor") and hasattr(actor, "policy"):
+                actor = actor.policy
+            actor = getattr(actor, "actor", actor)
+        if not hasattr(actor, "latent_pi") or not hasattr(actor, "mu") or not hasattr(actor, "log_std"):
+            raise ValueError("not an SB3 SAC actor (latent_pi, mu, log_std)")
+        if getattr(actor, "use_sde", False):
+            raise ValueError("gSDE SAC actors are not supported (the fused actor is the squashed Gaussian of MlpPolicy)")
+        fe = getattr(actor, "features_extractor", None)
+        if fe is not None and type(fe).__name__ != "FlattenExtractor":
+            raise ValueError(f"features_extractor is {type(fe).__name__}; only FlattenExtractor is supported")
+        mods = list(actor.latent_pi)
+        names = [type(m).__name__ for m in mods]
+        if names != ["Linear", "ReLU"] * 3:
+            raise ValueError(f"actor.latent_pi is {names}; the fused actor is MlpPolicy's ReLU [128, 128, 128] "
+                             "(rl/baselines/RL_Mesh.py:183-196)")
+        return cls.from_torch([mods[0], mods[2], mods[4]], actor.mu, actor.log_std, device=device, low=low, high=high)
+
     def forward(self, obs, noise=None, out=None):
         """obs: float32 CUDA [n, 18]; noise: float32 CUDA [n, 3] of N(0,1) samples or None (deterministic).
         Returns actions float32 CUDA [n, 3] inside the action Box."""

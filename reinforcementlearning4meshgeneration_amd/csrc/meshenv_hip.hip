@@ -25,6 +25,7 @@
 #include "meshenv_fused.h"
 #include "meshenv_policy.h"
 #include "meshenv_gae.h"
+#include "meshenv_eval.h"
 
 using namespace meshenv;
 
@@ -161,6 +162,13 @@ struct MeshEnv {
     int32_t *nv_meta = nullptr;  // [E][kNvMeta] episode counter + last_not_valid_points summary
     uint8_t *move_mask = nullptr;  // [E] envs of the last meshenv_move that went through smooth_pave
     long long ev_count = 0;      // launches recorded since timing was armed
+    // meshenv_evaluate's step buffers (allocated by its first call without caller buffers) and the pinned host word it
+    // reads the short-envs counter into
+    float *eval_obs = nullptr;
+    float *eval_act = nullptr;   // [2][E][3] ping-pong
+    double *eval_reward = nullptr;
+    uint8_t *eval_done = nullptr, *eval_complete = nullptr;
+    int32_t *eval_host = nullptr;
 };
 
 namespace {
@@ -257,6 +265,7 @@ void meshenv_destroy(MeshEnv *h)
     DeviceGuard guard(h->device);
     (void)hipStreamSynchronize(h->stream);
     for (void *p : h->allocs) (void)hipFree(p);
+    if (h->eval_host) (void)hipHostFree(h->eval_host);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     delete h;
 }
@@ -2118,6 +2127,180 @@ int meshenv_gae(MeshEnv *h, int T, const double *reward_dev, const float *value_
     hipLaunchKernelGGL(long_t ? k_gae<512> : k_gae<256>, dim3((unsigned)((n + kGaeEnvs - 1) / kGaeEnvs)), dim3(long_t ? 512 : 256),
                        0, h->stream, A);
     HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ policy evaluation
+namespace {
+
+// the buffers of a MeshEvalBuffers as kernel arguments; nullptr + message where a required one is missing
+const char *eval_args(const MeshEnv *h, const MeshEvalBuffers *b, EvalTallyArgs *A)
+{
+    if (!b || b->struct_size != (int32_t)sizeof(MeshEvalBuffers)) return "MeshEvalBuffers missing or struct_size mismatch";
+    if (!b->target_dev || !b->offset_dev || !b->count_dev || !b->length_dev || !b->seen_dev || !b->return_dev ||
+        !b->return_raw_dev || !b->short_dev)
+        return "MeshEvalBuffers: a per-env buffer (target, offset, count, length, seen, return, return_raw, short) is NULL";
+    if (!b->ep_env_dev || !b->ep_domain_dev || !b->ep_step_dev || !b->ep_length_dev || !b->ep_flags_dev ||
+        !b->ep_n_elements_dev || !b->ep_return_dev || !b->ep_return_raw_dev)
+        return "MeshEvalBuffers: a per-episode buffer (env, domain, step, length, flags, n_elements, return, return_raw) is NULL";
+    const int given = (b->obs_dev ? 1 : 0) + (b->reward_dev ? 1 : 0) + (b->done_dev ? 1 : 0) + (b->complete_dev ? 1 : 0);
+    if (given != 0 && given != 4) return "MeshEvalBuffers: obs, reward, done and complete are given all together or not at all";
+    EvalTallyArgs a{};
+    a.n = h->n_envs;
+    a.last_ep = h->S.prm.log_cap > 0 ? h->cold.last_ep : nullptr;
+    a.target = b->target_dev; a.offset = b->offset_dev;
+    a.count = b->count_dev; a.length = b->length_dev; a.seen = b->seen_dev;
+    a.ret = b->return_dev; a.ret_raw = b->return_raw_dev; a.short_envs = b->short_dev;
+    a.ep_env = b->ep_env_dev; a.ep_domain = b->ep_domain_dev; a.ep_step = b->ep_step_dev; a.ep_length = b->ep_length_dev;
+    a.ep_flags = b->ep_flags_dev; a.ep_n_elem = b->ep_n_elements_dev; a.ep_archive = b->ep_archive_dev;
+    a.ep_return = b->ep_return_dev; a.ep_return_raw = b->ep_return_raw_dev; a.ep_quality = b->ep_quality_dev;
+    *A = a;
+    return nullptr;
+}
+
+int eval_check(MeshEnv *h, const char *fn, const MeshEvalBuffers *b, EvalTallyArgs *A)
+{
+    const char *msg = eval_args(h, b, A);
+    if (msg) {
+        h->err = std::string(fn) + ": " + msg;
+        return MESHENV_E_ARG;
+    }
+    if (A->ep_quality && h->S.prm.log_cap <= 0) {
+        h->err = std::string(fn) + ": ep_quality_dev needs a handle created with log_capacity > 0";
+        return MESHENV_E_STATE;
+    }
+    return MESHENV_OK;
+}
+
+int eval_begin_launch(MeshEnv *h, const EvalTallyArgs &A)
+{
+    MESHENV_ON_DEVICE(h);   // (a no-op inside the entry points, which hold the guard already)
+    HIP_TRY(h, hipMemsetAsync(A.short_envs, 0, sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(k_eval_begin, dim3((h->n_envs + 63) / 64), dim3(64), 0, h->stream, h->S, A);
+    HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+int eval_tally_launch(MeshEnv *h, EvalTallyArgs A, int step, const double *reward, const uint8_t *done, const uint8_t *complete)
+{
+    MESHENV_ON_DEVICE(h);   // (a no-op inside the entry points, which hold the guard already)
+    A.step = step; A.reward = reward; A.done = done; A.complete = complete;
+    hipLaunchKernelGGL(k_eval_tally, dim3((h->n_envs + 63) / 64), dim3(64 * kEvalWaves), 0, h->stream, h->S, A);
+    HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+// short_dev -> the pinned host word, then wait for the stream
+int eval_read_short(MeshEnv *h, const int32_t *short_dev, int32_t *out)
+{
+    MESHENV_ON_DEVICE(h);   // (a no-op inside the entry points, which hold the guard already)
+    HIP_TRY(h, hipMemcpyAsync(h->eval_host, short_dev, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out = *h->eval_host;
+    return MESHENV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_eval_begin(MeshEnv *h, const MeshEvalBuffers *bufs)
+{
+    if (!h) return MESHENV_E_ARG;
+    EvalTallyArgs A;
+    const int rc = eval_check(h, "meshenv_eval_begin", bufs, &A);
+    if (rc != MESHENV_OK) return rc;
+    MESHENV_ON_DEVICE(h);
+    return eval_begin_launch(h, A);
+}
+
+int meshenv_eval_tally(MeshEnv *h, const MeshEvalBuffers *bufs, int step, const double *reward_dev, const uint8_t *done_dev,
+                       const uint8_t *complete_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (!reward_dev || !done_dev || !complete_dev) return fail_arg(h, "meshenv_eval_tally: null reward / done / complete");
+    EvalTallyArgs A;
+    const int rc = eval_check(h, "meshenv_eval_tally", bufs, &A);
+    if (rc != MESHENV_OK) return rc;
+    MESHENV_ON_DEVICE(h);
+    return eval_tally_launch(h, A, step, reward_dev, done_dev, complete_dev);
+}
+
+int meshenv_evaluate(MeshEnv *h, MeshPolicy *policy, MeshActor *actor, int sample, uint64_t seed, uint64_t counter, int max_steps,
+                     int check_every, const MeshEvalBuffers *bufs, int32_t *steps_out, int32_t *short_out)
+{
+    if (!h) return MESHENV_E_ARG;
+    if ((policy != nullptr) == (actor != nullptr)) return fail_arg(h, "meshenv_evaluate: give exactly one of policy and actor");
+    if (max_steps < 1 || check_every < 1) return fail_arg(h, "meshenv_evaluate: max_steps and check_every must be >= 1");
+    if (!steps_out || !short_out) return fail_arg(h, "meshenv_evaluate: steps_out and short_out are required");
+    if (policy ? !policy->loaded : !actor->loaded) {
+        h->err = "meshenv_evaluate: the policy / actor has no weights loaded";
+        return MESHENV_E_STATE;
+    }
+    if (policy ? (policy->device != h->device || policy->stream != h->stream) : (actor->device != h->device || actor->stream != h->stream)) {
+        h->err = "meshenv_evaluate: env and policy / actor must be on the same device and stream";
+        return MESHENV_E_STATE;
+    }
+    EvalTallyArgs A;
+    int rc = eval_check(h, "meshenv_evaluate", bufs, &A);
+    if (rc != MESHENV_OK) return rc;
+    MESHENV_ON_DEVICE(h);
+    const size_t n = (size_t)h->n_envs;
+    // every allocation before the first launch: nothing is allocated on the per-step path
+    if (!h->eval_host) {
+        void *p = nullptr;
+        HIP_TRY(h, hipHostMalloc(&p, sizeof(int32_t), hipHostMallocDefault));
+        h->eval_host = (int32_t *)p;
+    }
+    if (!h->eval_act && (rc = dev_alloc(h, &h->eval_act, 2 * n * 3)) != MESHENV_OK) return rc;
+    if (!bufs->obs_dev && !h->eval_obs) {
+        if ((rc = dev_alloc(h, &h->eval_obs, n * kObsDim)) != MESHENV_OK || (rc = dev_alloc(h, &h->eval_reward, n)) != MESHENV_OK ||
+            (rc = dev_alloc(h, &h->eval_done, n)) != MESHENV_OK || (rc = dev_alloc(h, &h->eval_complete, n)) != MESHENV_OK)
+            return rc;
+    }
+    float *obs = bufs->obs_dev ? bufs->obs_dev : h->eval_obs;
+    double *reward = bufs->obs_dev ? bufs->reward_dev : h->eval_reward;
+    uint8_t *done = bufs->obs_dev ? bufs->done_dev : h->eval_done;
+    uint8_t *complete = bufs->obs_dev ? bufs->complete_dev : h->eval_complete;
+    float *act[2] = {h->eval_act, h->eval_act + n * 3};
+    *steps_out = 0;
+    *short_out = 0;
+    if ((rc = meshenv_reset(h, nullptr, obs)) != MESHENV_OK) return rc;
+    if ((rc = eval_begin_launch(h, A)) != MESHENV_OK) return rc;
+    int32_t short_envs = 0;
+    if ((rc = eval_read_short(h, A.short_envs, &short_envs)) != MESHENV_OK) return rc;
+    if (short_envs == 0) return MESHENV_OK;
+    if (actor && (rc = actor_launch(actor, "meshenv_evaluate", (int)n, obs, nullptr, act[0], sample, seed, counter, nullptr)) != MESHENV_OK) {
+        h->err = actor->err;
+        return rc;
+    }
+    PolicyArgs P{};
+    P.n = (int)n; P.obs = obs; P.sample = sample ? 1 : 0; P.seed = seed; P.actions = act[0];
+    int t = 0;
+    while (t < max_steps) {
+        if (policy) {
+            P.counter = counter + (uint64_t)t;
+            if ((rc = policy_launch(policy, "meshenv_evaluate", P)) != MESHENV_OK) {
+                h->err = policy->err;
+                return rc;
+            }
+            rc = launch_step(h, 1, act[0], obs, reward, done, complete, nullptr, 1);
+        } else {
+            rc = meshenv_step_actor(h, actor, act[t & 1], obs, reward, done, complete, nullptr, 1, sample, seed, counter + (uint64_t)t + 1,
+                                    act[(t + 1) & 1], nullptr);
+        }
+        if (rc != MESHENV_OK) return rc;
+        if ((rc = eval_tally_launch(h, A, t, reward, done, complete)) != MESHENV_OK) return rc;
+        t += 1;
+        if (t % check_every == 0 || t == max_steps) {
+            if ((rc = eval_read_short(h, A.short_envs, &short_envs)) != MESHENV_OK) return rc;
+            if (short_envs == 0) break;
+        }
+    }
+    *steps_out = t;
+    *short_out = short_envs;
     return MESHENV_OK;
 }
 

@@ -98,17 +98,17 @@ __device__ __forceinline__ void element_quality(const P2 *m, double *q)
     q[7] = 1 / (aspect + err);  // 'default', components.py:864-869
 }
 
-// which = 0: the running episode of every env; 1: the last archived (finished) episode.
-// elem_out [E][log_cap][8] (rows >= count untouched), stats_out [E][8][4] = min, mean, max, variance,
-// count_out [E]; each pointer may be NULL.
-__global__ void __launch_bounds__(64)
-k_element_quality(DevState S, int which, double *__restrict__ elem_out, double *__restrict__ stats_out,
-                  int32_t *__restrict__ count_out)
+// The report of ONE env, computed by a whole wave: env and which are wave-uniform and all 64 lanes take part (the
+// statistics are DPP reductions).  which = 0: the running episode; 1: the last archived (finished) episode.
+// elem_out [E][log_cap][8] (rows >= count untouched), stats_row = the env's [8][4] min, mean, max, variance,
+// count_out = the env's count; each pointer may be NULL.  Shared by k_element_quality and k_eval_tally
+// (csrc/meshenv_eval.h), so both report the same bits.  sc = S.scal[env].
+__device__ __forceinline__ void env_quality(const DevState &S, const EnvScalars &sc, const DevCold &cold, int env, int which,
+                                            double *__restrict__ elem_out, double *__restrict__ stats_row,
+                                            int32_t *__restrict__ count_out)
 {
-    const int env = blockIdx.x, lane = lane_id();
+    const int lane = lane_id();
     const int cap = S.prm.log_cap;
-    const EnvScalars sc = S.scal[env];
-    const DevCold cold = load_cold(S);
     int half = (uniform_i32(sc.status) >> 4) & 1;
     int ne = uniform_i32(sc.n_elem);
     if (which) {
@@ -150,8 +150,8 @@ k_element_quality(DevState S, int which, double *__restrict__ elem_out, double *
             s2[k] += q[k] * q[k];
         }
     }
-    if (count_out && lane == 0) count_out[env] = ne;
-    if (stats_out) {
+    if (count_out && lane == 0) *count_out = ne;
+    if (stats_row) {
         double r = 0;
 #pragma unroll
         for (int k = 0; k < kQualityDim; k++) {
@@ -161,8 +161,22 @@ k_element_quality(DevState S, int which, double *__restrict__ elem_out, double *
             const int j = lane - 4 * k;
             r = j == 0 ? (ne ? a : 0.0) : (j == 1 ? avg : (j == 2 ? (ne ? c : 0.0) : (j == 3 ? var : r)));
         }
-        if (lane < 4 * kQualityDim) stats_out[(size_t)env * 4 * kQualityDim + lane] = r;
+        if (lane < 4 * kQualityDim) stats_row[lane] = r;
     }
+}
+
+// which = 0: the running episode of every env; 1: the last archived (finished) episode.
+// elem_out [E][log_cap][8] (rows >= count untouched), stats_out [E][8][4] = min, mean, max, variance,
+// count_out [E]; each pointer may be NULL.
+__global__ void __launch_bounds__(64)
+k_element_quality(DevState S, int which, double *__restrict__ elem_out, double *__restrict__ stats_out,
+                  int32_t *__restrict__ count_out)
+{
+    const int env = blockIdx.x;
+    const EnvScalars sc = S.scal[env];
+    const DevCold cold = load_cold(S);
+    env_quality(S, sc, cold, env, which, elem_out, stats_out ? stats_out + (size_t)env * 4 * kQualityDim : nullptr,
+                count_out ? count_out + env : nullptr);
 }
 
 // MeshGeneration.get_quality(element, index) (general/mesh.py:1728-1747) for arbitrary quads, the indices that are a

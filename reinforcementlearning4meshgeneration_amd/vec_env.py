@@ -655,6 +655,84 @@ class MeshVecEnv:
         self._check(rc, "meshenv_gae")
         return out
 
+    def evaluate(self, policy, n_eval_episodes: Optional[int] = None, episodes_per_env=None, deterministic: bool = True,
+                 seed: int = 0, counter: int = 0, max_steps: int = 20000, check_every: int = 32, quality: bool = True):
+        """SB3's evaluate_policy loop on the device (meshenv_evaluate): every env is reset, then per vector step the policy,
+        a step with auto-reset and one k_eval_tally launch, with no host synchronisation except a read of the envs-still-short
+        counter every check_every steps; the run stops when every env has recorded its target or after max_steps steps.
+
+        policy: a FusedPolicy (PPO / A2C / TD3 kinds) or a FusedActor (SAC) on this device.  Episodes per env: SB3's
+        (n_eval_episodes + i) // n_envs, or episodes_per_env (an int or an [n_envs] array), or one each by default; envs past
+        their target keep stepping and are not recorded.  deterministic=False samples with Philox noise; the actions of
+        vector step t use noise counter counter + t (the same stream as collect_rollout(policy, T, seed, counter) /
+        step_actor_T after a reset).  quality=True scores each finished mesh on the device (needs log_capacity > 0).
+        Returns an EvalResult (records sorted by (step, env)); finished is False, with a RuntimeWarning, when max_steps cut
+        the run short.  env.obs / reward / done / complete hold the last step afterwards."""
+        import warnings
+
+        from .actor import FusedActor
+        from .evaluation import EvalResult, episode_targets
+        from .policy import FusedPolicy
+        t = self._torch
+        n = self.num_envs
+        targets = episode_targets(n, n_eval_episodes, episodes_per_env)
+        for name, v in (("max_steps", max_steps), ("check_every", check_every)):
+            if isinstance(v, bool) or int(v) != v or not 1 <= v < 2 ** 31:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        if isinstance(policy, FusedPolicy):
+            pol, act = policy, None
+        elif isinstance(policy, FusedActor):
+            pol, act = None, policy
+        else:
+            raise TypeError(f"policy must be a FusedPolicy or a FusedActor, got {type(policy).__name__} (evaluation.evaluate_policy "
+                            "converts SB3 models)")
+        if policy.device != self.device:
+            raise ValueError(f"policy is on {policy.device}, the envs on {self.device}")
+        if quality and self.log_capacity <= 0:
+            raise _capi.MeshEnvError("quality=True needs a MeshVecEnv created with log_capacity > 0 (the finished meshes are "
+                                     "read from the element log); pass quality=False")
+        offsets = np.zeros(n, np.int32)
+        offsets[1:] = np.cumsum(targets, dtype=np.int64)[:-1]
+        total = int(targets.sum())
+        m = max(total, 1)
+        i32 = dict(dtype=t.int32, device=self.device)
+        f64 = dict(dtype=t.float64, device=self.device)
+        buf = dict(target_dev=t.from_numpy(targets).to(self.device), offset_dev=t.from_numpy(offsets).to(self.device),
+                   count_dev=t.empty(n, **i32), length_dev=t.empty(n, **i32), seen_dev=t.empty(n, **i32),
+                   return_dev=t.empty(n, **f64), return_raw_dev=t.empty(n, **f64), short_dev=t.zeros(1, **i32),
+                   ep_env_dev=t.zeros(m, **i32), ep_domain_dev=t.zeros(m, **i32), ep_step_dev=t.zeros(m, **i32),
+                   ep_length_dev=t.zeros(m, **i32), ep_flags_dev=t.zeros(m, **i32), ep_n_elements_dev=t.zeros(m, **i32),
+                   ep_archive_dev=t.zeros(m, **i32), ep_return_dev=t.zeros(m, **f64), ep_return_raw_dev=t.zeros(m, **f64))
+        if quality:
+            buf["ep_quality_dev"] = t.zeros((m, 8, 4), **f64)
+        buf.update(obs_dev=self.obs, reward_dev=self.reward, done_dev=self.done, complete_dev=self.complete)
+        B = _capi.MeshEvalBuffers()
+        B.struct_size = C.sizeof(_capi.MeshEvalBuffers)
+        for k, v in buf.items():
+            setattr(B, k, v.data_ptr())
+        self._bind_stream()
+        stream = t.cuda.current_stream(self.device).cuda_stream
+        if pol is not None:
+            pol._bind_stream()
+        elif stream != act._stream:
+            act._L.meshenv_actor_set_stream(act._h, C.c_void_p(stream))
+            act._stream = stream
+        steps, short = C.c_int32(0), C.c_int32(0)
+        rc = self._L.meshenv_evaluate(self._handle, pol._h if pol is not None else None, act._h if act is not None else None,
+                                      0 if deterministic else 1, C.c_uint64(seed & (2 ** 64 - 1)),
+                                      C.c_uint64(counter & (2 ** 64 - 1)), int(max_steps), int(check_every), C.byref(B),
+                                      C.byref(steps), C.byref(short))
+        self._check(rc, "meshenv_evaluate")
+        counts = buf["count_dev"].cpu().numpy()
+        owner = np.repeat(np.arange(n), targets)
+        keep = (np.arange(total) - offsets[owner]) < counts[owner]      # slots of episodes that were recorded
+        rec = {k[3:-4]: buf[k][:total].cpu().numpy()[keep] for k in buf if k.startswith("ep_")}
+        res = EvalResult.from_records(rec, targets, steps.value, short.value == 0)
+        if not res.finished:
+            warnings.warn(f"evaluate: max_steps = {max_steps} reached with {short.value} envs short of their episode target "
+                          f"({len(res)} of {total} episodes recorded)", RuntimeWarning, stacklevel=2)
+        return res
+
     def extract_samples(self, n_neighbor: int = 2, n_radius: int = 3, radius: float = 4.0, index: int = 1,
                         quality_threshold: float = 0.7, which: str = "current", mask=None):
         """MeshGeneration.extract_samples_2 (general/mesh.py:1438-1489) for the generated mesh of every env, on the device
