@@ -180,8 +180,14 @@ int meshenv_group_size(const MeshEnv *h);
  * batches whose ring stride is at most 64 slots (every ring pass is one 64-lane pass, no chunk loops).
  * 6 = k_step<false, true, false, true>: the one-wave-per-env kernel of such batches (default geometry constants).
  * 7 / 8 = k_step<false, true, false, false | true, true>: the throughput-regime forms of 0 / 6 (batches staged record-first,
- * from 8192 envs): a rule-0 quad with a corner that cannot be valid is rejected before the point-in-polygon pass. */
+ * from 8192 envs): a rule-0 quad with a corner that cannot be valid is rejected before the point-in-polygon pass.
+ * 9 / 10 = k_step<false, false> / k_step<false, false, true>: 0 / 3 of handles created with non-default geometry
+ * constants (MeshEnvParams), which read them at run time. */
 int meshenv_step_kernel(const MeshEnv *h);
+/* Which kernel meshenv_rollout (n_steps > 1) launches: 0 = k_step<true, true>, 1 = k_step<true, true, false, true> (ring
+ * stride <= 64), 2 = k_step<true, false> (non-default geometry constants), 3 / 4 = k_step<true, true | false, true> (after a
+ * front smoothing, as meshenv_step_kernel's 3 / 10). */
+int meshenv_rollout_kernel(const MeshEnv *h);
 /* The smoothing kernels evaluate `x ** 2` like the reference's libm (CPython's float ** 2 is pow(x, 2.0), which glibc does
  * not round correctly: it differs from x * x in 0.085 % of the arguments) through a restatement of glibc's pow
  * (csrc/meshenv_libm.h) that the library validates against the libm of the running process at the first smoothing call.

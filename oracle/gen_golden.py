@@ -383,11 +383,12 @@ GUIDED_TRACES = [
 ]
 
 
-def guided_trace(dom, seed, T, p_valid):
+def guided_trace(dom, seed, T, p_valid, pts=None):
     """With probability p_valid the next action is one the reference accepts at the current state -- found by trying
     rule -1, rule +1 and jittered parallelogram-completion points on a replay of the episode's history (the env cannot
-    be copied) -- otherwise a biased random one.  Gives fixtures whose steps are mostly extractions."""
-    pts = H.domain_points(dom)
+    be copied) -- otherwise a biased random one.  Gives fixtures whose steps are mostly extractions.  pts: the ring
+    (default: the named domain's)."""
+    pts = H.domain_points(dom) if pts is None else pts
 
     def accepted(hist, a):
         e = H.make_env(pts)
@@ -474,8 +475,45 @@ def plot_fixture():
     print(f"plot fixture: step {t}, {len(quads)} elements, PNG bytes {[len(out['png_' + k]) for k in calls]}")
 
 
+# Traces on scaled / shifted domains and with the env's radius changed (xf_*.npz): (fixture name, domain, scale, (dx, dy),
+# seed, T, radius; a negative seed = a guided stream).  The transform x -> scale x + dx is applied to the domain before
+# the reference env is built.  Biased streams where they give enough extractions, guided ones where the reference
+# rejects most biased actions (the ray end inside the domain, coordinates at 1e-3 rounded to 4 places).
+XF_TRACES = [
+    ("xf_boundary0_x1em3_g1", "boundary0", 1e-3, (0.0, 0.0), -1, 120, None),
+    ("xf_boundary0_x1e3_g2", "boundary0", 1e3, (0.0, 0.0), -2, 120, None),       # x in [0, 12000]: past the ray end
+    ("xf_boundary0_dx1e6_s3", "boundary0", 1.0, (1e6, 0.0), 3, 300, None),
+    ("xf_boundary0_d1e8_s4", "boundary0", 1.0, (1e8, -1e8), 4, 300, None),
+    ("xf_boundary0_ray_s5", "boundary0", 1.0, (9988.0, 0.0), 5, 300, None),      # the apex at x = 10000: the ray's end
+    ("xf_boundary16_dx1e6_s6", "boundary16", 1.0, (1e6, 0.0), 6, 300, None),
+    ("xf_boundary16_dx1e8_s7", "boundary16", 1.0, (1e8, 0.0), 7, 300, None),
+    ("xf_test1_x1e4_s8", "test1", 1e4, (0.0, 0.0), 8, 300, None),                 # mostly past the ray end
+    ("xf_boundary0_radius3_s9", "boundary0", 1.0, (0.0, 0.0), 9, 300, 3.0),
+    ("xf_boundary0_radius5_s10", "boundary0", 1.0, (0.0, 0.0), 10, 300, 5.0),
+]
+
+
+def transform(points, scale, shift):
+    return [(scale * x + shift[0], scale * y + shift[1]) for x, y in points]
+
+
+def main_transformed(only=()):
+    for name, dom, scale, shift, seed, T, radius in XF_TRACES:
+        if only and name not in only:
+            continue
+        pts = transform(H.domain_points(dom), scale, shift)
+        if seed < 0:
+            _, acts = guided_trace(dom, -seed, T, 0.6, pts=pts)
+        else:
+            acts = H.biased_actions(seed, T)
+        save(name, H.record_trace(pts, acts, radius=radius))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if "--transformed-only" in sys.argv:
+        main_transformed(only=[a for a in sys.argv[1:] if a.startswith("xf_")])
+        return
     if "--smooth-only" in sys.argv:
         main_smooth()
         main_final_smooth()
@@ -506,6 +544,7 @@ def main():
     save("boundary0_targeted", H.record_trace(pts, acts))
     main_samepoint()
     main_guided()
+    main_transformed()
     main_move()
     main_smooth()
     main_final_smooth()

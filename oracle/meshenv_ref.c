@@ -74,6 +74,8 @@ struct RefEnv {
     /* last_not_valid_points (B:48, 416-422): set only where move() smooths, NOT cleared by reset() -- first / last entry
      * and length are all the reference compares; a vertex is the same object only within one episode (reset() deep-copies) */
     int32_t last_first, last_last, last_count, last_epoch, epoch;
+    /* the geometry constants of MeshEnvParams (include/meshenv.h); meshenv_ref_create sets the reference's literals */
+    double radius, max_ref_angle, key_lambda, min_degree, max_degree, same_point_eps, ray_length;
     /* logs */
     int cap_v, cap_e;
     P2 *vtab;
@@ -176,9 +178,9 @@ static int check_boundary_point(const RefEnv *e, int index, double *out)
 {
     int n = e->n;
     P2 v = e->ring[index];
-    double w0 = 0.618, w1 = 1 - 0.618;
+    double w0 = e->key_lambda, w1 = 1 - e->key_lambda;
     double a0 = cw(v, e->ring[(index + 1) % n], e->ring[RI(index - 1, n)]);
-    if (a0 >= PI * 0.972 || a0 == 0) return 0;
+    if (a0 >= e->max_ref_angle || a0 == 0) return 0;
     double sum_angle = 0;
     sum_angle += a0 * w0;
     double a1 = cw(v, e->ring[(index + 2) % n], e->ring[RI(index - 2, n)]);
@@ -266,24 +268,24 @@ static int find_next_state_opt(RefEnv *e, float *obs, int is_static, int use_nv)
     for (int i = 1; i < 7; i++) sum += dist(nb[i], nb[i - 1]);
     const double bl = round4_py(sum / 6);
     e->bl = bl;
-    const double target_length = bl * 4;
+    const double target_length = bl * e->radius;
     const double theta = cw(ref, left, right);
 
     float r[9][2];
     for (int i = 0; i < 9; i++) r[i][0] = r[i][1] = 1.0f;
 
-    r[0][0] = (float)((dist(ref, right) / 4) / bl);
+    r[0][0] = (float)((dist(ref, right) / e->radius) / bl);
     r[0][1] = is_static ? 0.0f : (float)area_ratio;
-    r[8][0] = (float)((dist(ref, left) / 4) / bl);
+    r[8][0] = (float)((dist(ref, left) / e->radius) / bl);
     r[8][1] = (float)theta;
     for (int i = 1; i < 3; i++) {
         P2 pr = ring[RI(idx - i - 1, n)];
         double a = cw(ref, pr, right);
-        r[i][0] = (float)((dist(ref, pr) / 4) / bl);
+        r[i][0] = (float)((dist(ref, pr) / e->radius) / bl);
         r[i][1] = (float)(a < PI ? a : fmax(a, 1.5 * PI) - 2 * PI);
         P2 pl = ring[(idx + 1 + i) % n];
         a = cw(ref, pl, right);
-        r[8 - i][0] = (float)((dist(ref, pl) / 4) / bl);
+        r[8 - i][0] = (float)((dist(ref, pl) / e->radius) / bl);
         r[8 - i][1] = (float)fmin(a, theta + PI / 2);
     }
 
@@ -312,7 +314,7 @@ static int find_next_state_opt(RefEnv *e, float *obs, int is_static, int use_nv)
         const double kf = angle / (theta / 3);
         if (kf < 3.0 && d < target_length) { /* int(kf) < 3  <=>  kf < 3 for kf >= 0 */
             const int k = (int)kf;
-            const float cnd = (float)((d / 4) / bl);
+            const float cnd = (float)((d / e->radius) / bl);
             if (r[k + 3][0] > cnd) {
                 r[k + 3][0] = cnd;
                 r[k + 3][1] = (float)fmin(angle, theta + PI / 2);
@@ -337,7 +339,7 @@ static int find_next_state_opt(RefEnv *e, float *obs, int is_static, int use_nv)
         }
         if (0 < s && s < 1 && 0 < h && h < 1) {
             P2 vv = {ref.x + s * ux, ref.y + s * uy};
-            double val = (dist(ref, vv) / 4) / bl;
+            double val = (dist(ref, vv) / e->radius) / bl;
             if (shortest > val) {
                 shortest = val;
                 shortest_i = i;
@@ -347,7 +349,7 @@ static int find_next_state_opt(RefEnv *e, float *obs, int is_static, int use_nv)
     if (shortest != 1 && (float)shortest < r[4][0]) {
         for (int i = 0; i < 3; i++) {
             P2 v = ring[RI(i - 1 + shortest_i, n)];
-            r[3 + i][0] = (float)((dist(ref, v) / 4) / bl);
+            r[3 + i][0] = (float)((dist(ref, v) / e->radius) / bl);
             r[3 + i][1] = (float)cw(ref, v, right);
         }
     }
@@ -367,7 +369,7 @@ static int is_point_inside_area(const RefEnv *e, P2 p)
 {
     const int n = e->n, n0 = e->n0;
     const P2 *ring = e->ring;
-    const P2 far = {10000, p.y};
+    const P2 far = {e->ray_length, p.y};
     int count = 0;
     for (int i = 0; i < n; i++) {
         const int im1 = RI(i - 1, n), im2 = RI(i - 2, n), ip1 = (i + 1) % n;
@@ -396,13 +398,13 @@ static int is_point_inside_area(const RefEnv *e, P2 p)
 /* ---------------------------------------------------- quad validity (a9, a10) */
 
 /* Mesh.is_valid(0), C:738-757 + segments_crossed C:814-826 */
-static int quad_is_valid(const P2 *m)
+static int quad_is_valid(const RefEnv *e, const P2 *m)
 {
     if (is_cross(m[0], m[1], m[2], m[3])) return 0;
     if (is_cross(m[0], m[3], m[1], m[2])) return 0;
     for (int i = 0; i < 4; i++) {
         double degree = cw(m[i], m[(i + 1) % 4], m[(i + 3) % 4]);
-        if (degree > 0.99 * PI || degree < 0.01 * PI) return 0;
+        if (degree > e->max_degree || degree < e->min_degree) return 0;
     }
     return 1;
 }
@@ -661,9 +663,23 @@ RefEnv *meshenv_ref_create(int n0, const double *xy, double original_area, doubl
     e->cap_e = cap_new + n0;
     e->vtab = (P2 *)malloc(sizeof(P2) * e->cap_v);
     e->quads = (int32_t *)malloc(sizeof(int32_t) * 4 * e->cap_e);
+    /* the reference's literals: B:52, M:26, M:213, C:722, C:721, B:601, M:540 */
+    const double def[7] = {4, PI * 0.972, 0.618, 0.01 * PI, 0.99 * PI, 0.001, 10000};
+    meshenv_ref_set_params(e, def);
+    return e;
+}
+
+void meshenv_ref_set_params(RefEnv *e, const double *p)
+{
+    e->radius = p[0];
+    e->max_ref_angle = p[1];
+    e->key_lambda = p[2];
+    e->min_degree = p[3];
+    e->max_degree = p[4];
+    e->same_point_eps = p[5];
+    e->ray_length = p[6];
     float obs[18];
     meshenv_ref_reset(e, obs);
-    return e;
 }
 
 void meshenv_ref_destroy(RefEnv *e)
@@ -745,7 +761,7 @@ int meshenv_ref_step(RefEnv *e, const float *action, float *obs, double *reward_
             if (is_point_inside_area(e, new_point)) {
                 int same = -1; /* find_same_point, B:616-619 */
                 for (int i = 0; i < n; i++)
-                    if (dist(e->ring[i], new_point) < 0.001) {
+                    if (dist(e->ring[i], new_point) < e->same_point_eps) {
                         same = i;
                         break;
                     }
@@ -769,7 +785,7 @@ int meshenv_ref_step(RefEnv *e, const float *action, float *obs, double *reward_
             }
             for (int k = 0; k < 4; k++) m[k] = mpos[k] < 0 ? new_point : e->ring[mpos[k]];
 
-            if (quad_is_valid(m) && !intersects_boundary(e, m, mpos, r)) {
+            if (quad_is_valid(e, m) && !intersects_boundary(e, m, mpos, r)) {
                 const double b_reward = extract_element(e, m, mpos, new_vertex, index, new_point, 1);
                 const double mesh_area = quad_area(m);
                 e->cur_area -= mesh_area;
@@ -839,8 +855,8 @@ int meshenv_ref_move(RefEnv *e, const double *point, double type, float *obs, ui
     if (e->n <= 5 || e->ref < 0) return MESHENV_REF_MOVE_RAISES;
     const int n = e->n, index = e->ref;
     /* B:283-287 */
-    const double x = ((e->bl * 4) * point[0]) * cos(point[1]);
-    const double y = ((e->bl * 4) * point[0]) * sin(point[1]);
+    const double x = ((e->bl * e->radius) * point[0]) * cos(point[1]);
+    const double y = ((e->bl * e->radius) * point[0]) * sin(point[1]);
     const double px = round6_py(x), py = round6_py(y);
     const P2 p0 = e->ring[index], p1 = e->ring[RI(index - 1, n)];
     const double theta = 2 * PI - atan2(p1.y - p0.y, p1.x - p0.x);
@@ -869,7 +885,7 @@ int meshenv_ref_move(RefEnv *e, const double *point, double type, float *obs, ui
     }
     if (have_mesh) {
         for (int k = 0; k < 4; k++) m[k] = mpos[k] < 0 ? new_point : e->ring[mpos[k]];
-        if (quad_is_valid(m) && !intersects_boundary(e, m, mpos, r)) {
+        if (quad_is_valid(e, m) && !intersects_boundary(e, m, mpos, r)) {
             not_valid = 0;
             extract_element(e, m, mpos, new_vertex, index, new_point, 0);
             none = find_next_state_opt(e, obs, 1, 1); /* B:362, still with the old not_valid_points */

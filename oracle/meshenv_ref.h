@@ -37,6 +37,11 @@ RefEnv *meshenv_ref_create(int n0, const double *xy, double original_area, doubl
                            double est_crit_l, int cap_new);
 void meshenv_ref_destroy(RefEnv *e);
 
+/* The seven geometry constants of MeshEnvParams (include/meshenv.h), in its order: radius, max_ref_angle, key_lambda,
+ * min_degree, max_degree, same_point_eps, ray_length.  meshenv_ref_create sets the reference's literals
+ * (4, 0.972*pi, 0.618, 0.01*pi, 0.99*pi, 0.001, 10000); this replaces them and resets the env. */
+void meshenv_ref_set_params(RefEnv *e, const double *p /*[7]*/);
+
 /* reset(): rl/boundary_env.py:67-84.  Writes obs[18]; returns 1 if the reference would return None. */
 int meshenv_ref_reset(RefEnv *e, float *obs);
 

@@ -130,9 +130,13 @@ def biased_actions(seed: int, T: int) -> np.ndarray:
     return a.astype(np.float32)
 
 
-def record_trace(points, actions: np.ndarray, auto_reset: bool = True) -> dict:
-    """Drive the reference env with `actions` and record everything parity needs."""
+def record_trace(points, actions: np.ndarray, auto_reset: bool = True, radius=None) -> dict:
+    """Drive the reference env with `actions` and record everything parity needs.  radius: the env's `radius` attribute
+    (rl/boundary_env.py:52) set before the first reset; the fixture then stores the seven MeshEnvParams geometry constants
+    as `params` (oracle/ref_lib.PARAM_NAMES order)."""
     env = make_env(points)
+    if radius is not None:
+        env.radius = radius
     n0 = len(points)
     T = len(actions)
     reset_obs = env.reset()
@@ -200,6 +204,9 @@ def record_trace(points, actions: np.ndarray, auto_reset: bool = True) -> dict:
                          consts["est_min_l"], consts["est_crit_l"]], np.float64),
         auto_reset=np.uint8(auto_reset),
     )
+    if radius is not None:
+        from oracle.ref_lib import DEFAULT_PARAMS, PARAM_NAMES
+        out["params"] = np.array([float(radius) if k == "radius" else DEFAULT_PARAMS[k] for k in PARAM_NAMES], np.float64)
     return out
 
 

@@ -52,7 +52,7 @@ EXPORTS = [
     "meshenv_counters", "meshenv_set_timing", "meshenv_kernel_times", "meshenv_selftest", "meshenv_set_packed_output",
     "meshenv_actor_create", "meshenv_actor_destroy", "meshenv_actor_set_stream", "meshenv_actor_load",
     "meshenv_actor_forward", "meshenv_actor_sample", "meshenv_get_last_episode", "meshenv_element_quality",
-    "meshenv_reset_static", "meshenv_move", "meshenv_get_not_valid", "meshenv_step_kernel",
+    "meshenv_reset_static", "meshenv_move", "meshenv_get_not_valid", "meshenv_step_kernel", "meshenv_rollout_kernel",
     "meshenv_create_random", "meshenv_get_domain", "meshenv_smooth", "meshenv_smooth_final", "meshenv_get_not_valid_ids", "meshenv_step_actor",
     "meshenv_libm_exact", "meshenv_create_random_density", "meshenv_density_rings",
     "meshenv_step_actor_multi", "meshenv_extract_samples", "meshenv_atan2_exact", "meshenv_quad_quality",
@@ -115,6 +115,8 @@ def load():
     L.meshenv_group_size.restype = C.c_int
     L.meshenv_step_kernel.argtypes = [vp]
     L.meshenv_step_kernel.restype = C.c_int
+    L.meshenv_rollout_kernel.argtypes = [vp]
+    L.meshenv_rollout_kernel.restype = C.c_int
     L.meshenv_libm_exact.argtypes = [vp]
     L.meshenv_libm_exact.restype = C.c_int
     L.meshenv_atan2_exact.argtypes = []

@@ -299,6 +299,30 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
         const int n0 = dom_offsets_host[d + 1] - dom_offsets_host[d];
         if (n0 < 4) return fail_arg(nullptr, "meshenv_create: a domain ring needs at least 4 vertices");
         max_ring = n0 > max_ring ? n0 : max_ring;
+        if (gen) continue;
+        // Domains on which the reference divides by zero (supported coordinate range): a zero area
+        // (current_area / original_area, rl/boundary_env.py) and a base length -- the mean of the six edges around a
+        // vertex rounded to 4 places (general/components.py) -- that rounds to 0 (observation = distance / base length).
+        const double area = dom_consts_host[3 * d];
+        if (!(area != 0.0) || !std::isfinite(area))
+            return fail_arg(nullptr, "meshenv_create: a domain's area is 0 or not finite (the reference divides by it; "
+                                     "far from the origin a small domain's shoelace area cancels)");
+        const double *xy = dom_xy_host + 2 * (size_t)dom_offsets_host[d];
+        for (int i = 0; i < 2 * n0; i++)
+            if (!(std::fabs(xy[i]) < 1e100))
+                return fail_arg(nullptr, "meshenv_create: a domain coordinate is not finite or not below 1e100 in magnitude");
+        auto edge = [&](int i) {   // length of edge (i, i + 1), indices mod n0
+            const int a = ((i % n0) + n0) % n0, b = (a + 1) % n0;
+            const double dx = xy[2 * a] - xy[2 * b], dy = xy[2 * a + 1] - xy[2 * b + 1];
+            return std::sqrt(dx * dx + dy * dy);
+        };
+        for (int i = 0; i < n0; i++) {
+            double sum = 0;
+            for (int k = -3; k < 3; k++) sum += edge(i + k);
+            if (!((sum / 6) * 1e4 > 0.5))
+                return fail_arg(nullptr, "meshenv_create: a domain's base length (mean of six consecutive edges) rounds "
+                                         "to 0 at 4 places (edges below 5e-5: the reference divides by it)");
+        }
     }
     for (int e = 0; e < n_envs; e++)
         if (env_domain_host[e] < 0 || env_domain_host[e] >= n_domains)
@@ -834,13 +858,21 @@ int meshenv_group_size(const MeshEnv *h) { return h ? h->group : MESHENV_E_ARG; 
 int meshenv_step_kernel(const MeshEnv *h)
 {
     if (!h) return MESHENV_E_ARG;
-    if (h->front_moved) return 3;
+    if (h->front_moved) return h->default_params ? 3 : 10;
     if (h->group <= 1) {
+        if (!h->default_params) return 9;
         const bool pre = h->default_params && (h->stage_bits & 2);
         return h->default_params && h->cap <= 64 ? (pre ? 8 : 6) : (pre ? 7 : 0);
     }
     if (h->env_lds) return 4;
     return h->cap <= 64 ? 5 : 1;
+}
+int meshenv_rollout_kernel(const MeshEnv *h)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (h->front_moved) return h->default_params ? 3 : 4;
+    if (!h->default_params) return 2;
+    return h->cap <= 64 ? 1 : 0;
 }
 int meshenv_libm_exact(const MeshEnv *h) { return h ? h->libm_exact : MESHENV_E_ARG; }
 int meshenv_atan2_exact(void) { return atan_host().mode == 2 ? 1 : 0; }
@@ -1495,11 +1527,35 @@ __global__ void k_selftest(int what, int n, const double *in, double *out, int l
     } else if (what == 14) out[i] = atan2_cr(in[2 * i], in[2 * i + 1]);
     else if (what == 15) out[i] = sincos_small_nc(in[i]).s;   // against the host libm's sin / cos: within an ulp
     else if (what == 16) out[i] = sincos_small_nc(in[i]).c;
+    else if (what == 17) {
+        // the x-slab pre-filter of the observation scan against what the unfiltered scan evaluates for one position:
+        // 7 doubles = ref (x, y), p_s - ref before rounding (qx, qy), target_length, v.x, b.x -- with v = (v.x, ref.y - 1),
+        // b = (b.x, ref.y + 1), an edge across the bisector's line.  out = 1 kept by the filter + 2 the bisector hits the
+        // edge + 4 the fan-slot distance d(ref, v) < target_length; a position with 2 or 4 but not 1 is a dropped one.
+        const double *q = in + 7 * (size_t)i;
+        const P2 ref = mkp(q[0], q[1]);
+        const double tl = q[4];
+        const double ux = (ref.x + q[2]) - ref.x, uy = (ref.y + q[3]) - ref.y;
+        const P2 v = mkp(q[5], ref.y - 1), b = mkp(q[6], ref.y + 1);
+        const double W = slab_half_width(tl);
+        const double slab_lo = ref.x - W, slab_hi = ref.x + W;
+        double s;
+        out[i] = (slab_keeps(slab_lo, slab_hi, v.x, b.x) ? 1.0 : 0.0) + (bisector_hits(ref, ux, uy, v, b, s) ? 2.0 : 0.0) +
+                 (dist(ref, v) < tl ? 4.0 : 0.0);
+    } else if (what == 18) {
+        // the per-edge pre-filter of point_inside against is_cross: 7 doubles = p (x, y), vi (x, y), vm (x, y),
+        // ray_length.  out = 1 the filter drops the edge + 2 is_cross(p -> (ray_length, p.y), vi - vm) holds; 3 = a
+        // counted edge dropped.
+        const double *q = in + 7 * (size_t)i;
+        const P2 p = mkp(q[0], q[1]), vi = mkp(q[2], q[3]), vm = mkp(q[4], q[5]), far = mkp(q[6], q[1]);
+        out[i] = (pip_filter_usable(fabs(q[6] - p.x)) && pip_edge_clear(p, vi, vm) ? 1.0 : 0.0) + (straddle(p, far, vi, vm) && straddle(vi, vm, p, far) ? 2.0 : 0.0);
+    }
 }
 
 int meshenv_selftest(int device, int what, int n, int in_per_item, const double *in_host, double *out_host)
 {
     if (n <= 0 || !in_host || !out_host || in_per_item <= 0) return MESHENV_E_ARG;
+    if ((what == 17 || what == 18) && in_per_item != 7) return MESHENV_E_ARG;   // 7 doubles per case (k_selftest)
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return MESHENV_E_HIP;
     double *din = nullptr, *dout = nullptr;

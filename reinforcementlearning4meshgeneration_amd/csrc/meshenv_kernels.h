@@ -380,6 +380,36 @@ __device__ __forceinline__ double dist_lr(const LibmRef lr, P2 a, P2 b)
     return sqrt_pos(pow2_nc(a.x - b.x) + pow2_nc(a.y - b.y));
 }
 
+// Half width of the observation scan's x-slab pre-filter (long rings, stage C of find_next_state): target_length with a
+// relative and an absolute 1e-9 (see the pre-filter's comment for why no term follows |ref.x|), and the filter's keep
+// test of an edge (v, b).  k_selftest 17 and tests/test_slab_filter_cpu.py check them at |ref.x| up to 1e9.
+__device__ __forceinline__ double slab_half_width(double target_length)
+{
+    return target_length * (1 + 1e-9) + 1e-9;
+}
+__device__ __forceinline__ bool slab_keeps(double slab_lo, double slab_hi, double vx, double bx)
+{
+    const double xlo = vx < bx ? vx : bx, xhi = vx < bx ? bx : vx;
+    return xlo <= slab_hi && xhi >= slab_lo;
+}
+
+// Segment(ref, ref + u).intersection_vertex(Segment(v, b)) hits, C:649-668: 0 < s < 1 and 0 < h < 1.  The three
+// branches of the reference (w.y == 0 / w.x == 0 / general) are one instruction stream with selected operands, so an
+// axis-aligned domain does not pay for all three in turn:  s = num / den,  h = (a + s * b) / cden
+__device__ __forceinline__ bool bisector_hits(P2 ref, double ux, double uy, P2 v, P2 b, double &s)
+{
+    const double wx = b.x - v.x, wy = b.y - v.y;
+    const bool hy = wy == 0.0, hx = !hy && wx == 0.0;
+    const double rx = ref.x - v.x, ry = ref.y - v.y;
+    const double num_g = rx / wx - ry / wy, den_g = uy / wy - ux / wx;
+    const double num = hy ? (v.y - ref.y) : (hx ? (v.x - ref.x) : num_g);
+    const double den = hy ? uy : (hx ? ux : den_g);
+    const bool have = !((hy && uy == 0.0) || (hx && ux == 0.0));
+    s = num / den;
+    const double h = hx ? (ry + s * uy) / wy : (rx + s * ux) / wx;
+    return have && 0.0 < s && s < 1.0 && 0.0 < h && h < 1.0;
+}
+
 __device__ __forceinline__ int nf_compact(Ctx &c, bool near, int i, int count);   // (below: survivors of a 64-lane chunk -> c.list)
 
 __device__ __forceinline__ void find_next_state(Ctx &c, const DevState &S, BqArgs &bq, const bool is_static = false,
@@ -524,7 +554,10 @@ __device__ __forceinline__ void find_next_state(Ctx &c, const DevState &S, BqArg
     //    fl(r + fl(s u)) lies between 0 and w up to a rounding, i.e. ref.x + s u lies in the edge's x-extent widened by
     //    4 ulp of (|r| + |u|), and with 0 < s < 1 it also lies in ref.x +- |u|, |u| <= target_length (1 + 2^-50); in the
     //    w.x == 0 branch s = fl((v.x - ref.x) / u) in (0, 1) says the same of v.x = b.x directly.
-    // So a position whose edge has no x in common with the slab ref.x +- W, W = target_length (1 + 1e-9) + 1e-9, changes
+    // No slack has to follow |ref.x|: rounding is monotone, so a representable v.x outside fl(ref.x +- W) lies outside
+    // ref.x +- W, and ref.x + u = fl(ref.x + qx) with |qx| <= target_length (1 + 2^-50) < W lies inside fl(ref.x +- W);
+    // the roundings left (of r + s u and of the quotients) follow |r| + |u|, i.e. the edge and target_length.
+    // So a position whose edge has no x in common with the slab ref.x +- W, W = slab_half_width(target_length), changes
     // nothing, whatever its (possibly ill-conditioned) quotients evaluate to; NaN coordinates fail every comparison in
     // both forms.  -DMESHENV_NO_FILTERS builds the unfiltered scan.  (Rings of at most 65 vertices: every position is
     // scanned, in place -- `count` = n - 1 positions, position j IS traversal order j.)
@@ -535,16 +568,14 @@ __device__ __forceinline__ void find_next_state(Ctx &c, const DevState &S, BqArg
 #endif
     int count = n - 1;
     if (long_ring) {
-        const double W = target_length * (1 + 1e-9) + 1e-9;
+        const double W = slab_half_width(target_length);
         const double slab_lo = ref.x - W, slab_hi = ref.x + W;
         int m = 0;
         for (int base = 0; base < n - 1; base += 64) {
             const int ord = base + lane;
             const bool in = ord < n - 1;
             const int ii = wrapi(idc - 1 - (in ? ord : 0), n);
-            const P2 v = ldp(c, ii), b = ldp(c, wrapi(ii + 1, n));
-            const double xlo = v.x < b.x ? v.x : b.x, xhi = v.x < b.x ? b.x : v.x;
-            m = nf_compact(c, in && xlo <= slab_hi && xhi >= slab_lo, ord, m);
+            m = nf_compact(c, in && slab_keeps(slab_lo, slab_hi, ldp(c, ii).x, ldp(c, wrapi(ii + 1, n)).x), ord, m);
         }
         count = m;
         wave_sync();
@@ -609,20 +640,9 @@ __device__ __forceinline__ void find_next_state(Ctx &c, const DevState &S, BqArg
                 else if (k == 1) k1 = key < k1 ? key : k1;
                 else k2 = key < k2 ? key : k2;
             }
-            // Segment(ref, p_s).intersection_vertex(Segment(ring[i], ring[i+1])), C:649-668.  The three branches of
-            // the reference (w.y == 0 / w.x == 0 / general) are one instruction stream with selected operands, so an
-            // axis-aligned domain does not pay for all three in turn:  s = num / den,  h = (a + s * b) / cden
-            const P2 b = ldp(c, wrapi(ii + 1, n));
-            const double wx = b.x - v.x, wy = b.y - v.y;
-            const bool hy = wy == 0.0, hx = !hy && wx == 0.0;
-            const double rx = ref.x - v.x, ry = ref.y - v.y;
-            const double num_g = rx / wx - ry / wy, den_g = uy / wy - ux / wx;
-            const double num = hy ? (v.y - ref.y) : (hx ? (v.x - ref.x) : num_g);
-            const double den = hy ? uy : (hx ? ux : den_g);
-            const bool have = !((hy && uy == 0.0) || (hx && ux == 0.0));
-            const double s = num / den;
-            const double h = hx ? (ry + s * uy) / wy : (rx + s * ux) / wx;
-            if (have && 0.0 < s && s < 1.0 && 0.0 < h && h < 1.0) {
+            // Segment(ref, p_s).intersection_vertex(Segment(ring[i], ring[i+1])), C:649-668
+            double s;
+            if (bisector_hits(ref, ux, uy, v, ldp(c, wrapi(ii + 1, n)), s)) {
                 const double val = (dist_lr(lr, ref, mkp(ref.x + s * ux, ref.y + s * uy)) / radius) / bl;
                 if (val < rbest) { rbest = val; rord = ord; }
             }
@@ -758,13 +778,26 @@ __device__ __forceinline__ bool edge_counted(const Ctx &c, P2 p, P2 far, int ic,
     return counted;
 }
 
+// The per-edge pre-filter of point_inside (rings > 64): edge (vm, vi) lies clear of the ray's line, so is_cross cannot
+// count it (see point_inside).  The lemma needs products of L - p.x with a, b and the x offsets that neither underflow
+// nor overflow: the filter runs only while span = |L - p.x| lies in (1e-140, 1e140) (pip_filter_usable, one test per
+// point); meshenv_create keeps domain coordinates below 1e100, so a, b and the offsets stay far below overflow.
+// k_selftest 18 checks the pair against is_cross.
+__device__ __forceinline__ bool pip_filter_usable(double span) { return span > 1e-140 && span < 1e140; }
+__device__ __forceinline__ bool pip_edge_clear(P2 p, P2 vi, P2 vm)
+{
+    const double a = vi.y - p.y, b = vm.y - p.y;
+    const double ma = fmax(2e-3 * fabs(vi.x - p.x), 1e-9), mb = fmax(2e-3 * fabs(vm.x - p.x), 1e-9);
+    return (a > ma && b > mb) || (a < -ma && b < -mb);
+}
+
 __device__ __forceinline__ bool point_inside(Ctx &c, const Params &prm, P2 p)
 {
     const int n = c.n;
     const P2 far = mkp(prm.ray_length, p.y);
     int parity = 0;
 #ifndef MESHENV_NO_FILTERS
-    if (n > 64) {
+    if (n > 64 && pip_filter_usable(fabs(prm.ray_length - p.x))) {
         // Rings of several 64-vertex chunks: an exact pre-filter per edge, the survivors compacted (c.list), and the
         // crossing test itself once over the survivors instead of once per chunk.  An edge whose endpoints lie strictly on
         // the same side of the ray's line cannot be counted: with a = vi.y - p.y, b = vm.y - p.y of equal sign and
@@ -778,11 +811,7 @@ __device__ __forceinline__ bool point_inside(Ctx &c, const Params &prm, P2 p)
             const int i = i0 + c.lane;
             const bool in = i < n;
             const int ic = in ? i : 0;
-            const P2 vi = ldp(c, ic), vm = ldp(c, wrapi(ic - 1, n));
-            const double a = vi.y - p.y, b = vm.y - p.y;
-            const double ma = fmax(2e-3 * fabs(vi.x - p.x), 1e-9), mb = fmax(2e-3 * fabs(vm.x - p.x), 1e-9);
-            const bool clear = (a > ma && b > mb) || (a < -ma && b < -mb);
-            count = nf_compact(c, in && !clear, i, count);
+            count = nf_compact(c, in && !pip_edge_clear(p, ldp(c, ic), ldp(c, wrapi(ic - 1, n))), i, count);
         }
         wave_sync();
         for (int j0 = 0; j0 < count; j0 += 64) {

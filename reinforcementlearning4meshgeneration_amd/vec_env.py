@@ -373,8 +373,16 @@ class MeshVecEnv:
         return {0: "meshenv::k_step<false, true, false, false, false>", 6: "meshenv::k_step<false, true, false, true, false>",
                 7: "meshenv::k_step<false, true, false, false, true>", 8: "meshenv::k_step<false, true, false, true, true>", 1: f"meshenv::k_step_group<{self.group_size}, true, false, false>",
                 3: "meshenv::k_step<false, true, true, false, false>",
+                9: "meshenv::k_step<false, false, false, false, false>", 10: "meshenv::k_step<false, false, true, false, false>",
                 4: "meshenv::k_step_group<16, true, true, false>",
                 5: f"meshenv::k_step_group<{self.group_size}, true, false, true>"}[self._L.meshenv_step_kernel(self._handle)]
+
+    @property
+    def rollout_kernel(self) -> str:
+        """Name of the kernel rollout() (T > 1 steps in one launch) launches, from meshenv_rollout_kernel."""
+        return {0: "meshenv::k_step<true, true, false, false, false>", 1: "meshenv::k_step<true, true, false, true, false>",
+                2: "meshenv::k_step<true, false, false, false, false>", 3: "meshenv::k_step<true, true, true, false, false>",
+                4: "meshenv::k_step<true, false, true, false, false>"}[self._L.meshenv_rollout_kernel(self._handle)]
 
     @property
     def libm_exact(self) -> int:

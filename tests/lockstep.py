@@ -7,21 +7,22 @@ TOL = 1e-5
 
 
 def run_lockstep(torch, domains, env_domain, actions, check_every=64, sample=64, rollout=False, policy=None, T=None,
-                 threads=8, invariants=None):
+                 threads=8, invariants=None, params=None):
     """Step the HIP env and the CPU oracle on the same actions; compare everything.
 
     actions  float32 [T, n, 3] (open loop), or None with policy = callable(t, obs_dev) -> float32 CUDA [n, 3]
              (closed loop: the policy sees the DEVICE observation; the oracle is fed the actions it emitted)
-    invariants  optional callable(env, t) run at the ring-check steps (size-independent property checks)"""
+    invariants  optional callable(env, t) run at the ring-check steps (size-independent property checks)
+    params   MeshEnvParams geometry constants (oracle/ref_lib.PARAM_NAMES) given to both sides"""
     from oracle.ref_lib import RefBatch, RefEnv
     from reinforcementlearning4meshgeneration_amd.vec_env import MeshVecEnv
 
     n = len(env_domain)
     T = actions.shape[0] if actions is not None else int(T)
-    env = MeshVecEnv(domains, env_domain=env_domain, auto_reset=True, log_capacity=0)
+    env = MeshVecEnv(domains, env_domain=env_domain, auto_reset=True, log_capacity=0, params=params)
     consts = env.constants
     refs = [RefEnv(np.asarray(domains[d], np.float64), consts[d].original_area, consts[d].est_min_l,
-                   consts[d].est_crit_l, cap_new=64) for d in env_domain]
+                   consts[d].est_crit_l, cap_new=64, params=params) for d in env_domain]
     batch = RefBatch(refs)
     obs_ref = batch.reset().copy()
     obs = env.reset().cpu().numpy()
@@ -30,6 +31,7 @@ def run_lockstep(torch, domains, env_domain, actions, check_every=64, sample=64,
     obs_dev = env.obs
     stats = dict(obs_mismatch=0, obs_total=0, max_obs=0.0, max_rew=0.0, valid=0, done=0)
     if rollout:
+        stats["rollout_kernel"] = env.rollout_kernel
         _, rew_all, done_all, comp_all = env.rollout(acts_dev)
         rew_all = rew_all.cpu().numpy(); done_all = done_all.cpu().numpy(); comp_all = comp_all.cpu().numpy()
     rng = np.random.default_rng(0)
@@ -78,6 +80,7 @@ def run_lockstep(torch, domains, env_domain, actions, check_every=64, sample=64,
         assert np.abs(o.astype(np.float64) - batch.obs).max() <= TOL
     cnt = env.counters()
     stats["valid"] = cnt["valid"]
+    stats["kernel"] = env.step_kernel
     assert cnt["steps"] == T * n
     if n <= 512:
         assert cnt["sum_ring"] == sum_ring, (cnt, sum_ring)

@@ -1,0 +1,374 @@
+"""GPU: the step kernels against the CPU oracle on scaled and shifted domains and with non-default geometry constants.
+
+Every fixture domain has coordinates of order 1-20, while MeshVecEnv accepts any magnitude; the kernels' exact shortcuts
+(the long-ring pre-filters of the observation scan and of point_inside, the dist_lt band, the cw_fast and collinearity
+guard bands, the early quad rejection) argue exactness with absolute constants.  Here the same lockstep bars as
+tests/test_gpu_parity.py hold on boundary(0) and the d1 / d2 / d3 rings (120 / 196 / 272 vertices) under
+x -> scale x + shift, through every step instantiation, and with each MeshEnvParams geometry constant changed (the
+instantiations that read them at run time, against the parametrised oracle).  Each test asserts the kernel it ran and a
+minimum number of accepted extractions.  The two ring pre-filters are also checked case by case (meshenv_selftest)."""
+import math
+import os
+import time
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN_DIR
+from lockstep import run_lockstep
+
+pytestmark = pytest.mark.gpu
+
+# (id, scale, dx, dy)
+TRANSFORMS = [("x1em4", 1e-4, 0.0, 0.0), ("x1em2", 1e-2, 0.0, 0.0), ("x1e2", 1e2, 0.0, 0.0), ("x1e4", 1e4, 0.0, 0.0),
+              ("dx1e4", 1.0, 1e4, 0.0), ("dx1e6", 1.0, 1e6, 0.0), ("dx1e8", 1.0, 1e8, 0.0),
+              ("dy1e4", 1.0, 0.0, 1e4), ("dy1e6", 1.0, 0.0, 1e6), ("dy1e8", 1.0, 0.0, 1e8),
+              ("x1e3_d1e6", 1e3, 1e6, -1e6), ("x1e2_dm1e6", 1e2, -1e6, 1e6)]
+# The reference places new vertices on a 1e-4 lattice (4-place rounding), so its extractions need edges well above 1e-4:
+# x1e-4 runs the rings enlarged x100 first (boundary(0) 1200 units wide), i.e. coordinates up to 0.12.  The fixture
+# rings themselves at x1e-4 (base length rounding to 0) and x1e-2 shifted by 1e8 (shoelace area cancelling to 0) are
+# domains the reference divides by zero on: meshenv_create refuses them (test_create_refuses_domains_the_reference_divides_by_zero_on).
+PRESCALE = {"x1em4": 100.0}
+# Minimum accepted extractions per 1000 env-steps of the mixed batch.  Few at x1e4: the domains reach past the ray end at
+# x = 10000, so the reference tests most candidate points outside.
+MIN_VALID_PER_1000 = {"x1em4": 60, "x1e4": 2, "x1em2": 60, "x1e2_dm1e6": 100}
+DEFAULT_MIN_VALID_PER_1000 = 100
+
+
+def _rings():
+    from reinforcementlearning4meshgeneration_amd import boundary
+    long = [[tuple(p) for p in np.load(os.path.join(GOLDEN_DIR, f + ".npz"))["domain_xy"]]
+            for f in ("boundary16_biased_s2", "boundary15_biased_s5", "test1_biased_s42")]
+    return [[tuple(p) for p in boundary(0)]] + long
+
+
+def _transform(rings, scale, dx, dy, pre=1.0):
+    return [[(scale * (pre * x) + dx, scale * (pre * y) + dy) for x, y in r] for r in rings]
+
+
+def _actions(n, T, seed):
+    rng = np.random.default_rng(seed)
+    a = rng.uniform([-1, -1.5, 0], [1, 1.5, 1.5], size=(T, n, 3))
+    pick = rng.random((T, n)) < 0.6
+    b = np.stack([rng.uniform(-1, 1, (T, n)), rng.uniform(0.2, 1.0, (T, n)), rng.uniform(0.3, 1.2, (T, n))], axis=2)
+    a[pick] = b[pick]
+    return a.astype(np.float32)
+
+
+def _min_valid(tid, n, T):
+    return MIN_VALID_PER_1000.get(tid, DEFAULT_MIN_VALID_PER_1000) * n * T // 1000
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a ROCm device")
+    return torch
+
+
+@pytest.mark.parametrize("tid,scale,dx,dy", TRANSFORMS, ids=[t[0] for t in TRANSFORMS])
+def test_transformed_domains_lockstep(torch_cuda, tid, scale, dx, dy):
+    """Mixed boundary(0) / d1 / d2 / d3 batches: the CU-group kernel with ragged LDS (4096 envs) and the one-wave kernel
+    (600 envs), every step against the oracle."""
+    t0 = time.time()
+    doms = _transform(_rings(), scale, dx, dy, PRESCALE.get(tid, 1.0))
+    got = []
+    for n, T, want in ((4096, 24, "meshenv::k_step_group<16, true, true, false>"),
+                       (600, 48, "meshenv::k_step<false, true, false, false, false>")):
+        st = run_lockstep(torch_cuda, doms, (np.arange(n) % 4).astype(np.int32), _actions(n, T, 7), check_every=12,
+                          sample=48, threads=16)
+        assert st["kernel"] == want, (n, st["kernel"])
+        assert st["valid"] >= _min_valid(tid, n, T), (tid, n, st["valid"])
+        got.append((st["kernel"], st["valid"]))
+    print(f"{tid}: {got} in {time.time() - t0:.1f} s")
+
+
+GROUP_TRANSFORMS = [t for t in TRANSFORMS if t[0] in ("x1em4", "x1em2", "x1e2", "dx1e8", "dy1e6", "x1e3_d1e6", "x1e2_dm1e6")]
+
+
+@pytest.mark.parametrize("tid,scale,dx,dy", GROUP_TRANSFORMS, ids=[t[0] for t in GROUP_TRANSFORMS])
+def test_transformed_small_ring_kernels_lockstep(torch_cuda, tid, scale, dx, dy):
+    """boundary(0) alone (a ring of at most 64 slots): k_step_group<16> at 4096 envs, <8> at 2048, the ragged group
+    kernel with a long ring in the batch is above; the record-first / early-rejection form (kPre) at 8192 envs and the
+    multi-step rollout kernel."""
+    t0 = time.time()
+    ring = _transform(_rings()[:1], scale, dx, dy, PRESCALE.get(tid, 1.0))
+    got = []
+    for n, T, want in ((4096, 24, "meshenv::k_step_group<16, true, false, true>"),
+                       (2048, 24, "meshenv::k_step_group<8, true, false, true>"),
+                       (8192, 12, "meshenv::k_step<false, true, false, true, true>")):
+        st = run_lockstep(torch_cuda, ring, np.zeros(n, np.int32), _actions(n, T, 11), check_every=12, sample=32,
+                          threads=16)
+        assert st["kernel"] == want, (n, st["kernel"])
+        assert st["valid"] >= _min_valid(tid, n, T), (tid, n, st["valid"])
+        got.append((st["kernel"], st["valid"]))
+    n, T = 1024, 24
+    st = run_lockstep(torch_cuda, ring, np.zeros(n, np.int32), _actions(n, T, 13), rollout=True, threads=16)
+    assert st["rollout_kernel"] == "meshenv::k_step<true, true, false, true, false>", st["rollout_kernel"]
+    assert st["valid"] >= _min_valid(tid, n, T), (tid, "rollout", st["valid"])
+    got.append((st["rollout_kernel"], st["valid"]))
+    print(f"{tid}: {got} in {time.time() - t0:.1f} s")
+
+
+PARAMS = [("radius3", dict(radius=3.0)), ("radius5", dict(radius=5.0)), ("lambda05", dict(key_lambda=0.5)),
+          ("maxref09", dict(max_ref_angle=0.9 * math.pi)),
+          ("degrees", dict(min_degree=0.05 * math.pi, max_degree=0.95 * math.pi)),
+          ("noguard", dict(min_degree=0.0, max_degree=math.pi)),
+          ("same0", dict(same_point_eps=0.0)), ("same001", dict(same_point_eps=0.01)),
+          ("ray500", dict(ray_length=500.0)), ("ray1e6", dict(ray_length=1e6))]
+
+
+@pytest.mark.parametrize("pid,params", PARAMS, ids=[p[0] for p in PARAMS])
+def test_runtime_constants_against_the_parametrised_oracle(torch_cuda, pid, params):
+    """step (k_step<false, false>), rollout and move() with one geometry constant changed, against the oracle with the
+    same constant, on boundary(0) and d1."""
+    t0 = time.time()
+    doms = _rings()[:2]
+    n, T = 1024, 32
+    st = run_lockstep(torch_cuda, doms, (np.arange(n) % 2).astype(np.int32), _actions(n, T, 17), check_every=16,
+                      sample=48, threads=16, params=params)
+    assert st["kernel"] == "meshenv::k_step<false, false, false, false, false>", st["kernel"]
+    assert st["valid"] >= 0.05 * n * T, st["valid"]
+    sr = run_lockstep(torch_cuda, doms, (np.arange(n) % 2).astype(np.int32), _actions(n, T, 19), rollout=True,
+                      threads=16, params=params)
+    assert sr["rollout_kernel"] == "meshenv::k_step<true, false, false, false, false>", sr["rollout_kernel"]
+    assert sr["valid"] >= 0.05 * n * T, sr["valid"]
+    mv = _move_lockstep(torch_cuda, doms, params, n=256, T=40)
+    print(f"{pid}: step valid {st['valid']}, rollout valid {sr['valid']}, move valid {mv} in {time.time() - t0:.1f} s")
+
+
+def test_runtime_constants_combined_on_a_long_ring(torch_cuda):
+    """All seven constants changed at once, on d3 (272 vertices: the multi-chunk pre-filters) shifted by 1e6."""
+    params = dict(radius=5.0, max_ref_angle=0.95 * math.pi, key_lambda=0.55, min_degree=0.03 * math.pi,
+                  max_degree=0.97 * math.pi, same_point_eps=0.005, ray_length=2e7)
+    doms = _transform(_rings()[3:], 1.0, 1e6, 0.0)
+    n, T = 512, 40
+    st = run_lockstep(torch_cuda, doms, np.zeros(n, np.int32), _actions(n, T, 23), check_every=20, sample=32,
+                      threads=16, params=params)
+    assert st["kernel"] == "meshenv::k_step<false, false, false, false, false>", st["kernel"]
+    assert st["valid"] >= 0.05 * n * T, st["valid"]
+    mv = _move_lockstep(torch_cuda, doms, params, n=128, T=30)
+    print(f"combined on d3 + 1e6: step valid {st['valid']}, move valid {mv}")
+
+
+CLOSED_LOOP_TRANSFORMS = [t for t in TRANSFORMS if t[0] in ("x1em4", "x1e2", "dx1e8", "x1e3_d1e6")]
+
+
+@pytest.mark.parametrize("tid,scale,dx,dy", CLOSED_LOOP_TRANSFORMS, ids=[t[0] for t in CLOSED_LOOP_TRANSFORMS])
+def test_transformed_closed_loop_policies_against_the_oracle(torch_cuda, tid, scale, dx, dy):
+    """The closed-loop paths on transformed boundary(0), 4096 envs: collect_rollout with a fused PPO policy (one policy
+    launch and one CU-group step launch per vector step) and the fused step + SAC actor kernel (meshenv_step_actor: the
+    actor appended to k_step_group<16>); the oracle replays the actions on a 256-env subset (envs are independent)."""
+    import sys
+    torch = torch_cuda
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_gpu_policy import _fused, _modules
+    from oracle.ref_lib import RefBatch, RefEnv
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    from reinforcementlearning4meshgeneration_amd.actor import FusedActor
+    t0 = time.time()
+    ring = _transform(_rings()[:1], scale, dx, dy, PRESCALE.get(tid, 1.0))[0]
+    n, T, sub = 4096, 32, 256
+    torch.manual_seed(5)
+    _, _, m = _modules(torch, "ppo", 5)
+    with torch.no_grad():
+        m["action_net"].weight.mul_(6.0)
+        m["log_std"].fill_(-0.5)
+    pol = _fused("ppo", m)
+    lin = [torch.nn.Linear(18, 128), torch.nn.Linear(128, 128), torch.nn.Linear(128, 128)]
+    mu, ls = torch.nn.Linear(128, 3), torch.nn.Linear(128, 3)
+    with torch.no_grad():
+        mu.weight.mul_(6.0)
+        ls.bias.fill_(-0.5)
+    actor = FusedActor.from_torch(lin, mu, ls)
+
+    def oracle_replay(acts, obs, rew, done, comp, env):
+        c = env.constants[0]
+        batch = RefBatch([RefEnv(np.asarray(ring, np.float64), c.original_area, c.est_min_l, c.est_crit_l, cap_new=64)
+                          for _ in range(sub)])
+        o_ref = batch.reset()
+        for t in range(T):
+            assert np.abs(obs[t].astype(np.float64) - o_ref).max() <= 1e-5, t
+            o_ref, r_ref, d_ref, c_ref = batch.step(acts[t], auto_reset=True, threads=16)
+            np.testing.assert_array_equal(done[t], d_ref, err_msg=f"done step {t}")
+            np.testing.assert_array_equal(comp[t], c_ref, err_msg=f"complete step {t}")
+            assert np.abs(rew[t] - r_ref).max() <= 1e-5, t
+        return o_ref
+
+    got = []
+    env = MeshVecEnv([ring], n_envs=n, auto_reset=True)
+    assert env.step_kernel == "meshenv::k_step_group<16, true, false, true>", env.step_kernel
+    out = env.collect_rollout(pol, T, seed=5, counter=0)
+    o_last = oracle_replay(out["actions"][:, :sub].cpu().numpy(), out["obs"][:, :sub].cpu().numpy(),
+                           *(out[k][:, :sub].cpu().numpy() for k in ("reward", "done", "complete")), env)
+    assert np.abs(env.obs[:sub].cpu().numpy().astype(np.float64) - o_last).max() <= 1e-5
+    valid = env.counters()["valid"]
+    assert valid >= _min_valid(tid, n, T), (tid, "collect_rollout", valid)
+    got.append(("collect_rollout", env.step_kernel, valid))
+    env.close()
+
+    env = MeshVecEnv([ring], n_envs=n, auto_reset=True)
+    assert env.group_size == 16 and env.step_kernel == "meshenv::k_step_group<16, true, false, true>", env.step_kernel
+    obs = env.reset()
+    act = actor.sample(obs, seed=9, counter=0).clone()
+    acts, obss, rews, dones, comps = [], [], [], [], []
+    for t in range(T):
+        obss.append(obs[:sub].cpu().numpy())
+        acts.append(act[:sub].cpu().numpy())
+        o, r, d, c, nxt = env.step_actor(actor, act, seed=9, counter=t + 1)
+        rews.append(r[:sub].cpu().numpy()); dones.append(d[:sub].cpu().numpy()); comps.append(c[:sub].cpu().numpy())
+        obs, act = o.clone(), nxt.clone()
+    o_last = oracle_replay(np.stack(acts), np.stack(obss), np.stack(rews), np.stack(dones), np.stack(comps), env)
+    assert np.abs(obs[:sub].cpu().numpy().astype(np.float64) - o_last).max() <= 1e-5
+    valid = env.counters()["valid"]
+    assert valid >= _min_valid(tid, n, T), (tid, "step_actor", valid)
+    got.append(("step_actor", "k_step_group_actor<true, true>", valid))
+    env.close(); pol.close(); actor.close()
+    print(f"{tid}: {got} in {time.time() - t0:.1f} s")
+
+
+@pytest.mark.parametrize("scale,dx,dy,rings", [(1e-4, 0.0, 0.0, (1, 2, 3)), (1e-5, 0.0, 0.0, (0,)),
+                                               (1e-2, 1e8, 1e8, (0, 1, 2))],
+                         ids=["x1em4_d123", "x1em5_boundary0", "x1em2_d1e8"])
+def test_create_refuses_domains_the_reference_divides_by_zero_on(torch_cuda, scale, dx, dy, rings):
+    """A base length that rounds to 0 at 4 places, or a shoelace area of 0: the reference raises ZeroDivisionError (the
+    oracle's reset observation is not finite); meshenv_create refuses the domain with a clear error."""
+    from oracle.ref_lib import RefEnv
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    doms = _transform(_rings(), scale, dx, dy)
+    for k in rings:
+        assert not np.isfinite(RefEnv.from_points(doms[k], cap_new=8).reset()[0]).all(), k
+        with pytest.raises(RuntimeError, match="base length|area"):
+            MeshVecEnv([doms[k]], n_envs=64)
+    # the same batch sizes on the domains next to them are accepted
+    ok = _transform(_rings(), scale * 10 if dx == 0 else 1.0, dx, dy)
+    MeshVecEnv([ok[rings[0]]], n_envs=64).close()
+
+
+def test_create_refuses_coordinates_beyond_1e100(torch_cuda):
+    """The point_inside pre-filter's exactness needs finite products of coordinate differences: meshenv_create refuses
+    a domain with a coordinate of 1e100 or more, and accepts the same ring just inside the bound."""
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    ring = _rings()[0]
+    for bad in ([(x + 1e100, y) for x, y in ring], [(x, y * 1e100) for x, y in ring]):
+        with pytest.raises(RuntimeError, match="1e100|area"):
+            MeshVecEnv([bad], n_envs=64)
+    MeshVecEnv([[(x * 1e90, y * 1e90) for x, y in ring]], n_envs=64).close()
+
+
+def _move_lockstep(torch, doms, params, n, T):
+    """move() on the device against RefEnv.move with the same constants; returns the accepted moves."""
+    from oracle.ref_lib import RefEnv
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    env_domain = (np.arange(n) % len(doms)).astype(np.int32)
+    env = MeshVecEnv(doms, env_domain=env_domain, auto_reset=False, log_capacity=256, params=params)
+    refs = [RefEnv.from_points(doms[d], cap_new=256, params=params) for d in env_domain]
+    obs = env.reset(static=True).cpu().numpy()
+    np.testing.assert_array_equal(obs, np.stack([r.reset(static=True)[0] for r in refs]))
+    rng = np.random.default_rng(29)
+    valid = 0
+    for t in range(T):
+        pts = np.stack([rng.uniform(0.05, 0.45, n), rng.uniform(0.2, 1.5, n)], axis=1)
+        typ = rng.uniform(0, 1, n)
+        o, d, c, code = [x.cpu().numpy() for x in env.move(torch.from_numpy(pts), torch.from_numpy(typ))]
+        reset_mask = np.zeros(n, np.uint8)
+        for k in range(n):
+            n_before = refs[k].scalars()["n_elem"]
+            o_r, d_r, c_r, code_r = refs[k].move(pts[k], typ[k])
+            assert code[k] == code_r, (t, k, code[k], code_r)
+            if code_r != 2:
+                assert bool(d[k]) == d_r and bool(c[k]) == c_r, (t, k)
+            if code_r == 0:
+                assert np.abs(o[k].astype(np.float64) - o_r).max() <= 1e-5, (t, k)
+            valid += refs[k].scalars()["n_elem"] > n_before
+            if d_r or code_r >= 2:
+                reset_mask[k] = 1
+                refs[k].reset(static=True)
+        if reset_mask.any():
+            env.reset(mask=torch.from_numpy(reset_mask), static=True)
+    for k in range(0, n, max(1, n // 32)):
+        st = env.get_state(k)
+        ids, xy = refs[k].ring()
+        np.testing.assert_array_equal(st["ring_ids"], ids)
+        assert np.array_equal(st["ring_xy"], xy)
+    env.close()
+    assert valid >= 0.05 * n * T, valid
+    return valid
+
+
+# ------------------------------------------------------------------------------------------------ the pre-filters alone
+def _selftest(what, items):
+    from reinforcementlearning4meshgeneration_amd import _capi
+    L = _capi.load()
+    items = np.ascontiguousarray(items, np.float64)
+    out = np.zeros(items.shape[0], np.float64)
+    assert L.meshenv_selftest(0, what, items.shape[0], items.shape[1], items.ctypes.data, out.ctypes.data) == 0
+    return out
+
+
+def test_slab_prefilter_selftest_against_the_cpu_restatement():
+    """meshenv_selftest 17 on the CPU search's cases (tests/test_slab_filter_cpu.py): the device's filter, bisector and
+    fan-slot decisions equal the Python restatement's, and no counted position is dropped."""
+    from test_slab_filter_cpu import bisector_hits, cases, slab_half_width
+    hw = slab_half_width
+    items, want = [], []
+    for ref, q, tl, v, b in cases():
+        if v[0] != b[0]:
+            continue                     # the self-test's edge is vertical: (v.x, ref.y - 1) -> (b.x, ref.y + 1)
+        items.append([ref[0], ref[1], q[0], q[1], tl, v[0], b[0]])
+        ux, uy = (ref[0] + q[0]) - ref[0], (ref[1] + q[1]) - ref[1]
+        W = hw(ref[0], tl)
+        keep = min(v[0], b[0]) <= ref[0] + W and max(v[0], b[0]) >= ref[0] - W
+        hit = bisector_hits(ref, (ux, uy), (v[0], ref[1] - 1.0), (b[0], ref[1] + 1.0))
+        dx, dy = ref[0] - v[0], ref[1] - (ref[1] - 1.0)
+        fan = math.sqrt(dx * dx + dy * dy) < tl
+        want.append(int(keep) + 2 * int(hit) + 4 * int(fan))
+    out = _selftest(17, np.array(items)).astype(np.int64)
+    want = np.array(want)
+    assert (out == want).all(), np.flatnonzero(out != want)[:5]
+    dropped = ((out & 6) != 0) & ((out & 1) == 0)
+    assert not dropped.any() and int(((out & 6) != 0).sum()) > 1000, int(dropped.sum())
+    print(f"slab self-test: {len(out)} cases, {int(((out & 6) != 0).sum())} counted, 0 dropped")
+
+
+def _pip_cases():
+    """(p, vi, vm, ray_length): edges whose endpoints sit k ulp beyond the pre-filter's clear margin on each side of
+    the ray's line (the filter may drop them), edges with one endpoint on each side or on the line (it must keep those,
+    and many cross the ray), at |p| from 1e-300 to 1e300, with p.x == ray_length exactly and p.x beyond it."""
+    rng = np.random.default_rng(3)
+    out = []
+    for e in (-300, -150, -20, -5, 0, 3, 6, 9, 20, 150, 300):
+        m = 10.0 ** e
+        for L in (10000.0, 500.0, 1e6, m, 2 * m):
+            for px in (m, -m, L, math.nextafter(L, 0), math.nextafter(L, math.inf), 1.5 * L + m, 0.0):
+                py = float(rng.uniform(-1, 1)) * m
+                for dxi, dxm in ((0.3 * m, -0.7 * m), (2 * m, 3 * m), (0.0, 0.0), (-m, m)):
+                    mi = max(2e-3 * abs(dxi), 1e-9)
+                    mm = max(2e-3 * abs((px + dxm) - px), 1e-9)
+                    for side in (1.0, -1.0):
+                        for k in range(0, 4):
+                            yi, ym = py + side * mi, py + side * mm
+                            for _ in range(k):
+                                yi, ym = math.nextafter(yi, side * math.inf), math.nextafter(ym, side * math.inf)
+                            out.append([px, py, px + dxi, yi, px + dxm, ym, L])
+                    # across the line: one endpoint above, one below or exactly on it, the edge ahead of p (crossings)
+                    ahead = 0.5 * (L - px) if L != px else m
+                    for ya, yb in ((py + mi, py - mm), (py + 2 * mi, py), (py, py - 3 * mm), (py + m, py - m)):
+                        out.append([px, py, px + ahead, ya, px + ahead + dxi * 1e-3, yb, L])
+    items = np.array(out, np.float64)
+    return items[np.isfinite(items).all(axis=1)]
+
+
+def test_point_inside_prefilter_selftest():
+    """meshenv_selftest 18: an edge the point_inside pre-filter drops is never one is_cross counts, including a point
+    exactly on the ray end, points past it, and near-underflow / near-overflow magnitudes (the 1e-300 cases once
+    found p = (-1e-300, -4e-301), ray_length 1e-300 dropped although counted: the products underflowed)."""
+    items = _pip_cases()
+    out = _selftest(18, items).astype(np.int64)
+    assert not (out == 3).any(), items[out == 3][:3]
+    assert int((out & 1).sum()) > 1000 and int(((out & 2) != 0).sum()) > 500, (int((out & 1).sum()), int((out & 2).sum()))
+    a, b = items[:, 3] - items[:, 1], items[:, 5] - items[:, 1]
+    across = ~((a > 0) & (b > 0)) & ~((a < 0) & (b < 0))   # an endpoint on each side of the ray's line, or on it: kept
+    assert not (out[across] & 1).any(), items[across][(out[across] & 1) != 0][:3]
+    print(f"point_inside pre-filter self-test: {len(out)} cases, {int((out & 1).sum())} dropped, {int((out & 2).sum() // 2)} crossing")

@@ -87,3 +87,61 @@ def test_no_helper_and_no_filters_builds_agree_with_the_default_library():
         assert res["valid_long"] == base["valid_long"] > 20000 and res["checksum_long"] == base["checksum_long"], (name, res, base)
     assert base["kernels_long"] == ["meshenv::k_step_group<16, true, true, false>", "meshenv::k_step<false, true, false, false, false>"]
 
+
+
+CHILD_XF = r"""
+import json, os, sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+gold = os.path.join(sys.argv[1], "tests", "golden")
+rings = [[tuple(p) for p in np.load(os.path.join(gold, f + ".npz"))["domain_xy"]] for f in ("boundary16_biased_s2", "boundary15_biased_s5", "test1_biased_s42")]
+res, arrays = {}, {}
+for tid, scale, dx, dy in (("x1e4", 1e4, 0.0, 0.0), ("dx1e8", 1.0, 1e8, 0.0), ("dy1e8", 1.0, 0.0, 1e8), ("x1em2", 1e-2, 0.0, 0.0)):
+    doms = [[(scale * x + dx, scale * y + dy) for x, y in r] for r in rings]
+    for nl in (4096, 600):
+        el = MeshVecEnv(doms, env_domain=(np.arange(nl) % 3).astype(np.int32)); el.reset()
+        kernel = el.step_kernel
+        rl = np.random.default_rng(77)
+        obs, rew, done = [], [], []
+        for t in range(96):
+            al = rl.uniform([-1, -1.5, 0], [1, 1.5, 1.5], size=(nl, 3))
+            pk = rl.random(nl) < 0.6
+            bl = np.stack([rl.uniform(-1, 1, nl), rl.uniform(0.2, 1.0, nl), rl.uniform(0.3, 1.2, nl)], axis=1)
+            al[pk] = bl[pk]
+            o, r, d, c = el.step(torch.from_numpy(al.astype(np.float32)).cuda())
+            obs.append(o.cpu().numpy()); rew.append(r.cpu().numpy()); done.append(d.cpu().numpy())
+        key = f"{tid}_{nl}"
+        arrays[key + "_obs"], arrays[key + "_reward"], arrays[key + "_done"] = np.stack(obs), np.stack(rew), np.stack(done)
+        res[key] = dict(kernel=kernel, valid=el.counters()["valid"])
+        el.close()
+np.savez(sys.argv[2], **arrays)
+print(json.dumps(res))
+"""
+
+
+def _run_xf(lib, out):
+    env = dict(os.environ)
+    if lib:
+        env["MESHENV_LIB"] = lib
+    p = subprocess.run([sys.executable, "-c", CHILD_XF, ROOT, out], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return json.loads(p.stdout.strip().splitlines()[-1]), dict(np.load(out))
+
+
+def test_no_filters_build_agrees_bit_for_bit_on_transformed_long_rings(tmp_path):
+    """The long-ring pre-filters (observation-scan x-slab, point_inside) on d1 / d2 / d3 scaled x1e4 and x1e-2 and shifted
+    by 1e8 in x and in y: the default library's obs / reward / done byte arrays over 96 steps equal those of the
+    -DMESHENV_NO_FILTERS build, on the ragged CU-group kernel (4096 envs) and on k_step (600 envs)."""
+    base, a = _run_xf(None, str(tmp_path / "base.npz"))
+    res, b = _run_xf(_build("nofilters", ["-DMESHENV_NO_FILTERS"]), str(tmp_path / "nofilters.npz"))
+    assert sorted(a) == sorted(b)
+    for k in sorted(a):
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, k
+        assert a[k].tobytes() == b[k].tobytes(), (k, int((a[k] != b[k]).sum()))
+    assert res == base, (res, base)
+    for key, r in base.items():
+        assert r["kernel"] == ("meshenv::k_step_group<16, true, true, false>" if key.endswith("_4096")
+                               else "meshenv::k_step<false, true, false, false, false>"), (key, r)
+        frac = {"x1e4": 0.001, "x1em2": 0.02}.get(key.split("_")[0], 0.05)   # few at x1e4: past the reference's ray end
+        assert r["valid"] >= frac * int(key.rsplit("_", 1)[1]) * 96, (key, r)
+    print("transformed long rings, default == -DMESHENV_NO_FILTERS bit for bit:", base)

@@ -6,12 +6,17 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_DIR, golden_names
-from oracle.ref_lib import RefEnv
+from oracle.ref_lib import DEFAULT_PARAMS, PARAM_NAMES, RefEnv
 
 
-def replay(tr, check_candidates=True):
+def trace_params(tr):
+    """The MeshEnvParams geometry constants a fixture was recorded with (xf_*_radius*), or None for the defaults."""
+    return dict(zip(PARAM_NAMES, (float(v) for v in tr["params"]))) if "params" in tr else None
+
+
+def replay(tr, check_candidates=True, params="trace"):
     c = tr["consts"]
-    env = RefEnv(tr["domain_xy"], c[0], c[2], c[3])
+    env = RefEnv(tr["domain_xy"], c[0], c[2], c[3], params=trace_params(tr) if params == "trace" else params)
     obs, none = env.reset()
     assert not none
     np.testing.assert_array_equal(obs, tr["reset_obs"])
@@ -53,6 +58,47 @@ def replay(tr, check_candidates=True):
 def test_oracle_matches_reference_trace(name):
     tr = dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
     replay(tr)
+
+
+@pytest.mark.parametrize("name", [n for n in golden_names() if "params" not in np.load(os.path.join(GOLDEN_DIR, n + ".npz"))])
+def test_explicit_default_params_replay_bit_exactly(name):
+    """The parametrised oracle with the reference's literals passed explicitly is the unparametrised one, bit for bit."""
+    tr = dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
+    replay(tr, params=dict(DEFAULT_PARAMS))
+
+
+def test_nondefault_params_change_the_oracle():
+    """The constants reach the oracle: each non-default value changes some output of a boundary0 stream."""
+    from oracle.ref_harness import BOUNDARY0, biased_actions
+    acts = biased_actions(1, 200)
+
+    def run(params):
+        env = RefEnv.from_points(BOUNDARY0, params=params)
+        env.reset()
+        out = []
+        for a in acts:
+            o, r, d, c, none = env.step(a)
+            out.append((o.tobytes(), r, d, c, none, env.ref_id()))
+            if d:
+                env.reset()
+        return out
+
+    base = run(None)
+    assert run(dict(DEFAULT_PARAMS)) == base
+    for p in (dict(radius=3.0), dict(radius=5.0), dict(key_lambda=0.5), dict(max_ref_angle=0.7 * np.pi),
+              dict(min_degree=0.05 * np.pi, max_degree=0.95 * np.pi), dict(same_point_eps=0.3), dict(ray_length=5.0)):
+        assert run(p) != base, p
+
+
+def test_transformed_fixtures_have_extractions():
+    """The scaled / shifted / radius fixtures (oracle/gen_golden.py XF_TRACES) are not vacuous.  Where the domain reaches
+    past the reference's ray end (x = 10000) the reference rejects most candidate points as outside: fewer there."""
+    names = [n for n in golden_names() if n.startswith("xf_")]
+    assert len(names) >= 10, names
+    low = {"xf_boundary0_x1e3_g2": 2, "xf_test1_x1e4_s8": 5}
+    for n in names:
+        tr = np.load(os.path.join(GOLDEN_DIR, n + ".npz"))
+        assert int(tr["valid"].sum()) >= low.get(n, 15), (n, int(tr["valid"].sum()))
 
 
 def test_golden_covers_edge_cases():
