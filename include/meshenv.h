@@ -558,6 +558,47 @@ int meshenv_gae(MeshEnv *h, int T, const double *reward_dev, const float *value_
                 float *advantage_dev, float *return_dev, float *buffer_reward_dev);
 
 /*
+ * The replay buffer of the off-policy algorithms (SAC, TD3) on the device (csrc/meshenv_replay.h).  Storage is one
+ * caller-owned, 16-byte aligned float32 DEVICE array store_dev [rows][n_envs][R], R = meshenv_replay_record_floats(), one
+ * packed record per transition: observation 0..17 | next observation 18..35 | action 36..38 | reward 39 | done 40 |
+ * timeout 41 | zero padding.  pos / full are the caller's (SB3: ReplayBuffer.pos, .full); the calls are stateless, one
+ * launch each on the handle's stream, no host synchronisation.
+ */
+int meshenv_replay_record_floats(void);
+/*
+ * T vector steps into rows (pos + t) % rows: SB3 2.x's OffPolicyAlgorithm._store_transition + ReplayBuffer.add, T times:
+ *   observation      = obs0 at t = 0, obs_after[t - 1] beyond (what step t acted on)
+ *   next observation = terminal_obs[t] where done[t], else obs_after[t]
+ *   action           = actions[t], or 2.0f * ((a - low) / (high - low)) - 1.0f in float32 (SAC's policy.scale_action) when
+ *                      action_low_high_host, a HOST array low[3], high[3], is given
+ *   reward = (float)reward[t], done = done[t] != 0, timeout = handle_timeouts && done && !complete (TimeLimit.truncated)
+ * obs0_dev [n][18]; obs_after_dev, terminal_obs_dev [T][n][18]; actions_dev [T][n][3]; reward_dev [T][n] float64; done_dev,
+ * complete_dev [T][n] uint8 -- as meshenv_step_policy_multi (obs0 = obs slice 0, obs_after = slices 1..T) and
+ * meshenv_step_actor_multi (obs_after = obs, obs0 = the observation before the call) leave them.  With T > rows only the
+ * last rows steps are written, which is what T sequential adds leave.  The caller advances pos by T modulo rows.
+ * MESHENV_E_ARG for T < 1, rows < 1, pos outside [0, rows), a NULL pointer other than action_low_high_host, a misaligned
+ * store, or an input that overlaps the store.
+ */
+int meshenv_replay_add(MeshEnv *h, int T, const float *obs0_dev, const float *obs_after_dev, const float *terminal_obs_dev,
+                       const float *actions_dev, const double *reward_dev, const uint8_t *done_dev, const uint8_t *complete_dev,
+                       const float *action_low_high_host, int handle_timeouts, float *store_dev, int rows, int pos);
+/*
+ * batch transitions out of the store: SB3 2.x's ReplayBuffer.sample + _get_samples (optimize_memory_usage=False, no
+ * VecNormalize), the ReplayBufferSamples fields as contiguous float32 arrays obs_out [batch][18], actions_out [batch][3],
+ * next_obs_out [batch][18], dones_out [batch][1] = done * (1 - timeout), rewards_out [batch][1].  With rows_in_dev /
+ * envs_in_dev (int32 [batch], both or neither) it is _get_samples on those indices; one outside [0, rows) x [0, n_envs) is
+ * not read: its outputs are NaN and its rows_out -1.  Without them sample i draws row in [0, size) and env in [0, n_envs) from
+ * Philox4x32-10 keyed by seed at counter words (i, counter, tag 1) by multiply-high (csrc/meshenv_replay.h; SB3 draws
+ * from numpy's global stream instead).  size = ReplayBuffer.size().  rows_out_dev / envs_out_dev (nullable) receive the
+ * indices used.  MESHENV_E_ARG for batch < 1, rows < 1, size outside [1, rows], a NULL store or output, only one of
+ * rows_in / envs_in, a misaligned store, or outputs that overlap the store, the given indices or each other.
+ */
+int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size, int batch, uint64_t seed, uint64_t counter,
+                          const int32_t *rows_in_dev, const int32_t *envs_in_dev, float *obs_out_dev, float *actions_out_dev,
+                          float *next_obs_out_dev, float *dones_out_dev, float *rewards_out_dev, int32_t *rows_out_dev,
+                          int32_t *envs_out_dev);
+
+/*
  * Policy evaluation on the device (csrc/meshenv_eval.h): SB3 2.x's evaluate_policy loop (non-Monitor branch) -- the loop
  * the reference's evaluation callers run with a deterministic model.predict:
  *   rl/baselines/CustomizeCallback.py:27-141   every 1000 training steps, to pick best_model

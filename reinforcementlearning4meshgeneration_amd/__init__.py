@@ -6,7 +6,8 @@ ZhuoQiuMcgill/ReinforcementLearning4MeshGeneration as hand-written HIP kernels b
 from .domains import boundary, domain_constants, generate_polygon, random_domain, read_polygon  # noqa: F401
 
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
-           "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy"]
+           "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
+           "DeviceReplayBuffer", "ReplayBufferSamples"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -31,4 +32,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("EvalResult", "evaluate_policy"):
         from . import evaluation
         return getattr(evaluation, name)
+    if name in ("DeviceReplayBuffer", "ReplayBufferSamples"):
+        from . import replay
+        return getattr(replay, name)
     raise AttributeError(name)

@@ -59,6 +59,7 @@ EXPORTS = [
     "meshenv_policy_create", "meshenv_policy_destroy", "meshenv_policy_set_stream", "meshenv_policy_load",
     "meshenv_policy_forward", "meshenv_step_policy_multi", "meshenv_policy_last_error", "meshenv_gae",
     "meshenv_eval_begin", "meshenv_eval_tally", "meshenv_evaluate",
+    "meshenv_replay_record_floats", "meshenv_replay_add", "meshenv_replay_sample",
 ]
 
 
@@ -178,6 +179,12 @@ def load():
     L.meshenv_eval_tally.restype = C.c_int
     L.meshenv_evaluate.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, evp, i32p, i32p]
     L.meshenv_evaluate.restype = C.c_int
+    L.meshenv_replay_record_floats.argtypes = []
+    L.meshenv_replay_record_floats.restype = C.c_int
+    L.meshenv_replay_add.argtypes = [vp, C.c_int] + [vp] * 7 + [C.POINTER(C.c_float), C.c_int, vp, C.c_int, C.c_int]
+    L.meshenv_replay_add.restype = C.c_int
+    L.meshenv_replay_sample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 9
+    L.meshenv_replay_sample.restype = C.c_int
     for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
                  "meshenv_step_policy_multi"):
         getattr(L, name).restype = C.c_int

@@ -26,6 +26,7 @@
 #include "meshenv_policy.h"
 #include "meshenv_gae.h"
 #include "meshenv_eval.h"
+#include "meshenv_replay.h"
 
 using namespace meshenv;
 
@@ -2182,6 +2183,93 @@ int meshenv_gae(MeshEnv *h, int T, const double *reward_dev, const float *value_
     const bool long_t = T > kGaeShortT;   // the two workgroup shapes of meshenv_gae.h
     hipLaunchKernelGGL(long_t ? k_gae<512> : k_gae<256>, dim3((unsigned)((n + kGaeEnvs - 1) / kGaeEnvs)), dim3(long_t ? 512 : 256),
                        0, h->stream, A);
+    HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+int meshenv_replay_record_floats(void) { return kReplayR; }
+
+int meshenv_replay_add(MeshEnv *h, int T, const float *obs0_dev, const float *obs_after_dev, const float *terminal_obs_dev,
+                       const float *actions_dev, const double *reward_dev, const uint8_t *done_dev, const uint8_t *complete_dev,
+                       const float *action_low_high_host, int handle_timeouts, float *store_dev, int rows, int pos)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (T < 1) return fail_arg(h, "meshenv_replay_add: T >= 1 is required");
+    if (rows < 1) return fail_arg(h, "meshenv_replay_add: rows >= 1 is required");
+    if (pos < 0 || pos >= rows) return fail_arg(h, "meshenv_replay_add: pos must be in [0, rows)");
+    if (!obs0_dev || !obs_after_dev || !terminal_obs_dev || !actions_dev || !reward_dev || !done_dev || !complete_dev || !store_dev)
+        return fail_arg(h, "meshenv_replay_add: obs0, obs_after, terminal_obs, actions, reward, done, complete and store are "
+                           "required");
+    if ((uintptr_t)store_dev % 16 != 0) return fail_arg(h, "meshenv_replay_add: the store must be 16-byte aligned");
+    const size_t n = (size_t)h->n_envs, tn = (size_t)T * n;
+    struct Range { const void *p; size_t bytes; };
+    const Range store{store_dev, (size_t)rows * n * kReplayR * sizeof(float)};
+    const Range in[] = {{obs0_dev, n * kObsDim * 4}, {obs_after_dev, tn * kObsDim * 4}, {terminal_obs_dev, tn * kObsDim * 4},
+                        {actions_dev, tn * 3 * 4}, {reward_dev, tn * 8}, {done_dev, tn}, {complete_dev, tn}};
+    for (const Range &r : in) {
+        const uintptr_t a = (uintptr_t)store.p, b = (uintptr_t)r.p;
+        if (a < b + r.bytes && b < a + store.bytes) return fail_arg(h, "meshenv_replay_add: an input overlaps the store");
+    }
+    MESHENV_ON_DEVICE(h);
+    ReplayAddArgs A{};
+    A.n = h->n_envs; A.rows = rows; A.T = T;
+    A.t0 = T > rows ? T - rows : 0;     // T sequential adds leave the last `rows` steps
+    A.row0 = (int)(((long long)pos + A.t0) % rows);
+    A.handle_timeouts = handle_timeouts ? 1 : 0;
+    if (action_low_high_host) {
+        const float *lh = action_low_high_host;
+        A.scale = 1;
+        A.lo0 = lh[0]; A.lo1 = lh[1]; A.lo2 = lh[2]; A.hi0 = lh[3]; A.hi1 = lh[4]; A.hi2 = lh[5];
+    }
+    A.obs0 = obs0_dev; A.obs_after = obs_after_dev; A.tobs = terminal_obs_dev; A.actions = actions_dev;
+    A.reward = reward_dev; A.done = done_dev; A.complete = complete_dev; A.store = store_dev;
+    const int steps = T - A.t0;
+    const unsigned gy = (unsigned)((steps + 3) / 4 < 65535 ? (steps + 3) / 4 : 65535);      // a workgroup walks about four steps
+    hipLaunchKernelGGL(k_replay_add, dim3((unsigned)((n + kReplayGroups - 1) / kReplayGroups), gy), dim3(kReplayThreads), 0,
+                       h->stream, A);
+    HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size, int batch, uint64_t seed, uint64_t counter,
+                          const int32_t *rows_in_dev, const int32_t *envs_in_dev, float *obs_out_dev, float *actions_out_dev,
+                          float *next_obs_out_dev, float *dones_out_dev, float *rewards_out_dev, int32_t *rows_out_dev,
+                          int32_t *envs_out_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (batch < 1) return fail_arg(h, "meshenv_replay_sample: batch >= 1 is required");
+    if (rows < 1) return fail_arg(h, "meshenv_replay_sample: rows >= 1 is required");
+    if (size < 1 || size > rows) return fail_arg(h, "meshenv_replay_sample: size must be in [1, rows] (an empty buffer has no samples)");
+    if (!store_dev || !obs_out_dev || !actions_out_dev || !next_obs_out_dev || !dones_out_dev || !rewards_out_dev)
+        return fail_arg(h, "meshenv_replay_sample: store and the five outputs are required");
+    if ((rows_in_dev != nullptr) != (envs_in_dev != nullptr))
+        return fail_arg(h, "meshenv_replay_sample: rows_in and envs_in are given together or not at all");
+    if ((uintptr_t)store_dev % 16 != 0) return fail_arg(h, "meshenv_replay_sample: the store must be 16-byte aligned");
+    const size_t n = (size_t)h->n_envs, B = (size_t)batch;
+    struct Range { const void *p; size_t bytes; };
+    const Range in[] = {{store_dev, (size_t)rows * n * kReplayR * sizeof(float)}, {rows_in_dev, B * 4}, {envs_in_dev, B * 4}};
+    const Range out[] = {{obs_out_dev, B * kObsDim * 4}, {actions_out_dev, B * 3 * 4}, {next_obs_out_dev, B * kObsDim * 4},
+                         {dones_out_dev, B * 4}, {rewards_out_dev, B * 4}, {rows_out_dev, B * 4}, {envs_out_dev, B * 4}};
+    auto overlap = [](const Range &x, const Range &y) {
+        const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+        return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+    };
+    for (int i = 0; i < 7; i++) {
+        if (overlap(out[i], in[0])) return fail_arg(h, "meshenv_replay_sample: an output overlaps the store");
+        if (overlap(out[i], in[1]) || overlap(out[i], in[2]))
+            return fail_arg(h, "meshenv_replay_sample: an output overlaps rows_in / envs_in");
+        for (int j = 0; j < i; j++)
+            if (overlap(out[i], out[j])) return fail_arg(h, "meshenv_replay_sample: two outputs overlap");
+    }
+    MESHENV_ON_DEVICE(h);
+    ReplaySampleArgs A{};
+    A.n = h->n_envs; A.rows = rows; A.size = size; A.B = batch;
+    A.seed = seed; A.counter = counter;
+    A.store = store_dev; A.rows_in = rows_in_dev; A.envs_in = envs_in_dev;
+    A.obs = obs_out_dev; A.act = actions_out_dev; A.next = next_obs_out_dev; A.dones = dones_out_dev; A.rew = rewards_out_dev;
+    A.rows_out = rows_out_dev; A.envs_out = envs_out_dev;
+    hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)((B + kReplaySamples - 1) / kReplaySamples)), dim3(kReplayThreads), 0,
+                       h->stream, A);
     HIP_TRY(h, hipGetLastError());
     return MESHENV_OK;
 }
