@@ -599,6 +599,56 @@ int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size
                           int32_t *envs_out_dev);
 
 /*
+ * The TD target of SAC / TD3 on the device (csrc/meshenv_target.h): the `with th.no_grad():` block of SB3 2.x's SAC.train /
+ * TD3.train that follows replay_buffer.sample, one launch, from the tensors meshenv_replay_sample returns.
+ *   kind 0, SAC (actor ReLU [128, 128, 128] with mu / log_std heads, twin critics ReLU [128, 128, 128], 21 -> 1):
+ *     next_actions, next_log_prob = actor.action_log_prob(next_observations)        (log_std clamped to [-20, 2],
+ *         a = tanh(mean + exp(log_std) * eps), SquashedDiagGaussianDistribution.log_prob with epsilon 1e-6)
+ *     next_q_values = min(cat(critic_target(next_observations, next_actions), dim=1), dim=1)
+ *     next_q_values = next_q_values - ent_coef * next_log_prob.reshape(-1, 1)
+ *   kind 1, TD3 (actor_target ReLU [256, 256] + tanh, twin critics ReLU [256, 256]):
+ *     noise = actions.clone().normal_(0, target_policy_noise).clamp(-target_noise_clip, target_noise_clip)
+ *     next_actions = (actor_target(next_observations) + noise).clamp(-1, 1)
+ *     next_q_values = min(cat(critic_target(next_observations, next_actions), dim=1), dim=1)
+ *   both: target_q_values = rewards + (1 - dones) * gamma * next_q_values          (float32, in that order)
+ * Any other kind fails with MESHENV_E_ARG and a message naming the supported ones.  gamma in [0, 1]; ent_coef is SB3's fixed
+ * coefficient, used when meshenv_target_bind gets no log_ent_coef; policy_noise, noise_clip >= 0 (TD3).
+ */
+typedef struct MeshTarget MeshTarget;
+int meshenv_target_create(int device, void *stream, int kind, float gamma, float ent_coef, float policy_noise, float noise_clip,
+                          MeshTarget **out);
+void meshenv_target_destroy(MeshTarget *t);
+int meshenv_target_set_stream(MeshTarget *t, void *stream);
+const char *meshenv_target_last_error(const MeshTarget *t);   /* message of the handle's last failure */
+/*
+ * Records the DEVICE pointers of the live float32, contiguous torch.nn.Linear parameters ([out][in] weight, [out] bias; the
+ * caller checks dtype, layout and device).  Nothing is read yet.
+ *   actor_dev  kind 0: w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w log_std_b (n_actor 10); kind 1: w1 b1 w2 b2 mu_w mu_b (6)
+ *   q1_dev, q2_dev  critic_target.q_networks[0], [1]: kind 0: w1 b1 w2 b2 w3 b3 w4 b4 (n_critic 8); kind 1: 6; w1 is [H][21]
+ *   log_ent_coef_dev  kind 0: SAC's learned log_ent_coef [1] (ent_coef = exp of it: th.exp(self.log_ent_coef.detach())) or NULL
+ * SB3's optimisers and polyak_update write in place, so the pointers stay valid; bind again after anything that reallocates.
+ * MESHENV_E_ARG for a wrong count, a NULL entry, or log_ent_coef_dev with kind 1.
+ */
+int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
+                        const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev);
+/* Copies every bound tensor (log_ent_coef included) into the kernel's layout: ONE launch on the handle's stream, no host
+ * copy, no synchronisation.  A forward sees the values of the last refresh before it on the stream -- call it after
+ * optimizer.step() / polyak_update.  MESHENV_E_STATE before meshenv_target_bind. */
+int meshenv_target_refresh(MeshTarget *t);
+/*
+ * One launch.  next_obs_dev [n][18], rewards_dev, dones_dev [n] (= ReplayBufferSamples' [n][1]; dones is dones * (1 -
+ * timeouts) already).  eps: noise_dev [n][3], or sample != 0 for Philox4x32-10 keyed by seed at counter words (sample
+ * index, counter lo, counter hi, 2) -- tag 2 is this call's own (rollout noise 0, replay draw 1) -- or neither for eps = 0.
+ * Outputs, each nullable and written only when given: target_dev [n] (needs rewards and dones), next_actions_dev [n][3] (in
+ * [-1, 1], what the critics see), next_log_prob_dev [n] (kind 0), q1_dev, q2_dev [n], eps_out_dev [n][3] (needs noise).
+ * MESHENV_E_STATE before the first refresh; MESHENV_E_ARG for n < 1, a missing input, noise and sample together,
+ * next_log_prob_dev with kind 1, eps_out_dev without noise, or no output.
+ */
+int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, const float *rewards_dev, const float *dones_dev,
+                           const float *noise_dev, int sample, uint64_t seed, uint64_t counter, float *target_dev,
+                           float *next_actions_dev, float *next_log_prob_dev, float *q1_dev, float *q2_dev, float *eps_out_dev);
+
+/*
  * Policy evaluation on the device (csrc/meshenv_eval.h): SB3 2.x's evaluate_policy loop (non-Monitor branch) -- the loop
  * the reference's evaluation callers run with a deterministic model.predict:
  *   rl/baselines/CustomizeCallback.py:27-141   every 1000 training steps, to pick best_model

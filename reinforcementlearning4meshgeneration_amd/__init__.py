@@ -7,7 +7,7 @@ from .domains import boundary, domain_constants, generate_polygon, random_domain
 
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
-           "DeviceReplayBuffer", "ReplayBufferSamples"]
+           "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -35,4 +35,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("DeviceReplayBuffer", "ReplayBufferSamples"):
         from . import replay
         return getattr(replay, name)
+    if name in ("FusedTDTarget", "TDTargetSpec"):
+        from . import td_target
+        return getattr(td_target, name)
     raise AttributeError(name)

@@ -60,6 +60,8 @@ EXPORTS = [
     "meshenv_policy_forward", "meshenv_step_policy_multi", "meshenv_policy_last_error", "meshenv_gae",
     "meshenv_eval_begin", "meshenv_eval_tally", "meshenv_evaluate",
     "meshenv_replay_record_floats", "meshenv_replay_add", "meshenv_replay_sample",
+    "meshenv_target_create", "meshenv_target_destroy", "meshenv_target_set_stream", "meshenv_target_last_error",
+    "meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward",
 ]
 
 
@@ -185,6 +187,18 @@ def load():
     L.meshenv_replay_add.restype = C.c_int
     L.meshenv_replay_sample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 9
     L.meshenv_replay_sample.restype = C.c_int
+    L.meshenv_target_create.argtypes = [C.c_int, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(vp)]
+    L.meshenv_target_destroy.argtypes = [vp]
+    L.meshenv_target_destroy.restype = None
+    L.meshenv_target_set_stream.argtypes = [vp, vp]
+    L.meshenv_target_last_error.argtypes = [vp]
+    L.meshenv_target_last_error.restype = C.c_char_p
+    L.meshenv_target_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, vp]
+    L.meshenv_target_refresh.argtypes = [vp]
+    L.meshenv_target_forward.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 6
+    for name in ("meshenv_target_create", "meshenv_target_set_stream", "meshenv_target_bind", "meshenv_target_refresh",
+                 "meshenv_target_forward"):
+        getattr(L, name).restype = C.c_int
     for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
                  "meshenv_step_policy_multi"):
         getattr(L, name).restype = C.c_int

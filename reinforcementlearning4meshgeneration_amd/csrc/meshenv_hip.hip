@@ -27,6 +27,7 @@
 #include "meshenv_gae.h"
 #include "meshenv_eval.h"
 #include "meshenv_replay.h"
+#include "meshenv_target.h"
 
 using namespace meshenv;
 
@@ -2445,6 +2446,193 @@ int meshenv_evaluate(MeshEnv *h, MeshPolicy *policy, MeshActor *actor, int sampl
     }
     *steps_out = t;
     *short_out = short_envs;
+    return MESHENV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC / TD3 TD targets
+struct MeshTarget {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int kind = -1;
+    float gamma = 0.f, ent_coef = 0.f, policy_noise = 0.f, noise_clip = 0.f;
+    float *buf = nullptr;      // every packed weight, one allocation, zeroed once
+    TargetWeights W{};
+    PackTable table{};
+    int n_copies = 0;
+    bool bound = false, packed = false;
+    std::string err;
+};
+
+namespace {
+
+int target_fail(MeshTarget *t, int rc, const std::string &msg)
+{
+    t->err = msg;
+    return rc;
+}
+
+const char *kTargetKinds = "supported kinds: 0 (SAC: ReLU [128, 128, 128] actor with mu / log_std heads and twin ReLU [128, 128, 128] "
+                           "critics) or 1 (TD3: ReLU [256, 256] tanh actor and twin ReLU [256, 256] critics); 18 observations, 3 actions";
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_target_create(int device, void *stream, int kind, float gamma, float ent_coef, float policy_noise, float noise_clip,
+                          MeshTarget **out)
+{
+    if (!out) return MESHENV_E_ARG;
+    *out = nullptr;
+    if (kind != kTargetSAC && kind != kTargetTD3) {
+        g_create_error = std::string("meshenv_target_create: unsupported kind; ") + kTargetKinds;
+        return MESHENV_E_ARG;
+    }
+    if (!(gamma >= 0.0f && gamma <= 1.0f) || !std::isfinite(ent_coef) || !(policy_noise >= 0.0f) || !(noise_clip >= 0.0f) ||
+        !std::isfinite(policy_noise) || !std::isfinite(noise_clip)) {
+        g_create_error = "meshenv_target_create: gamma must lie in [0, 1], ent_coef be finite, policy_noise and noise_clip be finite and >= 0";
+        return MESHENV_E_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        g_create_error = "meshenv_target_create: no such HIP device";
+        return MESHENV_E_HIP;
+    }
+    MeshTarget *t = new MeshTarget();
+    t->device = device;
+    t->stream = (hipStream_t)stream;
+    t->kind = kind;
+    t->gamma = gamma; t->ent_coef = ent_coef; t->policy_noise = policy_noise; t->noise_clip = noise_clip;
+    *out = t;
+    return MESHENV_OK;
+}
+
+void meshenv_target_destroy(MeshTarget *t)
+{
+    if (!t) return;
+    DeviceGuard guard(t->device);
+    (void)hipStreamSynchronize(t->stream);
+    if (t->buf) (void)hipFree(t->buf);
+    delete t;
+}
+
+const char *meshenv_target_last_error(const MeshTarget *t) { return t ? t->err.c_str() : g_create_error.c_str(); }
+
+int meshenv_target_set_stream(MeshTarget *t, void *stream)
+{
+    if (!t) return MESHENV_E_ARG;
+    t->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
+                        const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev)
+{
+    if (!t) return MESHENV_E_ARG;
+    const bool sac = t->kind == kTargetSAC;
+    const int H = sac ? 128 : 256, NL = sac ? 3 : 2, G = H / 16;
+    const int want_actor = 2 * NL + (sac ? 4 : 2), want_critic = 2 * NL + 2;
+    if (!actor_dev || !q1_dev || !q2_dev || n_actor != want_actor || n_critic != want_critic)
+        return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: kind " + std::to_string(t->kind) + " takes " +
+                           std::to_string(want_actor) + " actor and " + std::to_string(want_critic) + " critic tensors; " + kTargetKinds);
+    for (int i = 0; i < n_actor; i++)
+        if (!actor_dev[i]) return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: null actor tensor");
+    for (int i = 0; i < n_critic; i++)
+        if (!q1_dev[i] || !q2_dev[i]) return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: null critic tensor");
+    if (!sac && log_ent_coef_dev) return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: TD3 has no entropy coefficient (pass NULL)");
+    DeviceGuard guard(t->device);
+    if (guard.err != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_bind: hipSetDevice failed");
+    // layout of the buffer: per tower w1p b1 w2p b2 [w3p b3] whp bh, then log_ent_coef
+    const size_t tower_floats = (size_t)G * 2 * 256 + H + (size_t)(NL - 1) * ((size_t)G * G * 256 + H) + (size_t)G * 256 + 16;
+    const size_t total = 3 * tower_floats + 4;
+    if (!t->buf) {
+        if (hipMalloc((void **)&t->buf, total * sizeof(float)) != hipSuccess ||
+            hipMemsetAsync(t->buf, 0, total * sizeof(float), t->stream) != hipSuccess ||
+            hipStreamSynchronize(t->stream) != hipSuccess)   // the stream may change before the first refresh
+            return target_fail(t, MESHENV_E_HIP, "meshenv_target_bind: allocation failed");
+    }
+    t->n_copies = 0;
+    auto add = [&](const float *src, float *dst, int out, int in, int groups, int tiles, int n_off, int kind) {
+        PackCopy &c = t->table.c[t->n_copies++];
+        c.src = src; c.dst = dst; c.out = out; c.in = in; c.groups = groups; c.tiles = tiles; c.n_off = n_off; c.kind = kind;
+    };
+    auto tower = [&](TargetTower &T, float *base, const float *const *p, int in1, bool actor) {
+        float *at = base;
+        int i = 0;
+        T.w1p = at; add(p[i++], at, H, in1, 2, G, 0, kPackMatrix); at += (size_t)G * 2 * 256;
+        T.b1 = at; add(p[i++], at, H, 0, 0, 0, 0, kPackVector); at += H;
+        T.w2p = at; add(p[i++], at, H, H, G, G, 0, kPackMatrix); at += (size_t)G * G * 256;
+        T.b2 = at; add(p[i++], at, H, 0, 0, 0, 0, kPackVector); at += H;
+        T.w3p = T.b3 = nullptr;
+        if (NL == 3) {
+            T.w3p = at; add(p[i++], at, H, H, G, G, 0, kPackMatrix); at += (size_t)G * G * 256;
+            T.b3 = at; add(p[i++], at, H, 0, 0, 0, 0, kPackVector); at += H;
+        }
+        float *wh = at, *bh = at + (size_t)G * 256;
+        T.whp = wh; T.bh = bh;
+        const int n_out = actor ? 3 : 1;
+        add(p[i], wh, n_out, H, G, 1, 0, kPackMatrix); add(p[i + 1], bh, n_out, 0, 0, 0, 0, kPackVector);
+        if (actor && sac) {   // log_std head: columns 3..5 of the same tile
+            add(p[i + 2], wh, 3, H, G, 1, 3, kPackMatrix); add(p[i + 3], bh, 3, 0, 0, 0, 3, kPackVector);
+        }
+    };
+    tower(t->W.actor, t->buf, actor_dev, kObsDim, true);
+    tower(t->W.q1, t->buf + tower_floats, q1_dev, kTgtIn, false);
+    tower(t->W.q2, t->buf + 2 * tower_floats, q2_dev, kTgtIn, false);
+    t->W.log_ent_coef = nullptr;
+    if (log_ent_coef_dev) {
+        float *dst = t->buf + 3 * tower_floats;
+        add(log_ent_coef_dev, dst, 1, 0, 0, 0, 0, kPackVector);
+        t->W.log_ent_coef = dst;
+    }
+    static_assert(10 + 2 * 8 + 1 <= kTgtMaxCopies, "the copy table holds SAC's 27 sources");
+    t->bound = true;
+    t->packed = false;
+    return MESHENV_OK;
+}
+
+int meshenv_target_refresh(MeshTarget *t)
+{
+    if (!t) return MESHENV_E_ARG;
+    if (!t->bound) return target_fail(t, MESHENV_E_STATE, "meshenv_target_refresh: no tensors bound (meshenv_target_bind)");
+    DeviceGuard guard(t->device);
+    if (guard.err != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_refresh: hipSetDevice failed");
+    // the largest copy is an H x H matrix: H * H / 256 blocks cover it in one pass
+    const int H = t->kind == kTargetSAC ? 128 : 256;
+    hipLaunchKernelGGL(k_target_pack, dim3(H * H / 256, t->n_copies), dim3(256), 0, t->stream, t->table);
+    if (hipGetLastError() != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_refresh: launch failed");
+    t->packed = true;
+    return MESHENV_OK;
+}
+
+int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, const float *rewards_dev, const float *dones_dev,
+                           const float *noise_dev, int sample, uint64_t seed, uint64_t counter, float *target_dev,
+                           float *next_actions_dev, float *next_log_prob_dev, float *q1_dev, float *q2_dev, float *eps_out_dev)
+{
+    if (!t) return MESHENV_E_ARG;
+    if (!t->packed) return target_fail(t, MESHENV_E_STATE, "meshenv_target_forward: no weights packed (meshenv_target_bind, then meshenv_target_refresh)");
+    if (n <= 0 || !next_obs_dev) return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: n > 0 and next_obs_dev are required");
+    if (noise_dev && sample) return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: explicit noise and sample are exclusive");
+    if (target_dev && (!rewards_dev || !dones_dev))
+        return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: target_dev needs rewards_dev and dones_dev");
+    if (t->kind == kTargetTD3 && next_log_prob_dev)
+        return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: TD3 has no next_log_prob (pass NULL)");
+    if (eps_out_dev && !sample && !noise_dev) return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: eps_out_dev without noise");
+    if (!target_dev && !next_actions_dev && !next_log_prob_dev && !q1_dev && !q2_dev && !eps_out_dev)
+        return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: no output requested");
+    TargetArgs A{};
+    A.n = n; A.next_obs = next_obs_dev; A.rewards = rewards_dev; A.dones = dones_dev; A.noise = noise_dev;
+    A.sample = sample ? 1 : 0; A.seed = seed; A.counter = counter;
+    A.gamma = t->gamma; A.ent_coef = t->ent_coef; A.policy_noise = t->policy_noise; A.noise_clip = t->noise_clip;
+    A.target = target_dev; A.next_actions = next_actions_dev; A.next_log_prob = next_log_prob_dev; A.q1 = q1_dev; A.q2 = q2_dev;
+    A.eps_out = eps_out_dev;
+    DeviceGuard guard(t->device);
+    if (guard.err != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_forward: hipSetDevice failed");
+    const dim3 grid((n + kTgtRows - 1) / kTgtRows);
+    if (t->kind == kTargetSAC) hipLaunchKernelGGL(k_td_target<kTargetSAC>, grid, dim3(512), 0, t->stream, t->W, A);
+    else hipLaunchKernelGGL(k_td_target<kTargetTD3>, grid, dim3(1024), 0, t->stream, t->W, A);
+    if (hipGetLastError() != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_forward: launch failed");
     return MESHENV_OK;
 }
 
