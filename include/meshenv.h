@@ -649,6 +649,42 @@ int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, cons
                            float *next_actions_dev, float *next_log_prob_dev, float *q1_dev, float *q2_dev, float *eps_out_dev);
 
 /*
+ * The critic loss of SAC / TD3 and its gradients on the device (csrc/meshenv_critic_grad.h): the statements of SB3 2.x's
+ * SAC.train / TD3.train that follow the TD target,
+ *     current_q_values = self.critic(replay_data.observations, replay_data.actions)
+ *     critic_loss = 0.5 * sum(F.mse_loss(current_q, target_q_values) for current_q in current_q_values)
+ *     self.critic.optimizer.zero_grad(); critic_loss.backward()
+ * for the twin critics of meshenv_target_create's kinds (kind 0: ReLU [128, 128, 128]; kind 1: ReLU [256, 256]; input
+ * cat(obs, action) = 21, float32).  The optimiser step stays the caller's.  Any other kind fails with MESHENV_E_ARG.
+ */
+typedef struct MeshCriticGrad MeshCriticGrad;
+int meshenv_critic_grad_create(int device, void *stream, int kind, MeshCriticGrad **out);
+void meshenv_critic_grad_destroy(MeshCriticGrad *g);
+int meshenv_critic_grad_set_stream(MeshCriticGrad *g, void *stream);
+const char *meshenv_critic_grad_last_error(const MeshCriticGrad *g);   /* message of the handle's last failure */
+/*
+ * Records the DEVICE pointers of the LIVE critics' float32, contiguous torch.nn.Linear parameters (self.critic.q_networks,
+ * not critic_target; per critic w1 b1 w2 b2 [w3 b3] out_w out_b: n_critic 8 for kind 0, 6 for kind 1; [H][H] weights
+ * 16-byte aligned) and of the caller's flat gradient buffer grad_dev [n_grad]: per critic, in the same order and in
+ * torch's [out][in] / [out] layout, w1 [H][21], b1 [H], w_l [H][H], b_l [H], out_w [H], out_b [1], each critic padded to a
+ * multiple of 64 floats (n_grad = 2 * 36032 for kind 0, 2 * 71744 for kind 1).  The parameters are read at every backward
+ * as they are then (optimisers write in place); bind again after anything that reallocates.  Allocates the handle's
+ * workspace of 128 partial gradient sets (n_grad + 64 floats each) on the first call.
+ */
+int meshenv_critic_grad_bind(MeshCriticGrad *g, const float *const *q1_dev, const float *const *q2_dev, int n_critic,
+                             float *grad_dev, int64_t n_grad);
+/*
+ * Two launches on the handle's stream, no host copy, no synchronisation.  obs_dev [n][18], actions_dev [n][3], target_dev
+ * [n] (target_q_values: a constant, no gradient flows into it).  OVERWRITES grad_dev with the gradients of critic_loss and
+ * writes critic_loss to loss_dev [1].  Optional: q1_dev, q2_dev [n] (current_q_values), acts1_dev / acts2_dev (both or
+ * neither): per hidden layer a [n][H] buffer receiving that critic's post-ReLU activations (a > 0 is the mask the backward
+ * pass used).  Deterministic: the sum over the batch has a fixed order, the same inputs give the same bits.
+ * MESHENV_E_STATE before meshenv_critic_grad_bind; MESHENV_E_ARG for n < 1 or a missing input.
+ */
+int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev, const float *actions_dev, const float *target_dev,
+                                 float *loss_dev, float *q1_dev, float *q2_dev, float *const *acts1_dev, float *const *acts2_dev);
+
+/*
  * Policy evaluation on the device (csrc/meshenv_eval.h): SB3 2.x's evaluate_policy loop (non-Monitor branch) -- the loop
  * the reference's evaluation callers run with a deterministic model.predict:
  *   rl/baselines/CustomizeCallback.py:27-141   every 1000 training steps, to pick best_model

@@ -7,7 +7,7 @@ from .domains import boundary, domain_constants, generate_polygon, random_domain
 
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
-           "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec"]
+           "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -38,4 +38,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedTDTarget", "TDTargetSpec"):
         from . import td_target
         return getattr(td_target, name)
+    if name in ("FusedCriticGrad", "CriticGradSpec"):
+        from . import critic_grad
+        return getattr(critic_grad, name)
     raise AttributeError(name)

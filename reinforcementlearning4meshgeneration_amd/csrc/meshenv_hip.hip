@@ -28,6 +28,7 @@
 #include "meshenv_eval.h"
 #include "meshenv_replay.h"
 #include "meshenv_target.h"
+#include "meshenv_critic_grad.h"
 
 using namespace meshenv;
 
@@ -2633,6 +2634,159 @@ int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, cons
     if (t->kind == kTargetSAC) hipLaunchKernelGGL(k_td_target<kTargetSAC>, grid, dim3(512), 0, t->stream, t->W, A);
     else hipLaunchKernelGGL(k_td_target<kTargetTD3>, grid, dim3(1024), 0, t->stream, t->W, A);
     if (hipGetLastError() != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_forward: launch failed");
+    return MESHENV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC / TD3 critic loss gradients
+struct MeshCriticGrad {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int kind = -1;
+    CgCritic c[2]{};
+    float *grad = nullptr;      // the caller's flat gradient buffer (CgLayout::grads floats)
+    float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
+    bool bound = false;
+    std::string err;
+};
+
+namespace {
+
+int cg_fail(MeshCriticGrad *g, int rc, const std::string &msg)
+{
+    g->err = msg;
+    return rc;
+}
+
+const char *kCriticGradKinds = "supported kinds: 0 (SAC: twin ReLU [128, 128, 128] critics) or 1 (TD3: twin ReLU [256, 256] critics); "
+                               "input cat(obs, action) = 21, float32";
+
+template <int H, int NL>
+void cg_sizes(int *grads, int *set) { *grads = CgLayout<H, NL>::grads; *set = CgLayout<H, NL>::set; }
+
+void cg_layout(int kind, int *grads, int *set)
+{
+    if (kind == kTargetSAC) cg_sizes<128, 3>(grads, set);
+    else cg_sizes<256, 2>(grads, set);
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_critic_grad_create(int device, void *stream, int kind, MeshCriticGrad **out)
+{
+    if (!out) return MESHENV_E_ARG;
+    *out = nullptr;
+    if (kind != kTargetSAC && kind != kTargetTD3) {
+        g_create_error = std::string("meshenv_critic_grad_create: unsupported kind; ") + kCriticGradKinds;
+        return MESHENV_E_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        g_create_error = "meshenv_critic_grad_create: no such HIP device";
+        return MESHENV_E_HIP;
+    }
+    MeshCriticGrad *g = new MeshCriticGrad();
+    g->device = device;
+    g->stream = (hipStream_t)stream;
+    g->kind = kind;
+    *out = g;
+    return MESHENV_OK;
+}
+
+void meshenv_critic_grad_destroy(MeshCriticGrad *g)
+{
+    if (!g) return;
+    DeviceGuard guard(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    if (g->partial) (void)hipFree(g->partial);
+    delete g;
+}
+
+const char *meshenv_critic_grad_last_error(const MeshCriticGrad *g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+
+int meshenv_critic_grad_set_stream(MeshCriticGrad *g, void *stream)
+{
+    if (!g) return MESHENV_E_ARG;
+    g->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+int meshenv_critic_grad_bind(MeshCriticGrad *g, const float *const *q1_dev, const float *const *q2_dev, int n_critic,
+                             float *grad_dev, int64_t n_grad)
+{
+    if (!g) return MESHENV_E_ARG;
+    const int NL = g->kind == kTargetSAC ? 3 : 2, want = 2 * NL + 2;
+    int grads = 0, set = 0;
+    cg_layout(g->kind, &grads, &set);
+    if (!q1_dev || !q2_dev || n_critic != want)
+        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: kind " + std::to_string(g->kind) + " takes " + std::to_string(want) +
+                       " tensors per critic; " + kCriticGradKinds);
+    if (!grad_dev || n_grad != grads)
+        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: the gradient buffer of kind " + std::to_string(g->kind) + " has " +
+                       std::to_string(grads) + " floats, got " + std::to_string((long long)n_grad));
+    for (int i = 0; i < want; i++) {
+        if (!q1_dev[i] || !q2_dev[i]) return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: null critic tensor");
+        // the hidden layers' [H][H] weights are read 16 bytes at a time
+        if (i % 2 == 0 && i >= 2 && (((uintptr_t)q1_dev[i] | (uintptr_t)q2_dev[i]) & 15))
+            return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: hipSetDevice failed");
+    if (!g->partial) {
+        const size_t bytes = (size_t)kCgMaxGroups * set * sizeof(float);
+        if (hipMalloc((void **)&g->partial, bytes) != hipSuccess || hipMemsetAsync(g->partial, 0, bytes, g->stream) != hipSuccess ||
+            hipStreamSynchronize(g->stream) != hipSuccess)   // the stream may change before the first backward
+            return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: allocation failed");
+    }
+    for (int k = 0; k < 2; k++) {
+        const float *const *p = k == 0 ? q1_dev : q2_dev;
+        for (int l = 0; l <= NL; l++) {
+            g->c[k].w[l] = p[2 * l];
+            g->c[k].b[l] = p[2 * l + 1];
+        }
+    }
+    g->grad = grad_dev;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev, const float *actions_dev, const float *target_dev,
+                                 float *loss_dev, float *q1_dev, float *q2_dev, float *const *acts1_dev, float *const *acts2_dev)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!g->bound) return cg_fail(g, MESHENV_E_STATE, "meshenv_critic_grad_backward: no tensors bound (meshenv_critic_grad_bind)");
+    if (n <= 0 || !obs_dev || !actions_dev || !target_dev || !loss_dev)
+        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: n > 0, obs_dev, actions_dev, target_dev and loss_dev are required");
+    if ((acts1_dev == nullptr) != (acts2_dev == nullptr))
+        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: acts1_dev and acts2_dev go together");
+    const int NL = g->kind == kTargetSAC ? 3 : 2;
+    int grads = 0, set = 0;
+    cg_layout(g->kind, &grads, &set);
+    CgArgs A{};
+    const int tiles = (n + kCgRows - 1) / kCgRows;
+    A.n = n;
+    A.nwg = tiles <= 512 ? (tiles < 64 ? tiles : 64) : kCgMaxGroups;
+    A.obs = obs_dev; A.actions = actions_dev; A.target = target_dev;
+    A.c[0] = g->c[0]; A.c[1] = g->c[1];
+    A.partial = g->partial;
+    A.q[0] = q1_dev; A.q[1] = q2_dev;
+    for (int l = 0; l < NL; l++) {
+        A.acts[0][l] = acts1_dev ? acts1_dev[l] : nullptr;
+        A.acts[1][l] = acts2_dev ? acts2_dev[l] : nullptr;
+        if (acts1_dev && (!A.acts[0][l] || !A.acts[1][l]))
+            return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: null activation output");
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: hipSetDevice failed");
+    if (g->kind == kTargetSAC) hipLaunchKernelGGL(k_critic_grad<kTargetSAC>, dim3(A.nwg, 2), dim3(512), 0, g->stream, A);
+    else hipLaunchKernelGGL(k_critic_grad<kTargetTD3>, dim3(A.nwg, 2 * kCgSplitTD3), dim3(1024), 0, g->stream, A);
+    if (hipGetLastError() != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: launch failed");
+    hipLaunchKernelGGL(k_critic_grad_reduce, dim3((grads + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg, set,
+                       grads, n, g->grad, loss_dev);
+    if (hipGetLastError() != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: reduction launch failed");
     return MESHENV_OK;
 }
 
