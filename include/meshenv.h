@@ -800,6 +800,13 @@ int meshenv_step_actor_multi(MeshEnv *h, MeshActor *a, int T, float *actions_dev
  *        9 / 10 x / y of a front-smoother vertex construction (9 doubles: which = 0 middle_vertex, 1 side_vertex,
  *               2 indention_vertex (general/mesh.py:805-909), 3 Mesh.estimate_4th_vertex (factor, suggest_dist or < 0);
  *               vertex, p1, p2; angle; dist), NaN where it is undefined
+ *        11-16 libm building blocks: pow(x, 2), the quantised angle of (c, d), the atan2 tie-breaker, atan2, sin, cos
+ *        17 / 18 the x-slab and point_inside pre-filters against the unfiltered tests (7 doubles; any other
+ *               in_per_item is MESHENV_E_ARG)
+ *        19 one entry of the element quality record for an arbitrary quad (9 doubles: the four vertices (x, y) in
+ *               Mesh.vertices order, then the record index 0-7 as in meshenv_element_quality; any other in_per_item
+ *               is MESHENV_E_ARG): what meshenv_quad_quality does not expose -- the corner angles, scaled Jacobian,
+ *               taper and area of degenerate, concave, inverted and non-finite quads (tests/test_gpu_quality_edges.py)
  */
 int meshenv_selftest(int device, int what, int n, int in_per_item, const double *in_host, double *out_host);
 

@@ -493,6 +493,50 @@ XF_TRACES = [
 ]
 
 
+def quality_edge_fixture():
+    """The reference's own quality methods on quads no episode produces (tests/quality_ref.py: concave, inverted,
+    self-intersecting, zero edges, coincident / collinear vertices, near-degenerate, axis-aligned, non-finite, and the
+    scaled / shifted images): per quad the eight record values (reference_element_record) and
+    MeshGeneration.get_quality(element, index) for the indices 0, 1, 3, 4, 5, each evaluated on its own, with a mask of
+    the values the reference cannot produce because it raises.  -> tests/golden/quality_edge_quads.npz"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import quality_ref as Q
+    _, Vertex, _, _ = H.load_reference()
+    from mesh_rl.legacy.components_legacy import Mesh
+    env = H.make_env(H.domain_points("boundary0"))
+    names, quads, cid = Q.golden_sample()
+    raises = (ZeroDivisionError, ValueError, OverflowError)
+    rec = np.zeros((len(quads), 8)); rec_raised = np.zeros((len(quads), 8), np.uint8)
+    idx = np.zeros((len(quads), len(Q.INDICES))); idx_raised = np.zeros((len(quads), len(Q.INDICES)), np.uint8)
+    for n, q in enumerate(quads):
+        def mesh():
+            return Mesh([Vertex(float(x), float(y)) for x, y in q])
+
+        def angles():
+            m = mesh()
+            return [m.vertices[i].to_find_clockwise_angle(m.vertices[(i + 1) % 4], m.vertices[i - 1]) for i in range(4)]
+        record = [lambda: math.degrees(min(angles())), lambda: math.degrees(max(angles())),
+                  lambda: mesh().get_quality(type='s_jacobian'), lambda: mesh().get_quality(type='stretch'),
+                  lambda: mesh().get_quality(type='taper'), lambda: mesh().get_quality(type='robust'),
+                  lambda: mesh().compute_area()[0], lambda: mesh().get_quality()]
+        for k, f in enumerate(record):
+            try:
+                rec[n, k] = f()
+            except raises:
+                rec_raised[n, k] = 1
+        for k, index in enumerate(Q.INDICES):
+            try:
+                idx[n, k] = env.get_quality(mesh(), index)
+            except raises:
+                idx_raised[n, k] = 1
+    np.savez_compressed(os.path.join(OUT, "quality_edge_quads.npz"), quad_xy=quads, class_id=cid, class_names=np.array(names),
+                        record=rec, record_raised=rec_raised, index=np.array(Q.INDICES, np.int32), index_value=idx,
+                        index_raised=idx_raised)
+    print(f"quality edge fixture: {len(quads)} quads of {len(names)} classes; the reference raises for "
+          f"{int(rec_raised.sum())} record and {int(idx_raised.sum())} index values; non-finite without raising: "
+          f"{int((~np.isfinite(rec) & (rec_raised == 0)).sum())} / {int((~np.isfinite(idx) & (idx_raised == 0)).sum())}")
+
+
 def transform(points, scale, shift):
     return [(scale * x + shift[0], scale * y + shift[1]) for x, y in points]
 
@@ -523,6 +567,9 @@ def main():
         quality_fixture()
         plot_fixture()
         return
+    if "--quality-edges-only" in sys.argv:
+        quality_edge_fixture()
+        return
     if "--samepoint-only" in sys.argv:
         main_samepoint()
         return
@@ -536,6 +583,7 @@ def main():
     export_fixture()
     quality_fixture()
     plot_fixture()
+    quality_edge_fixture()
     for name, dom, kind, seed, T in TRACES:
         pts = H.domain_points(dom)
         acts = (H.uniform_actions if kind == "uniform" else H.biased_actions)(seed, T)

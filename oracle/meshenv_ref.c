@@ -453,18 +453,19 @@ static double quad_area(const P2 *m)
 /* Mesh.get_quality('robust'), C:881-892 */
 static double quad_robust(const P2 *m)
 {
-    double mn = INFINITY;
+    /* Python's min() / max() of a list start from its first entry (a NaN there stays, a later one is passed over) */
+    double mn = 0;
     for (int i = 0; i < 4; i++) {
         double l = dist(m[(i + 3) % 4], m[i]);
-        if (l < mn) mn = l;
+        if (i == 0 || l < mn) mn = l;
     }
     double d0 = dist(m[0], m[2]), d1 = dist(m[1], m[3]);
     double q1 = sqrt(2.0) * mn / (d1 > d0 ? d1 : d0);
-    double amin = INFINITY, amax = -INFINITY;
+    double amin = 0, amax = 0;
     for (int i = 0; i < 4; i++) {
         double a = cw(m[i], m[(i + 1) % 4], m[(i + 3) % 4]);
-        if (a < amin) amin = a;
-        if (a > amax) amax = a;
+        if (i == 0 || a < amin) amin = a;
+        if (i == 0 || a > amax) amax = a;
     }
     double q2 = amin / amax;
     return sqrt(q1 * q2);
@@ -1614,13 +1615,14 @@ void meshenv_ref_element_quality(const double *xy, double *out)
     P2 m[4];
     for (int i = 0; i < 4; i++) { m[i].x = xy[2 * i]; m[i].y = xy[2 * i + 1]; }
     /* corner angles as in 'robust' (components.py:878-881); math.degrees(x) = x * (180 / pi) */
-    double amin = INFINITY, amax = -INFINITY, err = -INFINITY;
+    /* (min() / max() of a Python list start from its first entry: a NaN there stays, a later one is passed over) */
+    double amin = 0, amax = 0, err = 0;
     for (int i = 0; i < 4; i++) {
         double a = cw(m[i], m[(i + 1) % 4], m[(i + 3) % 4]);
-        if (a < amin) amin = a;
-        if (a > amax) amax = a;
+        if (i == 0 || a < amin) amin = a;
+        if (i == 0 || a > amax) amax = a;
         double e = fabs(a - PI / 2); /* get_ave_error_angle, components.py:855-861 */
-        if (e > err) err = e;
+        if (i == 0 || e > err) err = e;
     }
     out[0] = amin * (180.0 / PI);
     out[1] = amax * (180.0 / PI);
@@ -1633,11 +1635,14 @@ void meshenv_ref_element_quality(const double *xy, double *out)
         double a1 = crossp(l0x, l0y, l1x, l1y), a0 = crossp(l3x, l3y, l0x, l0y);
         double n0 = sqrt(SQ(l0x) + SQ(l0y)), n1 = sqrt(SQ(l1x) + SQ(l1y));
         double n2 = sqrt(SQ(l2x) + SQ(l2y)), n3 = sqrt(SQ(l3x) + SQ(l3y));
-        double j = a0 / (n0 * n3);
-        double t = a1 / (n0 * n1); if (t < j) j = t;
-        t = a2 / (n1 * n2); if (t < j) j = t;
-        t = a3 / (n2 * n3); if (t < j) j = t;
-        out[2] = j;
+        /* a zero edge makes its two terms 0 / 0 and the reference raises ZeroDivisionError: the IEEE value is that NaN,
+         * the value of the first term with a zero denominator (min() alone passes over a NaN that is not the first term) */
+        double t0 = a0 / (n0 * n3), t1 = a1 / (n0 * n1), t2 = a2 / (n1 * n2), t3 = a3 / (n2 * n3);
+        double j = t0;
+        if (t1 < j) j = t1;
+        if (t2 < j) j = t2;
+        if (t3 < j) j = t3;
+        out[2] = n0 * n3 == 0 ? t0 : (n0 * n1 == 0 ? t1 : (n1 * n2 == 0 ? t2 : (n2 * n3 == 0 ? t3 : j)));
         /* 'taper', components.py:885-890 */
         double x1x = (p1.x - p0.x) + (p2.x - p3.x), x1y = (p1.y - p0.y) + (p2.y - p3.y);
         double x2x = (p2.x - p1.x) + (p3.x - p0.x), x2y = (p2.y - p1.y) + (p3.y - p0.y);
@@ -1647,10 +1652,10 @@ void meshenv_ref_element_quality(const double *xy, double *out)
     }
     /* 'stretch', components.py:870-872 */
     {
-        double mn = INFINITY;
+        double mn = 0;
         for (int i = 0; i < 4; i++) {
             double l = dist(m[(i + 3) % 4], m[i]);
-            if (l < mn) mn = l;
+            if (i == 0 || l < mn) mn = l;
         }
         double d0 = dist(m[0], m[2]), d1 = dist(m[1], m[3]);
         out[3] = sqrt(2.0) * mn / (d1 > d0 ? d1 : d0);
@@ -1659,11 +1664,11 @@ void meshenv_ref_element_quality(const double *xy, double *out)
     out[6] = quad_area(m);
     /* 'default', components.py:864-869 with get_aspect_ratio 839-844 */
     {
-        double mx = -INFINITY, mn = INFINITY;
+        double mx = 0, mn = 0;
         for (int i = 0; i < 4; i++) {
             double l = dist(m[i], m[(i + 3) % 4]);
-            if (l > mx) mx = l;
-            if (l < mn) mn = l;
+            if (i == 0 || l > mx) mx = l;
+            if (i == 0 || l < mn) mn = l;
         }
         double aspect = mn != 0 ? mx / mn : 0.001;
         out[7] = 1 / (aspect + err);
@@ -1690,7 +1695,7 @@ double meshenv_ref_quad_quality(const double *xy, int index)
     }
     double area = 0.5 * e[0] * e[1] * sin(ang[0]) + 0.5 * e[2] * e[3] * sin(ang[2]); /* compute_area, C:935-950 */
     double q1 = 0;
-    if (area > 0) { /* get_quality_3, C:952-961 */
+    if (!(area <= 0)) { /* get_quality_3, C:952-961: `if area <= 0: q1 = 0`, so a NaN area takes the pow branch */
         double product = 1;
         for (int i = 0; i < 4; i++) product *= pow(e[i] / sqrt(area), sqrt(area) - e[i] > 0 ? 1 : -1);
         q1 = pow(product, 1.0 / 4);
@@ -1699,11 +1704,11 @@ double meshenv_ref_quad_quality(const double *xy, int index)
     for (int i = 0; i < 4; i++) ap *= 1 - (fabs(ang[i] * (180.0 / PI) - 90) / 90); /* math.degrees(x) = x * (180 / pi) */
     double q2 = ap < 0 ? 0 : pow(ap, 1.0 / 4);
     if (index == 1) return pow(q1 * q2, 1.0 / 2);
-    double amin = INFINITY, amax = -INFINITY;
+    double amin = 0, amax = 0;
     for (int i = 0; i < 4; i++) {
         double a = fabs(ang[i]);
-        if (a < amin) amin = a;
-        if (a > amax) amax = a;
+        if (i == 0 || a < amin) amin = a;
+        if (i == 0 || a > amax) amax = a;
     }
     return sqrt(q1 * (amin / amax));
 }

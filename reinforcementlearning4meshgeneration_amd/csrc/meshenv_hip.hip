@@ -1552,6 +1552,17 @@ __global__ void k_selftest(int what, int n, const double *in, double *out, int l
         const double *q = in + 7 * (size_t)i;
         const P2 p = mkp(q[0], q[1]), vi = mkp(q[2], q[3]), vm = mkp(q[4], q[5]), far = mkp(q[6], q[1]);
         out[i] = (pip_filter_usable(fabs(q[6] - p.x)) && pip_edge_clear(p, vi, vm) ? 1.0 : 0.0) + (straddle(p, far, vi, vm) && straddle(vi, vm, p, far) ? 2.0 : 0.0);
+    } else if (what == 19) {
+        // one entry of element_quality (csrc/meshenv_quality.h) for an arbitrary quad: 9 doubles = the four vertices
+        // (x, y) in Mesh.vertices order, then the record index 0-7; NaN for any other index
+        const double *q = in + 9 * (size_t)i;
+        P2 m[4];
+        for (int k = 0; k < 4; k++) m[k] = mkp(q[2 * k], q[2 * k + 1]);
+        double rec[kQualityDim];
+        element_quality(m, rec);
+        double r = __builtin_nan("");
+        for (int k = 0; k < kQualityDim; k++) r = q[8] == (double)k ? rec[k] : r;
+        out[i] = r;
     }
 }
 
@@ -1559,6 +1570,7 @@ int meshenv_selftest(int device, int what, int n, int in_per_item, const double 
 {
     if (n <= 0 || !in_host || !out_host || in_per_item <= 0) return MESHENV_E_ARG;
     if ((what == 17 || what == 18) && in_per_item != 7) return MESHENV_E_ARG;   // 7 doubles per case (k_selftest)
+    if (what == 19 && in_per_item != 9) return MESHENV_E_ARG;                    // 9 doubles per case (k_selftest)
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return MESHENV_E_HIP;
     double *din = nullptr, *dout = nullptr;

@@ -46,24 +46,27 @@ __device__ __forceinline__ double wave_sum_f64(double v)
 __device__ __forceinline__ void element_quality(const P2 *m, double *q)
 {
     const double kPi = 3.141592653589793;
-    double ang[4], amin = kInf, amax = -kInf, err = -kInf;
+    // Python's min() / max() of a list start from its FIRST entry and replace it only on a true comparison, so a NaN in
+    // slot 0 stays and a NaN in a later slot is passed over: every running minimum / maximum here starts the same way
+    // (tests/test_gpu_quality_edges.py, the non-finite class).
+    double ang[4], amin = 0, amax = 0, err = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         ang[i] = cw(m[i], m[(i + 1) & 3], m[(i + 3) & 3]);  // components.py:878-881
-        amin = ang[i] < amin ? ang[i] : amin;
-        amax = ang[i] > amax ? ang[i] : amax;
         const double e = fabs(ang[i] - kPi / 2);  // get_ave_error_angle, components.py:855-861
-        err = e > err ? e : err;
+        amin = (i == 0 || ang[i] < amin) ? ang[i] : amin;
+        amax = (i == 0 || ang[i] > amax) ? ang[i] : amax;
+        err = (i == 0 || e > err) ? e : err;
     }
     q[0] = amin * (180.0 / kPi);  // math.degrees
     q[1] = amax * (180.0 / kPi);
     // edge lengths e[i] = d(v[i], v[i-1]) and diagonals
-    double e[4], emin = kInf, emax = -kInf;
+    double e[4], emin = 0, emax = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         e[i] = dist(m[i], m[(i + 3) & 3]);
-        emin = e[i] < emin ? e[i] : emin;
-        emax = e[i] > emax ? e[i] : emax;
+        emin = (i == 0 || e[i] < emin) ? e[i] : emin;
+        emax = (i == 0 || e[i] > emax) ? e[i] : emax;
     }
     const double d0 = dist(m[0], m[2]), d1 = dist(m[1], m[3]);
     {
@@ -75,13 +78,14 @@ __device__ __forceinline__ void element_quality(const P2 *m, double *q)
         const double a1 = crossp(l0x, l0y, l1x, l1y), a0 = crossp(l3x, l3y, l0x, l0y);
         const double n0 = sqrt(l0x * l0x + l0y * l0y), n1 = sqrt(l1x * l1x + l1y * l1y);
         const double n2 = sqrt(l2x * l2x + l2y * l2y), n3 = sqrt(l3x * l3x + l3y * l3y);
-        double j = a0 / (n0 * n3), t = a1 / (n0 * n1);
-        j = t < j ? t : j;
-        t = a2 / (n1 * n2);
-        j = t < j ? t : j;
-        t = a3 / (n2 * n3);
-        j = t < j ? t : j;
-        q[2] = j;
+        // a zero edge makes its two terms 0 / 0, where the reference raises ZeroDivisionError: the value is that of the
+        // first term with a zero denominator (min() alone passes over a NaN that is not the first term)
+        const double t0 = a0 / (n0 * n3), t1 = a1 / (n0 * n1), t2 = a2 / (n1 * n2), t3 = a3 / (n2 * n3);
+        double j = t0;
+        j = t1 < j ? t1 : j;
+        j = t2 < j ? t2 : j;
+        j = t3 < j ? t3 : j;
+        q[2] = n0 * n3 == 0 ? t0 : (n0 * n1 == 0 ? t1 : (n1 * n2 == 0 ? t2 : (n2 * n3 == 0 ? t3 : j)));
         // 'taper', components.py:885-890
         const double x1x = (p1.x - p0.x) + (p2.x - p3.x), x1y = (p1.y - p0.y) + (p2.y - p3.y);
         const double x2x = (p2.x - p1.x) + (p3.x - p0.x), x2y = (p2.y - p1.y) + (p3.y - p0.y);
@@ -126,17 +130,23 @@ __device__ __forceinline__ void env_quality(const DevState &S, const EnvScalars 
         const int4 g = quads[i];
         const int gid[4] = {g.x, g.y, g.z, g.w};
         P2 m[4];
+        bool missing = false;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             // a created vertex past log_capacity was never stored (MESHENV_ST_LOG_OVERFLOW): NaN record, no read
             const int kn = gid[k] & ~kNewBit;
             const bool created = (gid[k] & kNewBit) != 0;
             const double kNaN = __builtin_nan("");
+            missing = missing || (created && kn >= cap);
             const double2 v = created ? (kn < cap ? vnew[kn] : make_double2(kNaN, kNaN)) : cold.dom_xy[doff + gid[k]];
             m[k] = mkp(v.x, v.y);
         }
         double q[kQualityDim];
         element_quality(m, q);
+        // (the corner opposite a NaN vertex does not see it, and min() / max() pass over a NaN behind the first slot:
+        // the NaN record is written out, not left to the arithmetic)
+#pragma unroll
+        for (int k = 0; k < kQualityDim; k++) q[k] = missing ? __builtin_nan("") : q[k];
         if (elem_out) {
             double2 *dst = reinterpret_cast<double2 *>(elem_out + ((size_t)env * cap + i) * kQualityDim);
 #pragma unroll
@@ -199,7 +209,7 @@ __device__ __forceinline__ double quad_quality_index(const P2 *m, int index)
     }
     const double area = 0.5 * e[0] * e[1] * sin(ang[0]) + 0.5 * e[2] * e[3] * sin(ang[2]);  // compute_area, C:935-950
     double q1 = 0.0;  // get_quality_3, C:952-972
-    if (area > 0) {
+    if (!(area <= 0)) {  // `if area <= 0: q1 = 0`: a NaN area takes the pow branch
         const double ra = sqrt(area);
         double product = 1.0;
 #pragma unroll
@@ -211,12 +221,12 @@ __device__ __forceinline__ double quad_quality_index(const P2 *m, int index)
     for (int i = 0; i < 4; i++) ap *= 1 - (fabs(ang[i] * (180.0 / kPi) - 90) / 90);
     const double q2 = ap < 0 ? 0.0 : pow(ap, 0.25);
     if (index == 1) return sqrt(q1 * q2);
-    double amin = kInf, amax = -kInf;
+    double amin = 0, amax = 0;  // min() / max() of a Python list: see element_quality
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const double a = fabs(ang[i]);
-        amin = a < amin ? a : amin;
-        amax = a > amax ? a : amax;
+        amin = (i == 0 || a < amin) ? a : amin;
+        amax = (i == 0 || a > amax) ? a : amax;
     }
     return sqrt(q1 * (amin / amax));  // 'strong'
 }
