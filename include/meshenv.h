@@ -685,6 +685,58 @@ int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev,
                                  float *loss_dev, float *q1_dev, float *q2_dev, float *const *acts1_dev, float *const *acts2_dev);
 
 /*
+ * The actor loss and the entropy-coefficient loss of SAC and their gradients on the device (csrc/meshenv_actor_grad.h): the
+ * statements of SB3 2.x's SAC.train that follow the critic update,
+ *     actions_pi, log_prob = self.actor.action_log_prob(replay_data.observations)
+ *     ent_coef = th.exp(self.log_ent_coef.detach())
+ *     ent_coef_loss = -(self.log_ent_coef * (log_prob + self.target_entropy).detach()).mean()
+ *     q_values_pi = th.cat(self.critic(replay_data.observations, actions_pi), dim=1)
+ *     min_qf_pi, _ = th.min(q_values_pi, dim=1, keepdim=True)
+ *     actor_loss = (ent_coef * log_prob - min_qf_pi).mean()
+ *     self.actor.optimizer.zero_grad(); actor_loss.backward()
+ * for the recipe the reference runs (rl/baselines/RL_Mesh.py:179-205: SAC('MlpPolicy', batch_size=100), actor ReLU
+ * [128, 128, 128] with mu / log_std heads, twin critics ReLU [128, 128, 128], float32).  SAC only; the optimiser steps stay
+ * the caller's.  ent_coef: SB3's fixed coefficient, used when meshenv_actor_grad_bind gets no log_ent_coef; target_entropy:
+ * self.target_entropy (-3 for the 3 actions).  MESHENV_E_ARG when either is not finite.
+ */
+typedef struct MeshActorGrad MeshActorGrad;
+int meshenv_actor_grad_create(int device, void *stream, float ent_coef, float target_entropy, MeshActorGrad **out);
+void meshenv_actor_grad_destroy(MeshActorGrad *g);
+int meshenv_actor_grad_set_stream(MeshActorGrad *g, void *stream);
+const char *meshenv_actor_grad_last_error(const MeshActorGrad *g);   /* message of the handle's last failure */
+/*
+ * Records the DEVICE pointers of the LIVE float32, contiguous torch.nn.Linear parameters (the caller checks dtype, layout
+ * and device).  Nothing is read yet.
+ *   actor_dev   self.actor: w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w log_std_b (n_actor 10)
+ *   q1_dev, q2_dev   self.critic.q_networks[0], [1] (not critic_target): w1 b1 w2 b2 w3 b3 w4 b4 (n_critic 8); read only
+ *   log_ent_coef_dev   self.log_ent_coef [1] (ent_coef = th.exp(self.log_ent_coef.detach()), taken at every backward), or NULL
+ *   grad_dev [n_grad]   the caller's flat gradient buffer, n_grad = 36288: the actor's gradients in the order of actor_dev
+ *       and in torch's [out][in] / [out] layout (w1 [128][18] first), then log_ent_coef.grad at float 36230, then padding
+ * [128][128] and [3][128] weights 16-byte aligned.  Optimisers write in place, so the pointers stay valid; bind again after
+ * anything that reallocates.  Allocates the handle's workspace of 128 partial gradient sets on the first call.
+ */
+int meshenv_actor_grad_bind(MeshActorGrad *g, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
+                            const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev, float *grad_dev, int64_t n_grad);
+/*
+ * actor_loss.backward() and the ent_coef statements: two launches on the handle's stream, no host copy, no
+ * synchronisation.  obs_dev [n][18] (replay_data.observations).  eps of actions_pi: noise_dev [n][3], or sample != 0 for
+ * Philox4x32-10 keyed by seed at counter words (sample index, counter lo, counter hi, 3) -- tag 3 is this call's own
+ * (rollout noise 0, replay draw 1, TD target 2) -- or neither for eps = 0.  OVERWRITES the actor's part of grad_dev with
+ * the gradients of actor_loss and, with a bound log_ent_coef, float 36230 with that of ent_coef_loss; the critics'
+ * parameters are read and receive nothing.  losses_dev [2]: actor_loss, ent_coef_loss (the second is written only with a
+ * bound log_ent_coef).  eps_out_dev [n][3] (nullable, needs noise or sample) receives the eps used.  Optional, all of an
+ * array or NULL: parts_dev[7] = actions_pi [n][3], log_prob [n], q1_pi [n], q2_pi
+ * [n], dq_da [n][3] (the selected critic's dQ/da; q1 <= q2 selects critic 1), d_mu [n][3], d_log_std [n][3] (the head
+ * gradients); acts_dev[9] = per network (actor, critic 1, critic 2) and hidden layer a [n][128] buffer receiving the
+ * post-ReLU activations (a > 0 is the mask the backward pass used).  Deterministic: the sums over the batch have a fixed
+ * order, the same inputs give the same bits.
+ * MESHENV_E_STATE before meshenv_actor_grad_bind; MESHENV_E_ARG for n < 1 or a missing input, noise_dev with sample, or
+ * eps_out_dev without either.
+ */
+int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, const float *noise_dev, int sample, uint64_t seed,
+                                uint64_t counter, float *losses_dev, float *eps_out_dev, float *const *parts_dev, float *const *acts_dev);
+
+/*
  * Policy evaluation on the device (csrc/meshenv_eval.h): SB3 2.x's evaluate_policy loop (non-Monitor branch) -- the loop
  * the reference's evaluation callers run with a deterministic model.predict:
  *   rl/baselines/CustomizeCallback.py:27-141   every 1000 training steps, to pick best_model

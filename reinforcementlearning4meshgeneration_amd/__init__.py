@@ -7,7 +7,8 @@ from .domains import boundary, domain_constants, generate_polygon, random_domain
 
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
-           "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec"]
+           "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
+           "FusedActorGrad", "ActorGradSpec"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -41,4 +42,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedCriticGrad", "CriticGradSpec"):
         from . import critic_grad
         return getattr(critic_grad, name)
+    if name in ("FusedActorGrad", "ActorGradSpec"):
+        from . import actor_grad
+        return getattr(actor_grad, name)
     raise AttributeError(name)

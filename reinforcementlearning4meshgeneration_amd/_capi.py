@@ -64,6 +64,8 @@ EXPORTS = [
     "meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward",
     "meshenv_critic_grad_create", "meshenv_critic_grad_destroy", "meshenv_critic_grad_set_stream",
     "meshenv_critic_grad_last_error", "meshenv_critic_grad_bind", "meshenv_critic_grad_backward",
+    "meshenv_actor_grad_create", "meshenv_actor_grad_destroy", "meshenv_actor_grad_set_stream",
+    "meshenv_actor_grad_last_error", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward",
 ]
 
 
@@ -211,6 +213,17 @@ def load():
     L.meshenv_critic_grad_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     for name in ("meshenv_critic_grad_create", "meshenv_critic_grad_set_stream", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward"):
+        getattr(L, name).restype = C.c_int
+    L.meshenv_actor_grad_create.argtypes = [C.c_int, vp, C.c_float, C.c_float, C.POINTER(vp)]
+    L.meshenv_actor_grad_destroy.argtypes = [vp]
+    L.meshenv_actor_grad_destroy.restype = None
+    L.meshenv_actor_grad_set_stream.argtypes = [vp, vp]
+    L.meshenv_actor_grad_last_error.argtypes = [vp]
+    L.meshenv_actor_grad_last_error.restype = C.c_char_p
+    L.meshenv_actor_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, vp, vp, C.c_int64]
+    L.meshenv_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    for name in ("meshenv_actor_grad_create", "meshenv_actor_grad_set_stream", "meshenv_actor_grad_bind",
+                 "meshenv_actor_grad_backward"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
                  "meshenv_step_policy_multi"):

@@ -29,6 +29,7 @@
 #include "meshenv_replay.h"
 #include "meshenv_target.h"
 #include "meshenv_critic_grad.h"
+#include "meshenv_actor_grad.h"
 
 using namespace meshenv;
 
@@ -2799,6 +2800,163 @@ int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev,
     hipLaunchKernelGGL(k_critic_grad_reduce, dim3((grads + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg, set,
                        grads, n, g->grad, loss_dev);
     if (hipGetLastError() != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: reduction launch failed");
+    return MESHENV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC actor / ent_coef loss gradients
+struct MeshActorGrad {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    float ent_coef = 0.0f, target_entropy = 0.0f;
+    AgActor a{};
+    CgCritic c[2]{};
+    const float *log_ent_coef = nullptr;
+    float *grad = nullptr;      // the caller's flat gradient buffer (AgLayout::stride floats)
+    float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
+    bool bound = false;
+    std::string err;
+};
+
+namespace {
+
+int ag_fail(MeshActorGrad *g, int rc, const std::string &msg)
+{
+    g->err = msg;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_actor_grad_create(int device, void *stream, float ent_coef, float target_entropy, MeshActorGrad **out)
+{
+    if (!out) return MESHENV_E_ARG;
+    *out = nullptr;
+    if (!std::isfinite(ent_coef) || !std::isfinite(target_entropy)) {
+        g_create_error = "meshenv_actor_grad_create: ent_coef and target_entropy must be finite";
+        return MESHENV_E_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        g_create_error = "meshenv_actor_grad_create: no such HIP device";
+        return MESHENV_E_HIP;
+    }
+    MeshActorGrad *g = new MeshActorGrad();
+    g->device = device;
+    g->stream = (hipStream_t)stream;
+    g->ent_coef = ent_coef;
+    g->target_entropy = target_entropy;
+    *out = g;
+    return MESHENV_OK;
+}
+
+void meshenv_actor_grad_destroy(MeshActorGrad *g)
+{
+    if (!g) return;
+    DeviceGuard guard(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    if (g->partial) (void)hipFree(g->partial);
+    delete g;
+}
+
+const char *meshenv_actor_grad_last_error(const MeshActorGrad *g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+
+int meshenv_actor_grad_set_stream(MeshActorGrad *g, void *stream)
+{
+    if (!g) return MESHENV_E_ARG;
+    g->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+int meshenv_actor_grad_bind(MeshActorGrad *g, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
+                            const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev, float *grad_dev, int64_t n_grad)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!actor_dev || !q1_dev || !q2_dev || n_actor != 10 || n_critic != 8)
+        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: takes 10 actor tensors and 8 tensors per critic (SAC: actor ReLU "
+                       "[128, 128, 128] with mu / log_std heads, twin ReLU [128, 128, 128] critics, float32)");
+    if (!grad_dev || n_grad != AgLayout::stride)
+        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: the gradient buffer has " + std::to_string(AgLayout::stride) +
+                       " floats, got " + std::to_string((long long)n_grad));
+    for (int i = 0; i < 10; i++) {
+        if (!actor_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: null actor tensor");
+        // the [H][H] weights and the heads' [3][H] weights are read 16 bytes at a time
+        if (i % 2 == 0 && i >= 2 && ((uintptr_t)actor_dev[i] & 15))
+            return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: actor weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    for (int i = 0; i < 8; i++) {
+        if (!q1_dev[i] || !q2_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: null critic tensor");
+        if (i % 2 == 0 && i >= 2 && (((uintptr_t)q1_dev[i] | (uintptr_t)q2_dev[i]) & 15))
+            return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: critic weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: hipSetDevice failed");
+    if (!g->partial) {
+        const size_t bytes = (size_t)kCgMaxGroups * AgLayout::set * sizeof(float);
+        if (hipMalloc((void **)&g->partial, bytes) != hipSuccess || hipMemsetAsync(g->partial, 0, bytes, g->stream) != hipSuccess ||
+            hipStreamSynchronize(g->stream) != hipSuccess)   // the stream may change before the first backward
+            return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: allocation failed");
+    }
+    for (int l = 0; l < 3; l++) {
+        g->a.w[l] = actor_dev[2 * l];
+        g->a.b[l] = actor_dev[2 * l + 1];
+    }
+    g->a.mu_w = actor_dev[6]; g->a.mu_b = actor_dev[7]; g->a.ls_w = actor_dev[8]; g->a.ls_b = actor_dev[9];
+    for (int k = 0; k < 2; k++) {
+        const float *const *p = k == 0 ? q1_dev : q2_dev;
+        for (int l = 0; l <= 3; l++) {
+            g->c[k].w[l] = p[2 * l];
+            g->c[k].b[l] = p[2 * l + 1];
+        }
+    }
+    g->log_ent_coef = log_ent_coef_dev;
+    g->grad = grad_dev;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, const float *noise_dev, int sample, uint64_t seed,
+                                uint64_t counter, float *losses_dev, float *eps_out_dev, float *const *parts_dev, float *const *acts_dev)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!g->bound) return ag_fail(g, MESHENV_E_STATE, "meshenv_actor_grad_backward: no tensors bound (meshenv_actor_grad_bind)");
+    if (n <= 0 || !obs_dev || !losses_dev)
+        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: n > 0, obs_dev and losses_dev are required");
+    if (noise_dev && sample)
+        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: noise_dev and sample are exclusive");
+    if (eps_out_dev && !noise_dev && !sample)
+        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: eps_out_dev needs noise_dev or sample");
+    AgArgs A{};
+    const int tiles = (n + kCgRows - 1) / kCgRows;
+    A.n = n;
+    A.nwg = tiles <= 512 ? (tiles < 64 ? tiles : 64) : kCgMaxGroups;
+    A.obs = obs_dev; A.noise = noise_dev; A.sample = sample ? 1 : 0; A.seed = seed; A.counter = counter;
+    A.a = g->a; A.c[0] = g->c[0]; A.c[1] = g->c[1];
+    A.log_ent_coef = g->log_ent_coef; A.ent_coef = g->ent_coef; A.target_entropy = g->target_entropy;
+    A.partial = g->partial;
+    A.eps_out = eps_out_dev;
+    if (parts_dev) {
+        for (int i = 0; i < kAgParts; i++)
+            if (!parts_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null per-sample output");
+        A.actions = parts_dev[0]; A.log_prob = parts_dev[1]; A.q[0] = parts_dev[2]; A.q[1] = parts_dev[3];
+        A.dq_da = parts_dev[4]; A.d_mu = parts_dev[5]; A.d_ls = parts_dev[6];
+    }
+    if (acts_dev) {
+        for (int i = 0; i < 9; i++) {
+            if (!acts_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null activation output");
+            A.acts[i / 3][i % 3] = acts_dev[i];
+        }
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: hipSetDevice failed");
+    hipLaunchKernelGGL(k_actor_grad, dim3(A.nwg), dim3(512), 0, g->stream, A);
+    if (hipGetLastError() != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: launch failed");
+    hipLaunchKernelGGL(k_actor_grad_reduce, dim3((AgLayout::ent + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg,
+                       n, g->log_ent_coef, g->grad, losses_dev);
+    if (hipGetLastError() != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: reduction launch failed");
     return MESHENV_OK;
 }
 
