@@ -8,7 +8,7 @@ from .domains import boundary, domain_constants, generate_polygon, random_domain
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
            "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
-           "FusedActorGrad", "ActorGradSpec"]
+           "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -45,4 +45,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedActorGrad", "ActorGradSpec"):
         from . import actor_grad
         return getattr(actor_grad, name)
+    if name in ("FusedOptimStep", "OptimStepSpec"):
+        from . import optim_step
+        return getattr(optim_step, name)
     raise AttributeError(name)

@@ -68,6 +68,20 @@ EXPORTS = [
     "meshenv_actor_grad_last_error", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward",
 ]
 
+# every symbol include/meshenv_optim.h declares (the optimiser step has a header of its own)
+EXPORTS_OPTIM = [
+    "meshenv_optim_create", "meshenv_optim_destroy", "meshenv_optim_set_stream", "meshenv_optim_last_error",
+    "meshenv_optim_bind", "meshenv_optim_step",
+]
+OPTIM_PROGRAMS, OPTIM_BLOCKS, OPTIM_CHUNK = 8, 4, 1024
+OPTIM_ADAM, OPTIM_POLYAK, OPTIM_ADAM_POLYAK = 1, 2, 3
+
+
+class MeshOptimScalars(C.Structure):
+    """include/meshenv_optim.h MeshOptimScalars: the host-computed scalars of one step, a kernel argument."""
+    _fields_ = [(name, C.c_float * OPTIM_BLOCKS) for name in ("step_size", "bc2_sqrt", "w1", "beta2", "w2", "eps")] + [
+        ("tau", C.c_float), ("one_minus_tau", C.c_float)]
+
 
 def load():
     """Load the HIP library (no GPU needed for loading; compute calls need one)."""
@@ -224,6 +238,16 @@ def load():
     L.meshenv_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     for name in ("meshenv_actor_grad_create", "meshenv_actor_grad_set_stream", "meshenv_actor_grad_bind",
                  "meshenv_actor_grad_backward"):
+        getattr(L, name).restype = C.c_int
+    L.meshenv_optim_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
+    L.meshenv_optim_destroy.argtypes = [vp]
+    L.meshenv_optim_destroy.restype = None
+    L.meshenv_optim_set_stream.argtypes = [vp, vp]
+    L.meshenv_optim_last_error.argtypes = [vp]
+    L.meshenv_optim_last_error.restype = C.c_char_p
+    L.meshenv_optim_bind.argtypes = [vp, C.c_int, C.c_int] + [C.POINTER(vp)] * 5 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 3
+    L.meshenv_optim_step.argtypes = [vp, C.c_int, C.POINTER(MeshOptimScalars)]
+    for name in ("meshenv_optim_create", "meshenv_optim_set_stream", "meshenv_optim_bind", "meshenv_optim_step"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
                  "meshenv_step_policy_multi"):

@@ -12,6 +12,7 @@ LIB_NAME = "libmeshenv_hip.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
 SOURCES = ["meshenv_hip.hip"]
 ARCH = "gfx950"
+PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h"]      # include/: the C-ABI the translation unit implements
 
 # -ffp-contract=off: the reference is CPython float arithmetic, which never fuses a*b+c.
 # -fhip-fp32-correctly-rounded-divide-sqrt: numpy's float32 round() divides in IEEE float32.
@@ -39,7 +40,7 @@ def needs_build() -> bool:
     t = os.path.getmtime(LIB_PATH)
     # every header of csrc/ is a dependency of the one translation unit (meshenv_hip.hip includes them all)
     deps = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip"))]
-    deps.append(os.path.join(os.path.dirname(PKG_DIR), "include", "meshenv.h"))
+    deps += [os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in PUBLIC_HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -55,7 +56,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
     import json
     h = hashlib.sha256()
     root = os.path.dirname(PKG_DIR)
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join(root, "include", "meshenv.h")]
+    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join(root, "include", h) for h in PUBLIC_HEADERS]
     for f in files:
         h.update(os.path.relpath(f, root).encode())
         h.update(open(f, "rb").read())

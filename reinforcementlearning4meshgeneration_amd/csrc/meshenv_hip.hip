@@ -4,6 +4,7 @@
 // the handle's stream.  Nothing here computes environment results on the host: without a working GPU every
 // entry point fails with MESHENV_E_HIP.
 #include "../../include/meshenv.h"
+#include "../../include/meshenv_optim.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -30,6 +31,7 @@
 #include "meshenv_target.h"
 #include "meshenv_critic_grad.h"
 #include "meshenv_actor_grad.h"
+#include "meshenv_optim.h"
 
 using namespace meshenv;
 
@@ -2957,6 +2959,177 @@ int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, c
     hipLaunchKernelGGL(k_actor_grad_reduce, dim3((AgLayout::ent + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg,
                        n, g->log_ent_coef, g->grad, losses_dev);
     if (hipGetLastError() != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: reduction launch failed");
+    return MESHENV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ Adam steps and polyak_update
+static_assert(sizeof(MeshOptimScalars) == sizeof(OptScalars), "include/meshenv_optim.h and csrc/meshenv_optim.h disagree");
+static_assert(MESHENV_OPTIM_BLOCKS == kOptBlocks && MESHENV_OPTIM_CHUNK == kOptChunk, "include/meshenv_optim.h and csrc/meshenv_optim.h disagree");
+static_assert(MESHENV_OPTIM_ADAM == kOptAdam && MESHENV_OPTIM_POLYAK == kOptPolyak && MESHENV_OPTIM_ADAM_POLYAK == kOptAdamPolyak, "ops");
+
+struct OptProgram {
+    char *dev = nullptr;        // the segment table, then the job table
+    char *host = nullptr;       // pinned staging of the same layout
+    size_t cap = 0;
+    size_t jobs_at = 0;         // byte offset of the job table
+    int n_jobs = 0;
+    hipEvent_t copied = nullptr;   // the last upload from `host`
+    hipStream_t ordered = nullptr; // the stream that is known to be ordered after that upload
+    bool bound = false;
+};
+
+struct MeshOptim {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t last_stream = nullptr;   // the stream of the last upload or launch: what may still read a table
+    bool used = false;
+    OptProgram prog[MESHENV_OPTIM_PROGRAMS];
+    std::string err;
+};
+
+namespace {
+
+int opt_fail(MeshOptim *o, int rc, const std::string &msg)
+{
+    o->err = msg;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_optim_create(int device, void *stream, MeshOptim **out)
+{
+    if (!out) return MESHENV_E_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        g_create_error = "meshenv_optim_create: no such HIP device";
+        return MESHENV_E_HIP;
+    }
+    MeshOptim *o = new MeshOptim();
+    o->device = device;
+    o->stream = (hipStream_t)stream;
+    *out = o;
+    return MESHENV_OK;
+}
+
+void meshenv_optim_destroy(MeshOptim *o)
+{
+    if (!o) return;
+    DeviceGuard guard(o->device);
+    if (o->used) (void)hipStreamSynchronize(o->last_stream);
+    for (OptProgram &P : o->prog) {
+        if (P.copied) (void)hipEventDestroy(P.copied);
+        if (P.dev) (void)hipFree(P.dev);
+        if (P.host) (void)hipHostFree(P.host);
+    }
+    delete o;
+}
+
+const char *meshenv_optim_last_error(const MeshOptim *o) { return o ? o->err.c_str() : g_create_error.c_str(); }
+
+int meshenv_optim_set_stream(MeshOptim *o, void *stream)
+{
+    if (!o) return MESHENV_E_ARG;
+    o->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param_dev, const float *const *grad_dev,
+                       float *const *exp_avg_dev, float *const *exp_avg_sq_dev, float *const *target_dev, const int64_t *n,
+                       const int32_t *op, const int32_t *block, const int32_t *vec)
+{
+    if (!o) return MESHENV_E_ARG;
+    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS)
+        return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_bind: program " + std::to_string(program) + " out of range");
+    if (n_seg < 1 || !param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !target_dev || !n || !op || !block || !vec)
+        return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_bind: n_seg > 0 and all nine arrays are required");
+    int64_t n_jobs = 0;
+    for (int i = 0; i < n_seg; i++) {
+        const std::string at = "meshenv_optim_bind: segment " + std::to_string(i) + ": ";
+        if (op[i] != kOptAdam && op[i] != kOptPolyak && op[i] != kOptAdamPolyak)
+            return opt_fail(o, MESHENV_E_ARG, at + "op " + std::to_string(op[i]));
+        if (n[i] < 1 || n[i] > INT32_MAX - kOptChunk)
+            return opt_fail(o, MESHENV_E_ARG, at + std::to_string((long long)n[i]) + " elements");
+        if (block[i] < 0 || block[i] >= kOptBlocks) return opt_fail(o, MESHENV_E_ARG, at + "block " + std::to_string(block[i]));
+        const bool adam = op[i] & kOptAdam, polyak = op[i] & kOptPolyak;
+        if (!param_dev[i] || adam != (grad_dev[i] != nullptr) || adam != (exp_avg_dev[i] != nullptr) ||
+            adam != (exp_avg_sq_dev[i] != nullptr) || polyak != (target_dev[i] != nullptr))
+            return opt_fail(o, MESHENV_E_ARG, at + "the pointers do not match op " + std::to_string(op[i]));
+        const uintptr_t all = (uintptr_t)param_dev[i] | (uintptr_t)grad_dev[i] | (uintptr_t)exp_avg_dev[i] |
+                              (uintptr_t)exp_avg_sq_dev[i] | (uintptr_t)target_dev[i];
+        if (all & 3) return opt_fail(o, MESHENV_E_ARG, at + "a pointer is not 4-byte aligned");
+        if (vec[i] != 0 && (vec[i] != 1 || (all & 15)))
+            return opt_fail(o, MESHENV_E_ARG, at + "vec = " + std::to_string(vec[i]) + " on pointers that are not all 16-byte aligned");
+        n_jobs += (n[i] + kOptChunk - 1) / kOptChunk;
+    }
+    if (n_jobs > INT32_MAX) return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_bind: more than 2^31 - 1 workgroups");
+    const size_t jobs_at = ((size_t)n_seg * sizeof(OptSeg) + 15) / 16 * 16;
+    const size_t bytes = jobs_at + (size_t)n_jobs * sizeof(OptJob);
+    OptProgram &P = o->prog[program];
+    DeviceGuard guard(o->device);
+    if (guard.err != hipSuccess) return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipSetDevice failed");
+    // the staging block is free once its last upload is done; work on another stream may still read the tables
+    if (o->used && o->last_stream != o->stream && hipStreamSynchronize(o->last_stream) != hipSuccess)
+        return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipStreamSynchronize failed");
+    if (P.copied && hipEventSynchronize(P.copied) != hipSuccess)
+        return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipEventSynchronize failed");
+    P.bound = false;
+    if (bytes > P.cap) {
+        if (o->used && hipStreamSynchronize(o->stream) != hipSuccess)     // a launch in flight reads the old tables
+            return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipStreamSynchronize failed");
+        if (P.dev) (void)hipFree(P.dev);
+        if (P.host) (void)hipHostFree(P.host);
+        P.dev = P.host = nullptr;
+        P.cap = 0;
+        const size_t cap = bytes + bytes / 2;
+        if (hipMalloc((void **)&P.dev, cap) != hipSuccess || hipHostMalloc((void **)&P.host, cap, hipHostMallocDefault) != hipSuccess ||
+            (!P.copied && hipEventCreateWithFlags(&P.copied, hipEventDisableTiming) != hipSuccess))
+            return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: allocation failed");
+        P.cap = cap;
+    }
+    OptSeg *segs = reinterpret_cast<OptSeg *>(P.host);
+    OptJob *jobs = reinterpret_cast<OptJob *>(P.host + jobs_at);
+    int j = 0;
+    for (int i = 0; i < n_seg; i++) {
+        segs[i] = OptSeg{param_dev[i], grad_dev[i], exp_avg_dev[i], exp_avg_sq_dev[i], target_dev[i], (int32_t)n[i], op[i], block[i], vec[i]};
+        for (int64_t first = 0; first < n[i]; first += kOptChunk) jobs[j++] = OptJob{i, (int32_t)first};
+    }
+    if (hipMemcpyAsync(P.dev, P.host, bytes, hipMemcpyHostToDevice, o->stream) != hipSuccess ||
+        hipEventRecord(P.copied, o->stream) != hipSuccess)
+        return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: upload failed");
+    o->last_stream = P.ordered = o->stream;
+    o->used = true;
+    P.jobs_at = jobs_at;
+    P.n_jobs = (int)n_jobs;
+    P.bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_optim_step(MeshOptim *o, int program, const MeshOptimScalars *scalars)
+{
+    if (!o) return MESHENV_E_ARG;
+    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || !scalars)
+        return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_step: program out of range or no scalars");
+    OptProgram &P = o->prog[program];
+    if (!P.bound) return opt_fail(o, MESHENV_E_STATE, "meshenv_optim_step: program " + std::to_string(program) + " is not bound (meshenv_optim_bind)");
+    DeviceGuard guard(o->device);
+    if (guard.err != hipSuccess) return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipSetDevice failed");
+    if (P.ordered != o->stream) {           // the tables were uploaded on another stream: order this one after the upload
+        if (hipStreamWaitEvent(o->stream, P.copied, 0) != hipSuccess)
+            return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipStreamWaitEvent failed");
+        P.ordered = o->stream;
+    }
+    o->last_stream = o->stream;
+    OptScalars S;
+    std::memcpy(&S, scalars, sizeof(S));
+    hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
+                       (const OptJob *)(P.dev + P.jobs_at), S);
+    if (hipGetLastError() != hipSuccess) return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_step: launch failed");
     return MESHENV_OK;
 }
 

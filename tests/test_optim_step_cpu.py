@@ -1,0 +1,387 @@
+"""Host only: the fp64 restatement of the fused optimiser step (tests/optim_step_ref.py) against stock torch.optim.Adam and
+SB3's two Polyak statements on the CPU; its bound against a float32 evaluation and against named mistakes; the host scalars;
+the state OptimStepSpec creates; every refusal; the segment table; packaging."""
+import copy
+import ctypes
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import optim_step_ref as O
+
+CASES = [(1, False), (7, True)]          # (the step the call ends at, from a loaded state)
+
+
+def _state(step, loaded):
+    """[(p, m, v, g)] of the test tensors for the step that ends at ``step``."""
+    return [O.tensors(s, seed=50 + i + 100 * step, loaded=loaded) for i, s in enumerate(O.SHAPES)]
+
+
+def _stock(ts, step, lr=O.LR, **kw):
+    """A stock single-tensor Adam on CPU copies of ts, its state loaded when step > 1, gradients set; not stepped."""
+    params = [torch.from_numpy(p.copy()).requires_grad_(True) for p, _, _, _ in ts]
+    opt = torch.optim.Adam(params, lr=lr, betas=O.BETAS, eps=O.EPS, foreach=False, **kw)
+    if step > 1:
+        sd = opt.state_dict()
+        sd["state"] = {i: {"step": torch.tensor(float(step - 1)), "exp_avg": torch.from_numpy(m.copy()),
+                           "exp_avg_sq": torch.from_numpy(v.copy())} for i, (_, m, v, _) in enumerate(ts)}
+        opt.load_state_dict(sd)
+    for q, (_, _, _, g) in zip(params, ts):
+        q.grad = torch.from_numpy(g.copy())
+    return params, opt
+
+
+# ----------------------------------------------------------------------------------------------------------- 1. stock torch
+@pytest.mark.parametrize("step,loaded", CASES)
+def test_stock_adam_lies_within_the_bound(step, loaded):
+    ts = _state(step, loaded)
+    params, opt = _stock(ts, step)
+    opt.step()
+    sc = O.scalars(step)
+    top = 0.0
+    for i, (q, (p, m, v, g)) in enumerate(zip(params, ts)):
+        ref = O.adam(p, m, v, g, sc)
+        st = opt.state[q]
+        assert float(st["step"]) == step
+        top = max(top, O.worst({"p": q, "exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"]}, ref, f"step {step} tensor {i}"))
+        assert not np.array_equal(q.detach().numpy(), p) or p.size == 1 and g.flat[0] == 0
+    print(f"\nstock Adam on the CPU at step {step}: max |torch - fp64| / bound = {top:.4f}")
+    assert top > 0.0                                     # not a comparison of the reference with itself
+
+
+@pytest.mark.parametrize("tau", [0.005, 0.0, 1.0])
+def test_sb3_polyak_statements_lie_within_the_bound(tau):
+    top = 0.0
+    for i, s in enumerate(O.SHAPES):
+        p, t = O.tensors(s, seed=70 + i)[0], O.targets(s, seed=70 + i)
+        tt, pp = torch.from_numpy(t.copy()), torch.from_numpy(p.copy())
+        with torch.no_grad():                            # stable_baselines3.common.utils.polyak_update
+            tt.mul_(1 - tau)
+            torch.add(tt, pp, alpha=tau, out=tt)
+        top = max(top, O.assert_within(tt.numpy(), O.polyak(t, p, tau), f"tau {tau} tensor {i}"))
+        if tau == 0.0:
+            assert np.array_equal(tt.numpy(), t)
+        if tau == 1.0:
+            assert np.array_equal(tt.numpy(), p)
+    print(f"\nSB3's polyak_update on the CPU, tau = {tau}: max ratio {top:.4f}")
+
+
+@pytest.mark.parametrize("step,loaded", CASES)
+def test_bound_admits_the_float32_restatement(step, loaded):
+    sc = O.scalars(step)
+    for i, (p, m, v, g) in enumerate(_state(step, loaded)):
+        got = O.adam_f32(p, m, v, g, sc)
+        assert O.worst(got, O.adam(p, m, v, g, sc), f"step {step} tensor {i} fp32") >= 0.0
+        t = O.targets(p.shape, seed=i)
+        f = O.fused(p, m, v, g, t, sc, 0.005, p_after=got["p"])
+        O.assert_within(O.polyak_f32(t, got["p"], 0.005), f["target"], f"fused target {i}")
+
+
+# ----------------------------------------------------------------------------------------------------------- 2. mutants
+@pytest.mark.parametrize("step,loaded", CASES)
+@pytest.mark.parametrize("mutant", O.ADAM_MUTANTS)
+def test_bound_rejects_adam_mistakes(mutant, step, loaded):
+    caught = []
+    for i, (p, m, v, g) in enumerate(_state(step, loaded)):
+        ref = O.adam(p, m, v, g, O.scalars(step))
+        bad = O.adam(p, m, v, g, O.scalars(step, mutant=mutant), mutant=mutant)
+        caught += [k for k in ref if O.ratio(bad[k][0], ref[k])[1].any()]
+        assert not any(O.ratio(ref[k][0], ref[k])[1].any() for k in ref)
+    assert caught, f"the bound admits the mutant {mutant} at step {step}"
+
+
+def test_bound_rejects_polyak_mistakes():
+    p, m, v, g = O.tensors((4097,), seed=3)
+    t = O.targets((4097,), seed=3)
+    sc = O.scalars(1)
+    assert O.ratio(O.polyak(t, p, 0.005, mutant="tau_swapped")[0], O.polyak(t, p, 0.005))[1].any()
+    stored = O.adam_f32(p, m, v, g, sc)["p"]
+    ref = O.fused(p, m, v, g, t, sc, 0.005, p_after=stored)["target"]
+    bad = O.fused(p, m, v, g, t, sc, 0.005, p_after=stored, mutant="polyak_before_adam")["target"]
+    assert O.ratio(bad[0], ref)[1].any(), "the bound admits a fused Polyak that reads the parameter before its step"
+    assert not O.ratio(O.polyak_f32(t, stored, 0.005), ref)[1].any()
+    assert set(O.MUTANTS) == set(O.ADAM_MUTANTS) | {"tau_swapped", "polyak_before_adam"}
+
+
+# ----------------------------------------------------------------------------------------------------------- 3. host scalars
+@pytest.mark.parametrize("step", [1, 2, 7, 1000, 123457])
+@pytest.mark.parametrize("lr,betas", [(3e-4, (0.9, 0.999)), (1e-3, (0.5, 0.99)), (7.3e-5, (0.95, 0.9999))])
+def test_host_scalars_are_the_doubles_torch_computes(step, lr, betas):
+    from reinforcementlearning4meshgeneration_amd.optim_step import adam_scalars
+    beta1, beta2 = betas
+    assert adam_scalars(float(step), lr, beta1, beta2) == (lr / (1 - beta1 ** float(step)), (1 - beta2 ** float(step)) ** 0.5)
+    assert adam_scalars(float(step), lr, beta1, beta2) == O.torch_doubles(float(step), lr, beta1, beta2)
+
+
+def test_commit_passes_float_rounded_scalars_and_steps_once():
+    from reinforcementlearning4meshgeneration_amd.optim_step import OptimStepSpec
+    ts = _state(7, True)
+    params, opt = _stock(ts, 7, lr=1e-3)
+    spec = OptimStepSpec(critic=opt)
+    plan = spec.prepare("critic")
+    assert all(float(opt.state[q]["step"]) == 6 for q in params)              # prepare steps nothing
+    opt.param_groups[0]["lr"] = 2e-3                                            # read at the call, as SB3 rewrites it
+    S = spec.commit(plan)
+    assert all(float(opt.state[q]["step"]) == 7 for q in params)
+    sc = O.scalars(7, lr=2e-3)
+    assert (S.step_size[0], S.bc2_sqrt[0], S.w1[0], S.beta2[0], S.w2[0], S.eps[0]) == tuple(sc)
+    assert (S.tau, S.one_minus_tau) == (O.f32(0.005), O.f32(1 - 0.005))
+    assert ctypes.sizeof(S) == 4 * (6 * 4 + 2)
+
+
+# ----------------------------------------------------------------------------------------------------------- 4. state created
+def test_state_created_matches_init_group():
+    from reinforcementlearning4meshgeneration_amd.optim_step import OptimStepSpec
+    ts = _state(1, False)
+    mine, opt_m = _stock(ts, 1)
+    theirs, opt_t = _stock(ts, 1)
+    OptimStepSpec(critic=opt_m).prepare("critic")
+    opt_t.step()
+    for a, b in zip(mine, theirs):
+        sa, sb = opt_m.state[a], opt_t.state[b]
+        assert list(sa) == list(sb) == ["step", "exp_avg", "exp_avg_sq"]
+        for k in sa:
+            assert sa[k].dtype == sb[k].dtype and sa[k].device == sb[k].device and sa[k].shape == sb[k].shape, k
+        assert float(sa["step"]) == 0.0 and not sa["exp_avg"].any() and not sa["exp_avg_sq"].any()
+    sd_m, sd_t = opt_m.state_dict(), opt_t.state_dict()
+    assert sd_m["state"].keys() == sd_t["state"].keys() and sd_m["param_groups"] == sd_t["param_groups"]
+    opt_m.step()                                           # and stock torch steps from it
+    assert all(torch.equal(a, b) for a, b in zip(mine, theirs))
+
+
+# ----------------------------------------------------------------------------------------------------------- 5. refusals
+def _opt(n=2, cls=torch.optim.Adam, grads=True, **kw):
+    ps = [torch.zeros(4, 3, requires_grad=True) for _ in range(n)]
+    if grads:
+        for p in ps:
+            p.grad = torch.ones_like(p)
+    return ps, cls(ps, lr=1e-3, **kw)
+
+
+def _refused(fn, *words):
+    with pytest.raises(ValueError) as e:
+        fn()
+    for w in words:
+        assert w in str(e.value), (w, str(e.value))
+
+
+def test_refusals_at_construction_name_what_was_found():
+    from reinforcementlearning4meshgeneration_amd.optim_step import OptimStepSpec
+    S = OptimStepSpec
+    _refused(lambda: S(critic=_opt(cls=torch.optim.SGD)[1]), "torch.optim.sgd.SGD", "not torch.optim.Adam")
+    _refused(lambda: S(critic=_opt(cls=torch.optim.AdamW)[1]), "AdamW", "not torch.optim.Adam")
+    ps, o = _opt()
+    o.add_param_group({"params": [torch.zeros(2, requires_grad=True)]})
+    _refused(lambda: S(critic=o), "2 param groups")
+    for flag in ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay"):
+        _refused(lambda: S(critic=_opt(**{flag: True})[1]), f"{flag}=True")
+    _refused(lambda: S(critic=_opt(weight_decay=0.01)[1]), "weight_decay=0.01")
+    ps, o = _opt()
+    o.param_groups[0]["fused"] = True
+    _refused(lambda: S(critic=o), "fused=True")
+    _refused(lambda: S(critic=torch.optim.Adam([torch.zeros(3, dtype=torch.float64, requires_grad=True)])), "float64", "(3,)")
+    _refused(lambda: S(critic=torch.optim.Adam([torch.zeros(4, 6)[:, ::2].requires_grad_(True)])), "not contiguous", "(4, 3)")
+    a, b = [torch.zeros(3), torch.zeros(2)], [torch.zeros(3)]
+    _refused(lambda: S(polyak=[(a, b)]), "2 parameters but 1 target")
+    _refused(lambda: S(polyak=[([torch.zeros(3, 2)], [torch.zeros(2, 3)])]), "(3, 2)", "(2, 3)")
+    _refused(lambda: S(polyak=[([torch.zeros(3)], [torch.zeros(3, dtype=torch.float16)])]), "float16")
+    for tau in (-0.1, 1.5, float("nan")):
+        _refused(lambda: S(polyak=[([torch.zeros(3)], [torch.zeros(3)])], tau=tau), "tau must lie in [0, 1]")
+    spec = S(polyak=[([torch.zeros(3)], [torch.zeros(3)])], tau=1.0)
+    with pytest.raises(ValueError, match="tau"):
+        spec.tau = 2.0
+    assert spec.tau == 1.0
+    x = torch.zeros(3)
+    _refused(lambda: S(polyak=[([x, x], [torch.zeros(3), torch.zeros(3)])]), "twice")
+    ps, o = _opt()
+    _refused(lambda: S(critic=o, polyak=[([torch.zeros(4, 3)], [ps[0]])]), "target is also a parameter")
+    _refused(lambda: S().prepare("critic"), "no critic optimiser")
+    _refused(lambda: S(critic=o).prepare("actor"), "no actor optimisers")
+    _refused(lambda: S(critic=o).prepare("polyak"), "no Polyak pairs")
+
+
+def test_refusals_at_the_call_name_what_was_found():
+    from reinforcementlearning4meshgeneration_amd.optim_step import OptimStepSpec
+    ps, o = _opt()
+    spec = OptimStepSpec(critic=o)
+    spec.prepare("critic")
+    ps[1].grad = None
+    _refused(lambda: spec.prepare("critic"), "parameter 1", ".grad None")
+    ps[1].grad_dtype = None                                # torch itself refuses the assignment otherwise
+    ps[1].grad = torch.ones(4, 3, dtype=torch.float64)
+    _refused(lambda: spec.prepare("critic"), "parameter 1", "float64")
+    ps[1].grad = torch.ones(4, 6)[:, ::2]
+    _refused(lambda: spec.prepare("critic"), "parameter 1", "not contiguous")
+    ps[1].grad = torch.ones(4, 3)
+    spec.prepare("critic")
+    far = torch.zeros(4, 3).as_subclass(_GradElsewhere)   # torch refuses a gradient on another device too: a stand-in
+    spec_far = OptimStepSpec(critic=torch.optim.Adam([ps[0], far], lr=1e-3))
+    _refused(lambda: spec_far.prepare("critic"), "parameter 1", ".grad is on meta", "the parameter on cpu")
+    o.state[ps[1]]["step"] += 1
+    _refused(lambda: spec.prepare("critic"), "differs between its parameters", "[0.0, 1.0]")
+    o.state[ps[0]]["step"] += 1
+    spec.prepare("critic")
+    o.param_groups[0]["amsgrad"] = True                    # edited after the bind
+    _refused(lambda: spec.prepare("critic"), "amsgrad=True")
+    o.param_groups[0]["amsgrad"] = False
+    o.param_groups[0]["lr"] = torch.tensor(1e-3)
+    _refused(lambda: spec.prepare("critic"), "lr and betas must be Python floats")
+
+
+class _GradElsewhere(torch.Tensor):
+    @property
+    def grad(self):
+        return torch.ones(4, 3, device="meta")
+
+
+class _BN(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.q_networks = torch.nn.ModuleList([torch.nn.Sequential(torch.nn.Linear(21, 8), torch.nn.BatchNorm1d(8), torch.nn.Linear(8, 1))])
+
+
+def _net(sizes):
+    mods = [x for i in range(len(sizes) - 1) for x in (torch.nn.Linear(sizes[i], sizes[i + 1]), torch.nn.ReLU())][:-1]
+    return torch.nn.Sequential(*mods)
+
+
+class _Critic(torch.nn.Module):
+    def __init__(self, h=16, n=2):
+        super().__init__()
+        self.q_networks = torch.nn.ModuleList([_net([21, h, h, 1]) for _ in range(n)])
+
+
+class _SacActor(torch.nn.Module):
+    def __init__(self, h=16):
+        super().__init__()
+        self.latent_pi, self.mu, self.log_std = _net([18, h, h]), torch.nn.Linear(h, 3), torch.nn.Linear(h, 3)
+
+
+class _Td3Actor(torch.nn.Module):
+    def __init__(self, h=16):
+        super().__init__()
+        self.mu = _net([18, h, h, 3])
+
+
+def sb3_stand_in(kind, learned=True):
+    """An SB3-shaped model: modules with .optimizer, critic_target (and actor_target), tau, log_ent_coef."""
+    actor = _SacActor() if kind == "sac" else _Td3Actor()
+    critic = _Critic()
+    actor.optimizer = torch.optim.Adam(actor.parameters(), lr=3e-4)
+    critic.optimizer = torch.optim.Adam(critic.parameters(), lr=3e-4)
+    m = types.SimpleNamespace(actor=actor, critic=critic, critic_target=copy.deepcopy(critic), tau=0.005)
+    if kind == "sac":
+        m.batch_norm_stats, m.batch_norm_stats_target = [], []
+        m.log_ent_coef, m.ent_coef_optimizer = None, None
+        if learned:
+            m.log_ent_coef = torch.zeros(1, requires_grad=True)
+            m.ent_coef_optimizer = torch.optim.Adam([m.log_ent_coef], lr=3e-4)
+    else:
+        m.actor_target = copy.deepcopy(actor)
+        m.critic_batch_norm_stats, m.actor_batch_norm_stats = [], []
+    return m
+
+
+def test_from_sb3_binds_the_two_recipes():
+    from reinforcementlearning4meshgeneration_amd import optim_step as M
+    m = sb3_stand_in("sac")
+    s = M.OptimStepSpec.from_sb3(m)
+    assert s.critic is m.critic.optimizer and s.actor == [m.actor.optimizer, m.ent_coef_optimizer] and s.tau == 0.005
+    cp, tp = list(m.critic.parameters()), list(m.critic_target.parameters())
+    assert len(s.pairs) == 12 and all(a is b and c is d for (a, c), b, d in zip(s.pairs, cp, tp))
+    assert [x.op for x in s.segments("critic")] == [M.ADAM] * 12
+    seg = s.segments("actor_polyak")          # 8 actor tensors, log_ent_coef, then the critics' pairs on their own
+    assert [x.op for x in seg] == [M.ADAM] * 9 + [M.POLYAK] * 12 and [x.block for x in seg[:9]] == [0] * 8 + [1]
+    assert seg[8].param is m.log_ent_coef and seg[9].param is cp[0] and seg[9].target is tp[0]
+    assert [x.op for x in s.segments("actor")] == [M.ADAM] * 9 and [x.op for x in s.segments("polyak")] == [M.POLYAK] * 12
+    s = M.OptimStepSpec.from_sb3(sb3_stand_in("sac", learned=False))
+    assert len(s.actor) == 1
+    m = sb3_stand_in("td3")
+    s = M.OptimStepSpec.from_sb3(m)
+    seg = s.segments("actor_polyak")          # the actor's targets ride with the step; the critics' do not
+    assert [x.op for x in seg] == [M.ADAM_POLYAK] * 6 + [M.POLYAK] * 12
+    assert seg[0].param is next(m.actor.parameters()) and seg[0].target is next(m.actor_target.parameters())
+    assert [x.op for x in s.segments("polyak")] == [M.POLYAK] * 18 and [x.op for x in s.segments("actor")] == [M.ADAM] * 6
+    # refusals
+    m = sb3_stand_in("sac"); m.batch_norm_stats = [torch.zeros(8)]
+    _refused(lambda: M.OptimStepSpec.from_sb3(m), "batch_norm_stats", "1 batch-norm")
+    m = sb3_stand_in("td3"); m.critic_batch_norm_stats = [torch.zeros(8), torch.zeros(8)]
+    _refused(lambda: M.OptimStepSpec.from_sb3(m), "critic_batch_norm_stats", "2 batch-norm")
+    m = sb3_stand_in("sac"); m.critic = _BN(); m.critic.optimizer = torch.optim.Adam(m.critic.parameters()); m.critic_target = _BN()
+    _refused(lambda: M.OptimStepSpec.from_sb3(m), "running_mean", "batch norm")
+    _refused(lambda: M.OptimStepSpec.from_sb3(types.SimpleNamespace(policy=None)), "not an SB3 SAC, TD3 or DDPG model")
+    m = sb3_stand_in("sac"); m.critic.optimizer = torch.optim.SGD(m.critic.parameters(), lr=0.1)
+    _refused(lambda: M.OptimStepSpec.from_sb3(m), "the critic optimiser", "SGD")
+    m = sb3_stand_in("sac"); m.critic_target = _Critic(n=1)
+    _refused(lambda: M.OptimStepSpec.from_sb3(m), "12 parameters but 6 target")
+    m = sb3_stand_in("sac"); m.tau = 1.2
+    _refused(lambda: M.OptimStepSpec.from_sb3(m), "tau must lie in [0, 1]")
+
+
+# ----------------------------------------------------------------------------------------------------------- 6. segment table
+def test_segment_table_covers_each_element_exactly_once():
+    from reinforcementlearning4meshgeneration_amd import optim_step as M
+    params = [torch.zeros(s, requires_grad=True) for s in O.SHAPES]
+    opt = torch.optim.Adam(params, lr=O.LR)
+    buf = O.flat_grads(torch, params, "cpu", lead=1)
+    tgt = [torch.zeros(s) for s in O.SHAPES]
+    spec = M.OptimStepSpec(actor=[opt], polyak=[(params, tgt)], tau=0.005)
+    plan = spec.prepare("actor_polyak")
+    rows = plan.rows
+    assert [r.seg.op for r in rows] == [M.ADAM_POLYAK] * len(O.SHAPES) and [r.seg.n for r in rows] == [1, 3, 63, 64, 65, 4097, 2688]
+    base = buf.data_ptr()
+    for r in rows:                               # the views sit where the flat buffer puts them, whatever their alignment
+        assert r.pointers[1] == r.tensors[1].data_ptr() and (r.pointers[1] - base) % 4 == 0
+        assert r.vec == int(all(q % 16 == 0 for q in r.pointers))
+    assert any((r.pointers[1] % 16) != 0 for r in rows) and not all(r.vec for r in rows)
+    jobs = M.OptimStepSpec.jobs(rows)
+    assert len(jobs) == sum(-(-r.seg.n // M.CHUNK) for r in rows) and all(first % M.CHUNK == 0 for _, first in jobs)
+    for force_vec in (None, 0, 1):               # both paths of the kernel on every size
+        seen = [np.zeros(r.seg.n, np.int64) for r in rows]
+        for i, first in jobs:
+            row = rows[i] if force_vec is None else types.SimpleNamespace(seg=rows[i].seg, vec=force_vec)
+            for tid in range(M.THREADS):
+                for e in M.OptimStepSpec.thread_elements(row, first, tid):
+                    assert first <= e < min(first + M.CHUNK, row.seg.n)
+                    seen[i][e] += 1
+        assert all((s == 1).all() for s in seen), force_vec
+    assert plan.key() == spec.prepare("actor_polyak").key()           # unchanged tensors: no new upload
+    params[2].grad = torch.zeros(63)
+    assert plan.key() != spec.prepare("actor_polyak").key()
+    opt.load_state_dict(copy.deepcopy(opt.state_dict()))               # replaces the state tensors
+    params[2].grad = plan.rows[2].tensors[1]
+    assert plan.key() != spec.prepare("actor_polyak").key()
+
+
+# ----------------------------------------------------------------------------------------------------------- 7. packaging
+def test_exported_lazily_declared_and_built():
+    import os
+    import re
+
+    import reinforcementlearning4meshgeneration_amd as pkg
+    from reinforcementlearning4meshgeneration_amd import _capi
+    assert pkg.FusedOptimStep.__name__ == "FusedOptimStep" and pkg.OptimStepSpec.__name__ == "OptimStepSpec"
+    assert "FusedOptimStep" in pkg.__all__ and "OptimStepSpec" in pkg.__all__
+    assert sorted(_capi.EXPORTS_OPTIM) == sorted("meshenv_optim_" + s for s in ("create", "destroy", "set_stream", "last_error", "bind", "step"))
+    assert not set(_capi.EXPORTS_OPTIM) & set(_capi.EXPORTS)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "meshenv_optim.h")).read()
+    assert sorted(set(re.findall(r"\b(meshenv_optim_[a-z_]+)\s*\(", header))) == sorted(_capi.EXPORTS_OPTIM)
+    L = _capi.load()
+    for name in _capi.EXPORTS_OPTIM:
+        assert hasattr(L, name), name
+    from reinforcementlearning4meshgeneration_amd import build
+    assert "meshenv_optim.h" in build.PUBLIC_HEADERS
+
+
+def test_no_cpu_fallback():
+    from reinforcementlearning4meshgeneration_amd import _capi
+    from reinforcementlearning4meshgeneration_amd.optim_step import FusedOptimStep, OptimStepSpec
+    spec = OptimStepSpec(critic=_opt()[1])
+    with pytest.raises(ValueError, match="is on cpu"):
+        spec.check_device(torch.device("cuda", 0))
+    if not torch.cuda.is_available():
+        with pytest.raises(_capi.MeshEnvError):
+            FusedOptimStep(spec)

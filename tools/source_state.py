@@ -1,4 +1,4 @@
-"""What library a profile describes: sha256 over csrc/ + include/meshenv.h, the library's own hash, and whether the library
+"""What library a profile describes: sha256 over csrc/ + include/meshenv.h + include/meshenv_optim.h, the library's own hash, and whether the library
 is older than its sources.  `python tools/source_state.py` prints it as JSON; `--require-fresh` exits 1 when the shipped .so is
 older than any source (tools/profile_round.sh / profile_set.sh refuse to profile such a library).  tools/summarize_profile.py and
 summarize_set.py compare the recorded source hash with the working tree and, where .git exists, refuse to summarise when
@@ -8,10 +8,11 @@ import hashlib, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "reinforcementlearning4meshgeneration_amd")
 CSRC = os.path.join(PKG, "csrc")
+PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h"]      # build.py's list
 
 
 def source_files():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join(ROOT, "include", "meshenv.h")]
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join(ROOT, "include", h) for h in PUBLIC_HEADERS]
 
 
 def source_hash():
@@ -42,7 +43,7 @@ def git_state():
     if not os.path.isdir(os.path.join(ROOT, ".git")):
         return None, None
     head = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip()
-    clean = subprocess.run(["git", "-C", ROOT, "diff", "--quiet", "HEAD", "--", os.path.relpath(CSRC, ROOT), "include/meshenv.h"]).returncode == 0
+    clean = subprocess.run(["git", "-C", ROOT, "diff", "--quiet", "HEAD", "--", os.path.relpath(CSRC, ROOT), *["include/" + h for h in PUBLIC_HEADERS]]).returncode == 0
     return head, clean
 
 
