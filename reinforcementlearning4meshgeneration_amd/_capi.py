@@ -174,19 +174,21 @@ def load():
     L.meshenv_selftest.restype = C.c_int
     L.meshenv_set_packed_output.argtypes = [vp, vp]
     L.meshenv_set_packed_output.restype = C.c_int
-    L.meshenv_actor_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
-    L.meshenv_actor_destroy.argtypes = [vp]
-    L.meshenv_actor_destroy.restype = None
-    L.meshenv_actor_set_stream.argtypes = [vp, vp]
+    # the handle families: <prefix>_create(device, stream, <extra>, out), _destroy, _set_stream and (all but the actor) _last_error
+    f32 = C.c_float
+    for prefix, extra, has_last_error in (("meshenv_actor", [], False), ("meshenv_policy", [], True),
+                                          ("meshenv_target", [C.c_int, f32, f32, f32, f32], True),
+                                          ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
+                                          ("meshenv_optim", [], True)):
+        fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
+        fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
+        fn("destroy").argtypes, fn("destroy").restype = [vp], None
+        fn("set_stream").argtypes, fn("set_stream").restype = [vp, vp], C.c_int
+        if has_last_error:
+            fn("last_error").argtypes, fn("last_error").restype = [vp], C.c_char_p
     L.meshenv_actor_load.argtypes = [vp] + [vp] * 12
     L.meshenv_actor_forward.argtypes = [vp, C.c_int, vp, vp, vp]
     L.meshenv_actor_sample.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp]
-    L.meshenv_policy_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
-    L.meshenv_policy_destroy.argtypes = [vp]
-    L.meshenv_policy_destroy.restype = None
-    L.meshenv_policy_set_stream.argtypes = [vp, vp]
-    L.meshenv_policy_last_error.argtypes = [vp]
-    L.meshenv_policy_last_error.restype = C.c_char_p
     L.meshenv_policy_load.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 15
     L.meshenv_policy_forward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
     L.meshenv_step_policy_multi.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 11 + [C.c_int]
@@ -205,55 +207,19 @@ def load():
     L.meshenv_replay_add.restype = C.c_int
     L.meshenv_replay_sample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 9
     L.meshenv_replay_sample.restype = C.c_int
-    L.meshenv_target_create.argtypes = [C.c_int, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(vp)]
-    L.meshenv_target_destroy.argtypes = [vp]
-    L.meshenv_target_destroy.restype = None
-    L.meshenv_target_set_stream.argtypes = [vp, vp]
-    L.meshenv_target_last_error.argtypes = [vp]
-    L.meshenv_target_last_error.restype = C.c_char_p
     L.meshenv_target_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, vp]
     L.meshenv_target_refresh.argtypes = [vp]
     L.meshenv_target_forward.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 6
-    for name in ("meshenv_target_create", "meshenv_target_set_stream", "meshenv_target_bind", "meshenv_target_refresh",
-                 "meshenv_target_forward"):
-        getattr(L, name).restype = C.c_int
-    L.meshenv_critic_grad_create.argtypes = [C.c_int, vp, C.c_int, C.POINTER(vp)]
-    L.meshenv_critic_grad_destroy.argtypes = [vp]
-    L.meshenv_critic_grad_destroy.restype = None
-    L.meshenv_critic_grad_set_stream.argtypes = [vp, vp]
-    L.meshenv_critic_grad_last_error.argtypes = [vp]
-    L.meshenv_critic_grad_last_error.restype = C.c_char_p
     L.meshenv_critic_grad_bind.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, vp, C.c_int64]
     L.meshenv_critic_grad_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
-    for name in ("meshenv_critic_grad_create", "meshenv_critic_grad_set_stream", "meshenv_critic_grad_bind",
-                 "meshenv_critic_grad_backward"):
-        getattr(L, name).restype = C.c_int
-    L.meshenv_actor_grad_create.argtypes = [C.c_int, vp, C.c_float, C.c_float, C.POINTER(vp)]
-    L.meshenv_actor_grad_destroy.argtypes = [vp]
-    L.meshenv_actor_grad_destroy.restype = None
-    L.meshenv_actor_grad_set_stream.argtypes = [vp, vp]
-    L.meshenv_actor_grad_last_error.argtypes = [vp]
-    L.meshenv_actor_grad_last_error.restype = C.c_char_p
     L.meshenv_actor_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, vp, vp, C.c_int64]
     L.meshenv_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp), C.POINTER(vp)]
-    for name in ("meshenv_actor_grad_create", "meshenv_actor_grad_set_stream", "meshenv_actor_grad_bind",
-                 "meshenv_actor_grad_backward"):
-        getattr(L, name).restype = C.c_int
-    L.meshenv_optim_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
-    L.meshenv_optim_destroy.argtypes = [vp]
-    L.meshenv_optim_destroy.restype = None
-    L.meshenv_optim_set_stream.argtypes = [vp, vp]
-    L.meshenv_optim_last_error.argtypes = [vp]
-    L.meshenv_optim_last_error.restype = C.c_char_p
     L.meshenv_optim_bind.argtypes = [vp, C.c_int, C.c_int] + [C.POINTER(vp)] * 5 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 3
     L.meshenv_optim_step.argtypes = [vp, C.c_int, C.POINTER(MeshOptimScalars)]
-    for name in ("meshenv_optim_create", "meshenv_optim_set_stream", "meshenv_optim_bind", "meshenv_optim_step"):
-        getattr(L, name).restype = C.c_int
-    for name in ("meshenv_policy_create", "meshenv_policy_set_stream", "meshenv_policy_load", "meshenv_policy_forward",
-                 "meshenv_step_policy_multi"):
-        getattr(L, name).restype = C.c_int
-    for name in ("meshenv_actor_create", "meshenv_actor_set_stream", "meshenv_actor_load", "meshenv_actor_forward",
-                 "meshenv_actor_sample"):
+    for name in ("meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
+                 "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
+                 "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",
+                 "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_reset_static", "meshenv_move", "meshenv_get_not_valid", "meshenv_set_stream", "meshenv_num_envs", "meshenv_max_ring", "meshenv_reset", "meshenv_step",
                  "meshenv_rollout", "meshenv_get_status", "meshenv_get_state", "meshenv_get_elements",

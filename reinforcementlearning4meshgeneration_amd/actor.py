@@ -10,24 +10,18 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import sb3_nets
+from ._handle import Handle
 from .vec_env import ACTION_HIGH, ACTION_LOW
 
 
-class FusedActor:
+class FusedActor(Handle):
+    PREFIX = "meshenv_actor"
+    LAST_ERROR = "meshenv_last_error"
+    HAS_LAST_ERROR = False
+
     def __init__(self, device: int = 0):
-        import torch
-        self._torch = torch
-        self._L = _capi.load()
-        if not torch.cuda.is_available():
-            raise _capi.MeshEnvError("FusedActor needs a ROCm GPU")
-        self.device = torch.device("cuda", device)
-        self._h = C.c_void_p()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.meshenv_actor_create(device, C.c_void_p(stream), C.byref(self._h))
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_actor_create failed ({rc}): {self._L.meshenv_last_error(None).decode()}")
-        self._stream = stream
+        super().__init__(device)
 
     @classmethod
     def from_torch(cls, linears, mu, log_std, device: int = 0, low=ACTION_LOW, high=ACTION_HIGH):
@@ -40,9 +34,7 @@ class FusedActor:
         shapes = [a.shape for a in arrs]
         assert shapes == [(128, 18), (128,), (128, 128), (128,), (128, 128), (128,), (3, 128), (3,), (3, 128), (3,)], shapes
         arrs += [np.ascontiguousarray(low, np.float32), np.ascontiguousarray(high, np.float32)]
-        rc = self._L.meshenv_actor_load(self._h, *[a.ctypes.data for a in arrs])
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_actor_load failed ({rc})")
+        self._check(self._L.meshenv_actor_load(self._h, *[a.ctypes.data for a in arrs]), "meshenv_actor_load")
         return self
 
     @classmethod
@@ -57,17 +49,11 @@ class FusedActor:
             actor = getattr(actor, "actor", actor)
         if not hasattr(actor, "latent_pi") or not hasattr(actor, "mu") or not hasattr(actor, "log_std"):
             raise ValueError("not an SB3 SAC actor (latent_pi, mu, log_std)")
-        if getattr(actor, "use_sde", False):
-            raise ValueError("gSDE SAC actors are not supported (the fused actor is the squashed Gaussian of MlpPolicy)")
-        fe = getattr(actor, "features_extractor", None)
-        if fe is not None and type(fe).__name__ != "FlattenExtractor":
-            raise ValueError(f"features_extractor is {type(fe).__name__}; only FlattenExtractor is supported")
-        mods = list(actor.latent_pi)
-        names = [type(m).__name__ for m in mods]
-        if names != ["Linear", "ReLU"] * 3:
-            raise ValueError(f"actor.latent_pi is {names}; the fused actor is MlpPolicy's ReLU [128, 128, 128] "
+        linears = sb3_nets.sac_actor(actor)
+        if len(linears) != 3:
+            raise ValueError(f"actor.latent_pi has {len(linears)} Linear layers; the fused actor is MlpPolicy's ReLU [128, 128, 128] "
                              "(rl/baselines/RL_Mesh.py:183-196)")
-        return cls.from_torch([mods[0], mods[2], mods[4]], actor.mu, actor.log_std, device=device, low=low, high=high)
+        return cls.from_torch(linears, actor.mu, actor.log_std, device=device, low=low, high=high)
 
     def forward(self, obs, noise=None, out=None):
         """obs: float32 CUDA [n, 18]; noise: float32 CUDA [n, 3] of N(0,1) samples or None (deterministic).
@@ -76,14 +62,10 @@ class FusedActor:
         n = obs.shape[0]
         if out is None:
             out = t.empty((n, 3), dtype=t.float32, device=self.device)
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        if stream != self._stream:
-            self._L.meshenv_actor_set_stream(self._h, C.c_void_p(stream))
-            self._stream = stream
+        self._bind_stream()
         rc = self._L.meshenv_actor_forward(self._h, n, obs.data_ptr(), noise.data_ptr() if noise is not None else None,
                                            out.data_ptr())
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_actor_forward failed ({rc})")
+        self._check(rc, "meshenv_actor_forward")
         return out
 
     def sample(self, obs, seed: int, counter: int, out=None, eps_out=None):
@@ -94,24 +76,9 @@ class FusedActor:
         n = obs.shape[0]
         if out is None:
             out = t.empty((n, 3), dtype=t.float32, device=self.device)
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        if stream != self._stream:
-            self._L.meshenv_actor_set_stream(self._h, C.c_void_p(stream))
-            self._stream = stream
+        self._bind_stream()
         rc = self._L.meshenv_actor_sample(self._h, n, obs.data_ptr(), C.c_uint64(seed & (2 ** 64 - 1)),
                                           C.c_uint64(counter & (2 ** 64 - 1)), out.data_ptr(),
                                           eps_out.data_ptr() if eps_out is not None else None)
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_actor_sample failed ({rc})")
+        self._check(rc, "meshenv_actor_sample")
         return out
-
-    def close(self):
-        if self._h:
-            self._L.meshenv_actor_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

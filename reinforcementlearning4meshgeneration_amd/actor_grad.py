@@ -27,14 +27,12 @@ import ctypes as C
 from dataclasses import dataclass, field
 from typing import List, Optional
 
-from . import _capi
-from .policy import _sequential
-from .td_target import ACT_DIM, KIND_SAC, OBS_DIM, SUPPORTED, _critic, _flatten_only, _mlp, _param
+from . import sb3_nets as N
+from ._handle import GradBuffer, Handle
+from .sb3_nets import ACT_DIM, KIND_SAC, OBS_DIM
 
 HIDDEN = 128
 PHILOX_TAG = 3                     # k_actor_grad's own stream (rollout noise 0, replay draw 1, TD target 2)
-SUPPORTED_ACTOR = ("SAC only: actor ReLU [128, 128, 128] with mu and log_std heads, twin critics ReLU [128, 128, 128]; 18 "
-                   "observations, 3 actions, critic input cat(obs, action) = 21, float32")
 
 
 @dataclass
@@ -79,22 +77,9 @@ class ActorGradSpec:
     # ---------------------------------------------------------------- constructors
     @classmethod
     def sac(cls, actor_layers, mu, log_std, q1, q2, log_ent_coef=None, ent_coef=None, target_entropy=-3.0) -> "ActorGradSpec":
-        if (log_ent_coef is None) == (ent_coef is None):
-            raise ValueError("SAC needs exactly one of log_ent_coef (the learned tensor) and ent_coef (a fixed float)")
-        te = float(target_entropy)
-        if not te == te or abs(te) == float("inf"):
-            raise ValueError(f"target_entropy must be finite, got {target_entropy!r}")
-        actor = _mlp(actor_layers, [("mu", ACT_DIM, mu), ("log_std", ACT_DIM, log_std)], OBS_DIM, KIND_SAC, "actor")
-        spec = cls(actor, _critic(q1, KIND_SAC, "q_networks[0]"), _critic(q2, KIND_SAC, "q_networks[1]"), target_entropy=te)
-        if log_ent_coef is not None:
-            if not hasattr(log_ent_coef, "numel") or log_ent_coef.numel() != 1:
-                raise ValueError(f"log_ent_coef must be a tensor of one element, got {log_ent_coef!r}")
-            spec.log_ent_coef = _param(log_ent_coef, "log_ent_coef", tuple(log_ent_coef.shape))
-        else:
-            spec.ent_coef = float(ent_coef)
-            if not spec.ent_coef == spec.ent_coef or abs(spec.ent_coef) == float("inf"):
-                raise ValueError(f"ent_coef must be finite, got {ent_coef!r}")
-        return spec
+        lec, fixed = N.ent_coef(log_ent_coef, ent_coef)
+        return cls(N.sac_actor_params(actor_layers, mu, log_std), *N.twin_params(KIND_SAC, q1, q2), log_ent_coef=lec, ent_coef=fixed,
+                   target_entropy=N.finite(target_entropy, "target_entropy"))
 
     @classmethod
     def from_sb3(cls, model) -> "ActorGradSpec":
@@ -106,63 +91,26 @@ class ActorGradSpec:
                 raise ValueError(f"{type(model).__name__} is a TD3 / DDPG model (a deterministic actor without latent_pi): "
                                  "not yet: SAC only")
             raise ValueError(f"{type(model).__name__} has no actor.latent_pi: not an SB3 SAC model")
-        critic = getattr(model, "critic", None)
-        if critic is None or not hasattr(critic, "q_networks"):
-            raise ValueError(f"{type(model).__name__} has no critic.q_networks: not an SB3 SAC model")
-        qs = list(critic.q_networks)
-        n_critics = int(getattr(critic, "n_critics", len(qs)))
-        if n_critics != 2 or len(qs) != 2:
-            raise ValueError(f"n_critics = {n_critics}; the twin critics of SAC (n_critics = 2) are supported")
-        _flatten_only(critic, "critic", shared=bool(getattr(critic, "share_features_extractor", False)))
-        _flatten_only(actor, "actor")
-        if getattr(actor, "use_sde", False):
-            raise ValueError("use_sde=True (gSDE actor) is not supported; " + SUPPORTED_ACTOR)
-        linears, acts = _sequential(actor.latent_pi)
-        if acts - {"relu"}:
-            raise ValueError(f"actor.latent_pi: activations {sorted(acts)}; supported: {SUPPORTED}")
-        if type(actor.log_std).__name__ != "Linear":
-            raise ValueError(f"actor.log_std is {type(actor.log_std).__name__}, not a Linear head (gSDE?); " + SUPPORTED_ACTOR)
+        qs = N.twin_critics(model, "critic", who="SAC")
         te = getattr(model, "target_entropy", None)
         if te is None or isinstance(te, str):
             raise ValueError(f"model.target_entropy is {te!r}; SB3 sets it to a float in _setup_model")
-        lec = getattr(model, "log_ent_coef", None)
-        if lec is not None:
-            return cls.sac(linears, actor.mu, actor.log_std, qs[0], qs[1], log_ent_coef=lec, target_entropy=float(te))
-        fixed = getattr(model, "ent_coef_tensor", None)
-        if fixed is None:
-            raise ValueError("the SAC model has neither log_ent_coef nor ent_coef_tensor")
-        return cls.sac(linears, actor.mu, actor.log_std, qs[0], qs[1], ent_coef=float(fixed), target_entropy=float(te))
+        return cls.sac(N.sac_actor(actor), actor.mu, actor.log_std, qs[0], qs[1], target_entropy=float(te), **N.model_ent_coef(model))
 
     def check_device(self, device) -> None:
         """Every bound tensor lives on `device` (a torch.device): the kernel reads them through raw pointers."""
-        for x in self.tensors():
-            if x.device != device:
-                raise ValueError(f"a parameter of shape {tuple(x.shape)} is on {x.device}; FusedActorGrad binds float32 "
-                                 f"contiguous CUDA tensors on {device}")
+        N.check_device(self.tensors(), device, "FusedActorGrad")
 
 
-class FusedActorGrad:
+class FusedActorGrad(GradBuffer, Handle):
     """An ActorGradSpec bound on one GPU.  backward() returns (actor_loss, ent_coef_loss) (0-dim float32 CUDA tensors; the
     second is None with a fixed ent_coef) and overwrites p.grad of the actor's parameters and of log_ent_coef."""
+    PREFIX = "meshenv_actor_grad"
 
     def __init__(self, spec: ActorGradSpec, device: int = 0):
-        import torch
-        self._torch = torch
-        self._L = _capi.load()
-        if not torch.cuda.is_available():
-            raise _capi.MeshEnvError("FusedActorGrad needs a ROCm GPU")
         self.spec = spec
-        self.device = torch.device("cuda", device)
-        spec.check_device(self.device)
-        self._h = C.c_void_p()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.meshenv_actor_grad_create(device, C.c_void_p(stream), spec.ent_coef, spec.target_entropy, C.byref(self._h))
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_actor_grad_create failed ({rc}): "
-                                     f"{self._L.meshenv_actor_grad_last_error(None).decode()}")
-        self._stream = stream
-        self.grad_buffer = torch.zeros(spec.n_grad, dtype=torch.float32, device=self.device)
-        self._views = []
+        super().__init__(device, spec.ent_coef, spec.target_entropy, check_device=spec.check_device)
+        self._alloc_grads()
         self.bind()
 
     kind = "sac"
@@ -175,47 +123,17 @@ class FusedActorGrad:
     def from_sb3(cls, model, device: int = 0):
         return cls(ActorGradSpec.from_sb3(model), device)
 
-    # ---------------------------------------------------------------- plumbing
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self._L.meshenv_actor_grad_last_error(self._h)
-            raise _capi.MeshEnvError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def _bind_stream(self):
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        if stream != self._stream:
-            self._check(self._L.meshenv_actor_grad_set_stream(self._h, C.c_void_p(stream)), "meshenv_actor_grad_set_stream")
-            self._stream = stream
-
     def bind(self) -> None:
         """Record the parameters' device pointers again: after anything that reallocates them (``.to()``; optimisers and
         ``load_state_dict`` write in place and need no new bind)."""
         s = self.spec
         s.check_device(self.device)
-        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])   # noqa: E731
+        arr = self._ptrs
         lec = s.log_ent_coef.data_ptr() if s.log_ent_coef is not None else None
         rc = self._L.meshenv_actor_grad_bind(self._h, arr(s.actor), len(s.actor), arr(s.q1), arr(s.q2), len(s.q1), lec,
                                              self.grad_buffer.data_ptr(), s.n_grad)
         self._check(rc, "meshenv_actor_grad_bind")
-        self._views = [(p, self.grad_buffer[at:at + p.numel()].view(p.shape)) for p, at in s.offsets()]
-
-    def _attach(self):
-        """p.grad of every parameter is its view of the gradient buffer: whatever it held (None, a tensor of the caller's)
-        is replaced; host-side pointer comparisons only."""
-        for p, v in self._views:
-            g = p.grad
-            if g is None or g.data_ptr() != v.data_ptr() or g.shape != v.shape or g.dtype != v.dtype or not g.is_contiguous():
-                p.grad = v
-
-    def _f32(self, x, name, shape):
-        t = self._torch
-        if x.requires_grad:
-            x = x.detach()
-        if x.dtype != t.float32 or not x.is_contiguous() or x.device != self.device:
-            x = x.to(device=self.device, dtype=t.float32).contiguous()
-        if tuple(x.shape) not in shape:
-            raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shape)}, got {tuple(x.shape)}")
-        return x
+        self._view_grads()
 
     # ---------------------------------------------------------------- public
     def backward(self, samples=None, *, observations=None, noise=None, seed=None, counter=None, return_parts: bool = False):
@@ -255,7 +173,7 @@ class FusedActorGrad:
             parts = dict(actions_pi=t.empty((B, ACT_DIM), **f32), log_prob=t.empty(B, **f32), q1_pi=t.empty(B, **f32),
                          q2_pi=t.empty(B, **f32), dq_da=t.empty((B, ACT_DIM), **f32), d_mu=t.empty((B, ACT_DIM), **f32),
                          d_log_std=t.empty((B, ACT_DIM), **f32))
-            arr = lambda ts: (C.c_void_p * len(ts))(*[x.data_ptr() for x in ts])   # noqa: E731
+            arr = self._ptrs
             pp = arr(list(parts.values()))
             for k in ("acts", "acts1", "acts2"):
                 parts[k] = [t.empty((B, HIDDEN), **f32) for _ in range(3)]
@@ -271,14 +189,3 @@ class FusedActorGrad:
         self._check(rc, "meshenv_actor_grad_backward")
         out = (losses[0], losses[1] if self.spec.log_ent_coef is not None else None)
         return (*out, parts) if return_parts else out
-
-    def close(self):
-        if self._h:
-            self._L.meshenv_actor_grad_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -13,27 +13,12 @@ are OVERWRITTEN by every call.  ``CriticGradSpec`` is the host half (kind, the p
 needed)."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass, field
 from typing import List
 
-from . import _capi
-from .td_target import ACT_DIM, HIDDEN, KIND_SAC, KIND_TD3, OBS_DIM, _critic, _flatten_only
-from .policy import _sequential
-
-SUPPORTED_CRITICS = ("twin critics ReLU [128, 128, 128] (SAC) or ReLU [256, 256] (TD3); 18 observations, 3 actions, critic input "
-                     "cat(obs, action) = 21, float32")
-
-
-def _kind_of(q, what):
-    """SAC or TD3 from the widths of a q_network (the refusals of a shape that is neither come from td_target._critic)."""
-    linears, _ = _sequential(q)
-    widths = [tuple(getattr(l.weight, "shape", ()))[:1] for l in linears[:-1]]
-    if widths == [(256,)] * 2:
-        return KIND_TD3
-    if widths == [(128,)] * 3:
-        return KIND_SAC
-    raise ValueError(f"{what}: hidden layers {[w[0] if w else None for w in widths]}; supported: {SUPPORTED_CRITICS}")
+from . import sb3_nets as N
+from ._handle import GradBuffer, Handle
+from .sb3_nets import ACT_DIM, HIDDEN, KIND_SAC, KIND_TD3, OBS_DIM
 
 
 @dataclass
@@ -76,7 +61,7 @@ class CriticGradSpec:
     # ---------------------------------------------------------------- constructors
     @classmethod
     def _twin(cls, kind, q1, q2) -> "CriticGradSpec":
-        return cls(kind, _critic(q1, kind, "q_networks[0]"), _critic(q2, kind, "q_networks[1]"))
+        return cls(kind, *N.twin_params(kind, q1, q2))
 
     @classmethod
     def sac(cls, q1, q2) -> "CriticGradSpec":
@@ -89,47 +74,23 @@ class CriticGradSpec:
     @classmethod
     def from_sb3(cls, model) -> "CriticGradSpec":
         """Duck-typed on SB3 2.x's SAC / TD3: ``model.critic.q_networks`` (the live critics, not ``critic_target``)."""
-        critic = getattr(model, "critic", None)
-        if critic is None or not hasattr(critic, "q_networks"):
-            raise ValueError(f"{type(model).__name__} has no critic.q_networks: not an SB3 SAC or TD3 model")
-        qs = list(critic.q_networks)
-        n_critics = int(getattr(critic, "n_critics", len(qs)))
-        if n_critics != 2 or len(qs) != 2:
-            ddpg = " (DDPG: one critic)" if n_critics == 1 else ""
-            raise ValueError(f"n_critics = {n_critics}{ddpg}; the twin critics of SAC / TD3 (n_critics = 2) are supported")
-        _flatten_only(critic, "critic", shared=bool(getattr(critic, "share_features_extractor", False)))
-        return cls._twin(_kind_of(qs[0], "q_networks[0]"), qs[0], qs[1])
+        qs = N.twin_critics(model, "critic", ddpg=True)
+        return cls._twin(N.critic_kind(qs[0], "q_networks[0]"), qs[0], qs[1])
 
     def check_device(self, device) -> None:
         """Every bound tensor lives on `device` (a torch.device): the kernel reads them through raw pointers."""
-        for x in self.tensors():
-            if x.device != device:
-                raise ValueError(f"a parameter of shape {tuple(x.shape)} is on {x.device}; FusedCriticGrad binds float32 "
-                                 f"contiguous CUDA tensors on {device}")
+        N.check_device(self.tensors(), device, "FusedCriticGrad")
 
 
-class FusedCriticGrad:
+class FusedCriticGrad(GradBuffer, Handle):
     """A CriticGradSpec bound on one GPU.  backward() returns critic_loss (0-dim float32 CUDA tensor) and overwrites p.grad
     of every bound parameter."""
+    PREFIX = "meshenv_critic_grad"
 
     def __init__(self, spec: CriticGradSpec, device: int = 0):
-        import torch
-        self._torch = torch
-        self._L = _capi.load()
-        if not torch.cuda.is_available():
-            raise _capi.MeshEnvError("FusedCriticGrad needs a ROCm GPU")
         self.spec = spec
-        self.device = torch.device("cuda", device)
-        spec.check_device(self.device)
-        self._h = C.c_void_p()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.meshenv_critic_grad_create(device, C.c_void_p(stream), spec.kind, C.byref(self._h))
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_critic_grad_create failed ({rc}): "
-                                     f"{self._L.meshenv_critic_grad_last_error(None).decode()}")
-        self._stream = stream
-        self.grad_buffer = torch.zeros(spec.n_grad, dtype=torch.float32, device=self.device)
-        self._views = []
+        super().__init__(device, spec.kind, check_device=spec.check_device)
+        self._alloc_grads()
         self.bind()
 
     @property
@@ -148,45 +109,15 @@ class FusedCriticGrad:
     def from_sb3(cls, model, device: int = 0):
         return cls(CriticGradSpec.from_sb3(model), device)
 
-    # ---------------------------------------------------------------- plumbing
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self._L.meshenv_critic_grad_last_error(self._h)
-            raise _capi.MeshEnvError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def _bind_stream(self):
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        if stream != self._stream:
-            self._check(self._L.meshenv_critic_grad_set_stream(self._h, C.c_void_p(stream)), "meshenv_critic_grad_set_stream")
-            self._stream = stream
-
     def bind(self) -> None:
         """Record the parameters' device pointers again: after anything that reallocates them (``.to()``; optimisers and
         ``load_state_dict`` write in place and need no new bind)."""
         s = self.spec
         s.check_device(self.device)
-        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])   # noqa: E731
-        rc = self._L.meshenv_critic_grad_bind(self._h, arr(s.q1), arr(s.q2), len(s.q1), self.grad_buffer.data_ptr(), s.n_grad)
+        rc = self._L.meshenv_critic_grad_bind(self._h, self._ptrs(s.q1), self._ptrs(s.q2), len(s.q1), self.grad_buffer.data_ptr(),
+                                              s.n_grad)
         self._check(rc, "meshenv_critic_grad_bind")
-        self._views = [(p, self.grad_buffer[at:at + p.numel()].view(p.shape)) for p, at in s.offsets()]
-
-    def _attach(self):
-        """p.grad of every parameter is its view of the gradient buffer: whatever it held (None, a tensor of the caller's)
-        is replaced; host-side pointer comparisons only."""
-        for p, v in self._views:
-            g = p.grad
-            if g is None or g.data_ptr() != v.data_ptr() or g.shape != v.shape or g.dtype != v.dtype or not g.is_contiguous():
-                p.grad = v
-
-    def _f32(self, x, name, shape):
-        t = self._torch
-        if x.requires_grad:
-            x = x.detach()
-        if x.dtype != t.float32 or not x.is_contiguous() or x.device != self.device:
-            x = x.to(device=self.device, dtype=t.float32).contiguous()
-        if tuple(x.shape) not in shape:
-            raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shape)}, got {tuple(x.shape)}")
-        return x
+        self._view_grads()
 
     # ---------------------------------------------------------------- public
     def backward(self, samples=None, target_q_values=None, *, observations=None, actions=None, return_parts: bool = False):
@@ -214,8 +145,7 @@ class FusedCriticGrad:
             H, NL = HIDDEN[self.spec.kind]
             parts = dict(q1=t.empty(B, **f32), q2=t.empty(B, **f32), acts1=[t.empty((B, H), **f32) for _ in range(NL)],
                          acts2=[t.empty((B, H), **f32) for _ in range(NL)])
-            arr = lambda ts: (C.c_void_p * len(ts))(*[x.data_ptr() for x in ts])   # noqa: E731
-            a1, a2 = arr(parts["acts1"]), arr(parts["acts2"])
+            a1, a2 = self._ptrs(parts["acts1"]), self._ptrs(parts["acts2"])
         self._attach()
         self._bind_stream()
         rc = self._L.meshenv_critic_grad_backward(
@@ -223,14 +153,3 @@ class FusedCriticGrad:
             parts["q1"].data_ptr() if parts else None, parts["q2"].data_ptr() if parts else None, a1, a2)
         self._check(rc, "meshenv_critic_grad_backward")
         return (loss, parts) if return_parts else loss
-
-    def close(self):
-        if self._h:
-            self._L.meshenv_critic_grad_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -232,6 +232,81 @@ int fail_arg(MeshEnv *h, const char *msg)
     return MESHENV_E_ARG;
 }
 
+// ---- what the handles of the fused networks share (MeshActor, MeshPolicy, MeshTarget, MeshCriticGrad, MeshActorGrad, MeshOptim)
+struct HandleBase {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+};
+
+template <typename H>
+int fail(H *h, int rc, const std::string &msg)
+{
+    h->err = msg;
+    return rc;
+}
+
+// The prologue of every *_create: a new H on `device` and `stream` in *out.  `refusal`: what the caller found wrong with its
+// own arguments, if anything.  A failed create leaves its message where *_last_error(NULL) reads it.
+template <typename H>
+int create_handle(const char *fn, int device, void *stream, H **out, const std::string &refusal = std::string())
+{
+    if (!out) return MESHENV_E_ARG;
+    *out = nullptr;
+    if (!refusal.empty()) {
+        g_create_error = std::string(fn) + ": " + refusal;
+        return MESHENV_E_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        g_create_error = std::string(fn) + ": no such HIP device";
+        return MESHENV_E_HIP;
+    }
+    *out = new H();
+    (*out)->device = device;
+    (*out)->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+// The epilogue of a *_destroy: waits for the handle's stream, frees its one device allocation (or none), deletes it.
+template <typename H>
+void destroy_handle(H *h, void *buf)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    if (buf) (void)hipFree(buf);
+    delete h;
+}
+
+int set_stream(HandleBase *h, void *stream)
+{
+    if (!h) return MESHENV_E_ARG;
+    h->stream = (hipStream_t)stream;
+    return MESHENV_OK;
+}
+
+const char *last_error(const HandleBase *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+// `count` floats at *buf, allocated and zeroed on the first call.  Synchronised: the stream may change before they are read.
+bool zeroed_once(const HandleBase *h, float **buf, size_t count)
+{
+    if (*buf) return true;
+    return hipMalloc((void **)buf, count * sizeof(float)) == hipSuccess &&
+           hipMemsetAsync(*buf, 0, count * sizeof(float), h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+}
+
+// Under the caller's guard of the handle's device: `enqueue` (the hipLaunchKernelGGL of one kernel), then the launch error,
+// under fn's name.
+template <typename H, typename F>
+int launch(H *h, const DeviceGuard &guard, const char *fn, F &&enqueue, const char *what = "launch")
+{
+    if (guard.err != hipSuccess) return fail(h, MESHENV_E_HIP, std::string(fn) + ": hipSetDevice failed");
+    enqueue();
+    if (hipGetLastError() != hipSuccess) return fail(h, MESHENV_E_HIP, std::string(fn) + ": " + what + " failed");
+    return MESHENV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1639,54 +1714,32 @@ int meshenv_kernel_times(MeshEnv *h, float *ms_host, int cap, int32_t *n_out)
 }
 
 // ------------------------------------------------------------------------------------------ fused SAC actor
-struct MeshActor {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MeshActor : HandleBase {
     float *buf = nullptr;  // all weights, one allocation
     size_t nfloat = 0;
     ActorWeights W{};
     bool loaded = false;
-    std::string err;
 };
 
 int meshenv_actor_create(int device, void *stream, MeshActor **out)
 {
-    if (!out) return MESHENV_E_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "meshenv_actor_create: no such HIP device";
-        return MESHENV_E_HIP;
-    }
-    MeshActor *a = new MeshActor();
-    a->device = device;
-    a->stream = (hipStream_t)stream;
+    const int rc = create_handle("meshenv_actor_create", device, stream, out);
+    if (rc != MESHENV_OK) return rc;
+    MeshActor *a = *out;
     a->nfloat = (size_t)kActInPad * kActHid + kActHid + 2 * ((size_t)kActHid * kActHid + kActHid) + (size_t)kActHid * 16 + 16;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess || hipMalloc((void **)&a->buf, a->nfloat * sizeof(float)) != hipSuccess) {
         g_create_error = "meshenv_actor_create: hipMalloc failed";
         delete a;
+        *out = nullptr;
         return MESHENV_E_HIP;
     }
-    *out = a;
     return MESHENV_OK;
 }
 
-void meshenv_actor_destroy(MeshActor *a)
-{
-    if (!a) return;
-    DeviceGuard guard(a->device);
-    (void)hipStreamSynchronize(a->stream);
-    if (a->buf) (void)hipFree(a->buf);
-    delete a;
-}
+void meshenv_actor_destroy(MeshActor *a) { destroy_handle(a, a ? a->buf : nullptr); }
 
-int meshenv_actor_set_stream(MeshActor *a, void *stream)
-{
-    if (!a) return MESHENV_E_ARG;
-    a->stream = (hipStream_t)stream;
-    return MESHENV_OK;
-}
+int meshenv_actor_set_stream(MeshActor *a, void *stream) { return set_stream(a, stream); }
 
 // weights in torch.nn.Linear layout ([out][in], row-major), host pointers
 int meshenv_actor_load(MeshActor *a, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
@@ -1765,17 +1818,10 @@ static int actor_launch(MeshActor *a, const char *fn, int n, const float *obs_de
         return MESHENV_E_STATE;
     }
     DeviceGuard guard(a->device);
-    if (guard.err != hipSuccess) {
-        a->err = std::string(fn) + ": hipSetDevice failed";
-        return MESHENV_E_HIP;
-    }
-    hipLaunchKernelGGL(k_actor_forward, dim3((n + kActEnvs - 1) / kActEnvs), dim3(64 * kActWaves), 0, a->stream, a->W, n, obs_dev, noise_dev,
-                       actions_dev, sample, seed, counter, eps_out_dev);
-    if (hipGetLastError() != hipSuccess) {
-        a->err = std::string(fn) + ": launch failed";
-        return MESHENV_E_HIP;
-    }
-    return MESHENV_OK;
+    return launch(a, guard, fn, [&] {
+        hipLaunchKernelGGL(k_actor_forward, dim3((n + kActEnvs - 1) / kActEnvs), dim3(64 * kActWaves), 0, a->stream, a->W, n, obs_dev,
+                           noise_dev, actions_dev, sample, seed, counter, eps_out_dev);
+    });
 }
 
 int meshenv_actor_forward(MeshActor *a, int n, const float *obs_dev, const float *noise_dev, float *actions_dev)
@@ -1912,14 +1958,11 @@ int meshenv_step_actor_multi(MeshEnv *h, MeshActor *a, int T, float *actions_dev
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ fused PPO / A2C / TD3 policies
-struct MeshPolicy {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MeshPolicy : HandleBase {
     float *buf = nullptr;  // all weights of the loaded policy, one allocation
     PolicyWeights W{};
     int kind = -1, hidden = 0, activation = 0;
     bool loaded = false;
-    std::string err;
 };
 
 namespace {
@@ -1953,22 +1996,9 @@ int policy_launch(MeshPolicy *p, const char *fn, const PolicyArgs &A)
     a.tower0 = pi ? 0 : 1;
     const dim3 grid((A.n + kPolEnvs - 1) / kPolEnvs, (pi ? 1 : 0) + (vf ? 1 : 0));
     DeviceGuard guard(p->device);
-    if (guard.err != hipSuccess) {
-        p->err = std::string(fn) + ": hipSetDevice failed";
-        return MESHENV_E_HIP;
-    }
-    hipLaunchKernelGGL(policy_kernel(p->kind, p->hidden, p->activation), grid, dim3(4 * p->hidden), 0, p->stream, p->W, a);
-    if (hipGetLastError() != hipSuccess) {
-        p->err = std::string(fn) + ": launch failed";
-        return MESHENV_E_HIP;
-    }
-    return MESHENV_OK;
-}
-
-int policy_fail(MeshPolicy *p, int rc, const std::string &msg)
-{
-    p->err = msg;
-    return rc;
+    return launch(p, guard, fn, [&] {
+        hipLaunchKernelGGL(policy_kernel(p->kind, p->hidden, p->activation), grid, dim3(4 * p->hidden), 0, p->stream, p->W, a);
+    });
 }
 
 }  // namespace
@@ -1977,37 +2007,14 @@ extern "C" {
 
 int meshenv_policy_create(int device, void *stream, MeshPolicy **out)
 {
-    if (!out) return MESHENV_E_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "meshenv_policy_create: no such HIP device";
-        return MESHENV_E_HIP;
-    }
-    MeshPolicy *p = new MeshPolicy();
-    p->device = device;
-    p->stream = (hipStream_t)stream;
-    *out = p;
-    return MESHENV_OK;
+    return create_handle("meshenv_policy_create", device, stream, out);
 }
 
-void meshenv_policy_destroy(MeshPolicy *p)
-{
-    if (!p) return;
-    DeviceGuard guard(p->device);
-    (void)hipStreamSynchronize(p->stream);
-    if (p->buf) (void)hipFree(p->buf);
-    delete p;
-}
+void meshenv_policy_destroy(MeshPolicy *p) { destroy_handle(p, p ? p->buf : nullptr); }
 
-const char *meshenv_policy_last_error(const MeshPolicy *p) { return p ? p->err.c_str() : g_create_error.c_str(); }
+const char *meshenv_policy_last_error(const MeshPolicy *p) { return last_error(p); }
 
-int meshenv_policy_set_stream(MeshPolicy *p, void *stream)
-{
-    if (!p) return MESHENV_E_ARG;
-    p->stream = (hipStream_t)stream;
-    return MESHENV_OK;
-}
+int meshenv_policy_set_stream(MeshPolicy *p, void *stream) { return set_stream(p, stream); }
 
 // weights in torch.nn.Linear layout ([out][in], row-major), host pointers
 int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, const float *pi_w1, const float *pi_b1,
@@ -2018,14 +2025,14 @@ int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, con
     if (!p) return MESHENV_E_ARG;
     if ((kind != kPolicyActorCritic && kind != kPolicyDeterministic) || (hidden != 64 && hidden != 128 && hidden != 256) ||
         (activation != kPolicyReLU && activation != kPolicyTanh))
-        return policy_fail(p, MESHENV_E_ARG, std::string("meshenv_policy_load: unsupported shape; ") + kPolicyShapes);
+        return fail(p, MESHENV_E_ARG, std::string("meshenv_policy_load: unsupported shape; ") + kPolicyShapes);
     const bool ac = kind == kPolicyActorCritic;
     if (!pi_w1 || !pi_b1 || !pi_w2 || !pi_b2 || !head_w || !head_b || !low || !high || (ac && !log_std_or_sigma))
-        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_load: null weight pointer");
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_load: null weight pointer");
     if (ac && (!vf_w1 || !vf_b1 || !vf_w2 || !vf_b2 || !value_w || !value_b))
-        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_load: the actor-critic kind needs the vf tower and value_net");
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_load: the actor-critic kind needs the vf tower and value_net");
     if (!ac && (vf_w1 || vf_b1 || vf_w2 || vf_b2 || value_w || value_b))
-        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_load: the deterministic kind has no vf tower (pass NULL)");
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_load: the deterministic kind has no vf tower (pass NULL)");
     const int H = hidden;
     std::vector<float> h;
     // torch [out][in] -> the per-lane MFMA B-operand order of meshenv_policy.h: [tile][K/16][lane][4]
@@ -2067,14 +2074,14 @@ int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, con
         h[o_aux + 6 + i] = high[i];
     }
     DeviceGuard guard(p->device);
-    if (guard.err != hipSuccess) return policy_fail(p, MESHENV_E_HIP, "meshenv_policy_load: hipSetDevice failed");
+    if (guard.err != hipSuccess) return fail(p, MESHENV_E_HIP, "meshenv_policy_load: hipSetDevice failed");
     (void)hipStreamSynchronize(p->stream);   // the previous weights may still be in use
     if (p->buf) (void)hipFree(p->buf);
     p->buf = nullptr;
     p->loaded = false;
     if (hipMalloc((void **)&p->buf, h.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(p->buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return policy_fail(p, MESHENV_E_HIP, "meshenv_policy_load: upload failed");
+        return fail(p, MESHENV_E_HIP, "meshenv_policy_load: upload failed");
     auto bind = [&](PolicyTower &T, const Offs &o) {
         T.w1p = p->buf + o.w1; T.b1 = p->buf + o.b1;
         T.w2p = p->buf + o.w2; T.b2 = p->buf + o.b2;
@@ -2094,16 +2101,16 @@ int meshenv_policy_forward(MeshPolicy *p, int n, const float *obs_dev, const flo
                            float *eps_out_dev)
 {
     if (!p) return MESHENV_E_ARG;
-    if (!p->loaded) return policy_fail(p, MESHENV_E_STATE, "meshenv_policy_forward: no weights loaded");
-    if (n <= 0 || !obs_dev) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: n > 0 and obs_dev are required");
-    if (noise_dev && sample) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: explicit noise and sample are exclusive");
+    if (!p->loaded) return fail(p, MESHENV_E_STATE, "meshenv_policy_forward: no weights loaded");
+    if (n <= 0 || !obs_dev) return fail(p, MESHENV_E_ARG, "meshenv_policy_forward: n > 0 and obs_dev are required");
+    if (noise_dev && sample) return fail(p, MESHENV_E_ARG, "meshenv_policy_forward: explicit noise and sample are exclusive");
     if (p->kind == kPolicyDeterministic && (log_prob_dev || value_dev))
-        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: the deterministic kind has no log_prob / value (pass NULL)");
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_forward: the deterministic kind has no log_prob / value (pass NULL)");
     if (eps_out_dev && !sample && !noise_dev)
-        return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: eps_out_dev without noise");
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_forward: eps_out_dev without noise");
     const bool pi = actions_dev || buffer_actions_dev || log_prob_dev || eps_out_dev;
-    if (!pi && !value_dev) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: no output requested");
-    if (!pi && (noise_dev || sample)) return policy_fail(p, MESHENV_E_ARG, "meshenv_policy_forward: noise without an action output");
+    if (!pi && !value_dev) return fail(p, MESHENV_E_ARG, "meshenv_policy_forward: no output requested");
+    if (!pi && (noise_dev || sample)) return fail(p, MESHENV_E_ARG, "meshenv_policy_forward: noise without an action output");
     PolicyArgs A{};
     A.n = n; A.obs = obs_dev; A.noise = noise_dev; A.sample = sample ? 1 : 0; A.seed = seed; A.counter = counter;
     A.actions = actions_dev; A.buffer_actions = buffer_actions_dev; A.log_prob = log_prob_dev; A.value = value_dev;
@@ -2468,9 +2475,7 @@ int meshenv_evaluate(MeshEnv *h, MeshPolicy *policy, MeshActor *actor, int sampl
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ SAC / TD3 TD targets
-struct MeshTarget {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MeshTarget : HandleBase {
     int kind = -1;
     float gamma = 0.f, ent_coef = 0.f, policy_noise = 0.f, noise_clip = 0.f;
     float *buf = nullptr;      // every packed weight, one allocation, zeroed once
@@ -2478,16 +2483,9 @@ struct MeshTarget {
     PackTable table{};
     int n_copies = 0;
     bool bound = false, packed = false;
-    std::string err;
 };
 
 namespace {
-
-int target_fail(MeshTarget *t, int rc, const std::string &msg)
-{
-    t->err = msg;
-    return rc;
-}
 
 const char *kTargetKinds = "supported kinds: 0 (SAC: ReLU [128, 128, 128] actor with mu / log_std heads and twin ReLU [128, 128, 128] "
                            "critics) or 1 (TD3: ReLU [256, 256] tanh actor and twin ReLU [256, 256] critics); 18 observations, 3 actions";
@@ -2499,48 +2497,24 @@ extern "C" {
 int meshenv_target_create(int device, void *stream, int kind, float gamma, float ent_coef, float policy_noise, float noise_clip,
                           MeshTarget **out)
 {
-    if (!out) return MESHENV_E_ARG;
-    *out = nullptr;
-    if (kind != kTargetSAC && kind != kTargetTD3) {
-        g_create_error = std::string("meshenv_target_create: unsupported kind; ") + kTargetKinds;
-        return MESHENV_E_ARG;
-    }
-    if (!(gamma >= 0.0f && gamma <= 1.0f) || !std::isfinite(ent_coef) || !(policy_noise >= 0.0f) || !(noise_clip >= 0.0f) ||
-        !std::isfinite(policy_noise) || !std::isfinite(noise_clip)) {
-        g_create_error = "meshenv_target_create: gamma must lie in [0, 1], ent_coef be finite, policy_noise and noise_clip be finite and >= 0";
-        return MESHENV_E_ARG;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "meshenv_target_create: no such HIP device";
-        return MESHENV_E_HIP;
-    }
-    MeshTarget *t = new MeshTarget();
-    t->device = device;
-    t->stream = (hipStream_t)stream;
+    std::string refusal;
+    if (kind != kTargetSAC && kind != kTargetTD3) refusal = std::string("unsupported kind; ") + kTargetKinds;
+    else if (!(gamma >= 0.0f && gamma <= 1.0f) || !std::isfinite(ent_coef) || !(policy_noise >= 0.0f) || !(noise_clip >= 0.0f) ||
+             !std::isfinite(policy_noise) || !std::isfinite(noise_clip))
+        refusal = "gamma must lie in [0, 1], ent_coef be finite, policy_noise and noise_clip be finite and >= 0";
+    const int rc = create_handle("meshenv_target_create", device, stream, out, refusal);
+    if (rc != MESHENV_OK) return rc;
+    MeshTarget *t = *out;
     t->kind = kind;
     t->gamma = gamma; t->ent_coef = ent_coef; t->policy_noise = policy_noise; t->noise_clip = noise_clip;
-    *out = t;
     return MESHENV_OK;
 }
 
-void meshenv_target_destroy(MeshTarget *t)
-{
-    if (!t) return;
-    DeviceGuard guard(t->device);
-    (void)hipStreamSynchronize(t->stream);
-    if (t->buf) (void)hipFree(t->buf);
-    delete t;
-}
+void meshenv_target_destroy(MeshTarget *t) { destroy_handle(t, t ? t->buf : nullptr); }
 
-const char *meshenv_target_last_error(const MeshTarget *t) { return t ? t->err.c_str() : g_create_error.c_str(); }
+const char *meshenv_target_last_error(const MeshTarget *t) { return last_error(t); }
 
-int meshenv_target_set_stream(MeshTarget *t, void *stream)
-{
-    if (!t) return MESHENV_E_ARG;
-    t->stream = (hipStream_t)stream;
-    return MESHENV_OK;
-}
+int meshenv_target_set_stream(MeshTarget *t, void *stream) { return set_stream(t, stream); }
 
 int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
                         const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev)
@@ -2550,24 +2524,19 @@ int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_acto
     const int H = sac ? 128 : 256, NL = sac ? 3 : 2, G = H / 16;
     const int want_actor = 2 * NL + (sac ? 4 : 2), want_critic = 2 * NL + 2;
     if (!actor_dev || !q1_dev || !q2_dev || n_actor != want_actor || n_critic != want_critic)
-        return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: kind " + std::to_string(t->kind) + " takes " +
+        return fail(t, MESHENV_E_ARG, "meshenv_target_bind: kind " + std::to_string(t->kind) + " takes " +
                            std::to_string(want_actor) + " actor and " + std::to_string(want_critic) + " critic tensors; " + kTargetKinds);
     for (int i = 0; i < n_actor; i++)
-        if (!actor_dev[i]) return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: null actor tensor");
+        if (!actor_dev[i]) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: null actor tensor");
     for (int i = 0; i < n_critic; i++)
-        if (!q1_dev[i] || !q2_dev[i]) return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: null critic tensor");
-    if (!sac && log_ent_coef_dev) return target_fail(t, MESHENV_E_ARG, "meshenv_target_bind: TD3 has no entropy coefficient (pass NULL)");
+        if (!q1_dev[i] || !q2_dev[i]) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: null critic tensor");
+    if (!sac && log_ent_coef_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: TD3 has no entropy coefficient (pass NULL)");
     DeviceGuard guard(t->device);
-    if (guard.err != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_bind: hipSetDevice failed");
+    if (guard.err != hipSuccess) return fail(t, MESHENV_E_HIP, "meshenv_target_bind: hipSetDevice failed");
     // layout of the buffer: per tower w1p b1 w2p b2 [w3p b3] whp bh, then log_ent_coef
     const size_t tower_floats = (size_t)G * 2 * 256 + H + (size_t)(NL - 1) * ((size_t)G * G * 256 + H) + (size_t)G * 256 + 16;
     const size_t total = 3 * tower_floats + 4;
-    if (!t->buf) {
-        if (hipMalloc((void **)&t->buf, total * sizeof(float)) != hipSuccess ||
-            hipMemsetAsync(t->buf, 0, total * sizeof(float), t->stream) != hipSuccess ||
-            hipStreamSynchronize(t->stream) != hipSuccess)   // the stream may change before the first refresh
-            return target_fail(t, MESHENV_E_HIP, "meshenv_target_bind: allocation failed");
-    }
+    if (!zeroed_once(t, &t->buf, total)) return fail(t, MESHENV_E_HIP, "meshenv_target_bind: allocation failed");
     t->n_copies = 0;
     auto add = [&](const float *src, float *dst, int out, int in, int groups, int tiles, int n_off, int kind) {
         PackCopy &c = t->table.c[t->n_copies++];
@@ -2611,15 +2580,15 @@ int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_acto
 int meshenv_target_refresh(MeshTarget *t)
 {
     if (!t) return MESHENV_E_ARG;
-    if (!t->bound) return target_fail(t, MESHENV_E_STATE, "meshenv_target_refresh: no tensors bound (meshenv_target_bind)");
-    DeviceGuard guard(t->device);
-    if (guard.err != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_refresh: hipSetDevice failed");
+    if (!t->bound) return fail(t, MESHENV_E_STATE, "meshenv_target_refresh: no tensors bound (meshenv_target_bind)");
     // the largest copy is an H x H matrix: H * H / 256 blocks cover it in one pass
     const int H = t->kind == kTargetSAC ? 128 : 256;
-    hipLaunchKernelGGL(k_target_pack, dim3(H * H / 256, t->n_copies), dim3(256), 0, t->stream, t->table);
-    if (hipGetLastError() != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_refresh: launch failed");
-    t->packed = true;
-    return MESHENV_OK;
+    DeviceGuard guard(t->device);
+    const int rc = launch(t, guard, "meshenv_target_refresh", [&] {
+        hipLaunchKernelGGL(k_target_pack, dim3(H * H / 256, t->n_copies), dim3(256), 0, t->stream, t->table);
+    });
+    if (rc == MESHENV_OK) t->packed = true;
+    return rc;
 }
 
 int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, const float *rewards_dev, const float *dones_dev,
@@ -2627,52 +2596,42 @@ int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, cons
                            float *next_actions_dev, float *next_log_prob_dev, float *q1_dev, float *q2_dev, float *eps_out_dev)
 {
     if (!t) return MESHENV_E_ARG;
-    if (!t->packed) return target_fail(t, MESHENV_E_STATE, "meshenv_target_forward: no weights packed (meshenv_target_bind, then meshenv_target_refresh)");
-    if (n <= 0 || !next_obs_dev) return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: n > 0 and next_obs_dev are required");
-    if (noise_dev && sample) return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: explicit noise and sample are exclusive");
+    if (!t->packed) return fail(t, MESHENV_E_STATE, "meshenv_target_forward: no weights packed (meshenv_target_bind, then meshenv_target_refresh)");
+    if (n <= 0 || !next_obs_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_forward: n > 0 and next_obs_dev are required");
+    if (noise_dev && sample) return fail(t, MESHENV_E_ARG, "meshenv_target_forward: explicit noise and sample are exclusive");
     if (target_dev && (!rewards_dev || !dones_dev))
-        return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: target_dev needs rewards_dev and dones_dev");
+        return fail(t, MESHENV_E_ARG, "meshenv_target_forward: target_dev needs rewards_dev and dones_dev");
     if (t->kind == kTargetTD3 && next_log_prob_dev)
-        return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: TD3 has no next_log_prob (pass NULL)");
-    if (eps_out_dev && !sample && !noise_dev) return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: eps_out_dev without noise");
+        return fail(t, MESHENV_E_ARG, "meshenv_target_forward: TD3 has no next_log_prob (pass NULL)");
+    if (eps_out_dev && !sample && !noise_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_forward: eps_out_dev without noise");
     if (!target_dev && !next_actions_dev && !next_log_prob_dev && !q1_dev && !q2_dev && !eps_out_dev)
-        return target_fail(t, MESHENV_E_ARG, "meshenv_target_forward: no output requested");
+        return fail(t, MESHENV_E_ARG, "meshenv_target_forward: no output requested");
     TargetArgs A{};
     A.n = n; A.next_obs = next_obs_dev; A.rewards = rewards_dev; A.dones = dones_dev; A.noise = noise_dev;
     A.sample = sample ? 1 : 0; A.seed = seed; A.counter = counter;
     A.gamma = t->gamma; A.ent_coef = t->ent_coef; A.policy_noise = t->policy_noise; A.noise_clip = t->noise_clip;
     A.target = target_dev; A.next_actions = next_actions_dev; A.next_log_prob = next_log_prob_dev; A.q1 = q1_dev; A.q2 = q2_dev;
     A.eps_out = eps_out_dev;
-    DeviceGuard guard(t->device);
-    if (guard.err != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_forward: hipSetDevice failed");
     const dim3 grid((n + kTgtRows - 1) / kTgtRows);
-    if (t->kind == kTargetSAC) hipLaunchKernelGGL(k_td_target<kTargetSAC>, grid, dim3(512), 0, t->stream, t->W, A);
-    else hipLaunchKernelGGL(k_td_target<kTargetTD3>, grid, dim3(1024), 0, t->stream, t->W, A);
-    if (hipGetLastError() != hipSuccess) return target_fail(t, MESHENV_E_HIP, "meshenv_target_forward: launch failed");
-    return MESHENV_OK;
+    DeviceGuard guard(t->device);
+    return launch(t, guard, "meshenv_target_forward", [&] {
+        if (t->kind == kTargetSAC) hipLaunchKernelGGL(k_td_target<kTargetSAC>, grid, dim3(512), 0, t->stream, t->W, A);
+        else hipLaunchKernelGGL(k_td_target<kTargetTD3>, grid, dim3(1024), 0, t->stream, t->W, A);
+    });
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ SAC / TD3 critic loss gradients
-struct MeshCriticGrad {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MeshCriticGrad : HandleBase {
     int kind = -1;
     CgCritic c[2]{};
     float *grad = nullptr;      // the caller's flat gradient buffer (CgLayout::grads floats)
     float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
     bool bound = false;
-    std::string err;
 };
 
 namespace {
-
-int cg_fail(MeshCriticGrad *g, int rc, const std::string &msg)
-{
-    g->err = msg;
-    return rc;
-}
 
 const char *kCriticGradKinds = "supported kinds: 0 (SAC: twin ReLU [128, 128, 128] critics) or 1 (TD3: twin ReLU [256, 256] critics); "
                                "input cat(obs, action) = 21, float32";
@@ -2686,48 +2645,50 @@ void cg_layout(int kind, int *grads, int *set)
     else cg_sizes<256, 2>(grads, set);
 }
 
+// The workgroups of a gradient kernel on n rows: one per 16-row tile up to 64, then 64, and kCgMaxGroups beyond 512 tiles.
+int grad_groups(int n)
+{
+    const int tiles = (n + kCgRows - 1) / kCgRows;
+    return tiles <= 512 ? (tiles < 64 ? tiles : 64) : kCgMaxGroups;
+}
+
+// The twin critics' tensors (w1 b1 ... out_w out_b, `count` each) into c[2].  The hidden layers' [H][H] weights are read 16
+// bytes at a time.  Returns what is wrong, or nothing; `weight` names a tensor in the alignment refusal.
+std::string bind_critics(CgCritic c[2], const float *const *q1_dev, const float *const *q2_dev, int count, const char *weight)
+{
+    for (int i = 0; i < count; i++) {
+        if (!q1_dev[i] || !q2_dev[i]) return "null critic tensor";
+        if (i % 2 == 0 && i >= 2 && (((uintptr_t)q1_dev[i] | (uintptr_t)q2_dev[i]) & 15))
+            return std::string(weight) + " tensor " + std::to_string(i) + " is not 16-byte aligned";
+    }
+    for (int k = 0; k < 2; k++) {
+        const float *const *p = k == 0 ? q1_dev : q2_dev;
+        for (int l = 0; l < count / 2; l++) {
+            c[k].w[l] = p[2 * l];
+            c[k].b[l] = p[2 * l + 1];
+        }
+    }
+    return std::string();
+}
+
 }  // namespace
 
 extern "C" {
 
 int meshenv_critic_grad_create(int device, void *stream, int kind, MeshCriticGrad **out)
 {
-    if (!out) return MESHENV_E_ARG;
-    *out = nullptr;
-    if (kind != kTargetSAC && kind != kTargetTD3) {
-        g_create_error = std::string("meshenv_critic_grad_create: unsupported kind; ") + kCriticGradKinds;
-        return MESHENV_E_ARG;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "meshenv_critic_grad_create: no such HIP device";
-        return MESHENV_E_HIP;
-    }
-    MeshCriticGrad *g = new MeshCriticGrad();
-    g->device = device;
-    g->stream = (hipStream_t)stream;
-    g->kind = kind;
-    *out = g;
-    return MESHENV_OK;
+    const bool known = kind == kTargetSAC || kind == kTargetTD3;
+    const int rc = create_handle("meshenv_critic_grad_create", device, stream, out,
+                                 known ? std::string() : std::string("unsupported kind; ") + kCriticGradKinds);
+    if (rc == MESHENV_OK) (*out)->kind = kind;
+    return rc;
 }
 
-void meshenv_critic_grad_destroy(MeshCriticGrad *g)
-{
-    if (!g) return;
-    DeviceGuard guard(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    if (g->partial) (void)hipFree(g->partial);
-    delete g;
-}
+void meshenv_critic_grad_destroy(MeshCriticGrad *g) { destroy_handle(g, g ? g->partial : nullptr); }
 
-const char *meshenv_critic_grad_last_error(const MeshCriticGrad *g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+const char *meshenv_critic_grad_last_error(const MeshCriticGrad *g) { return last_error(g); }
 
-int meshenv_critic_grad_set_stream(MeshCriticGrad *g, void *stream)
-{
-    if (!g) return MESHENV_E_ARG;
-    g->stream = (hipStream_t)stream;
-    return MESHENV_OK;
-}
+int meshenv_critic_grad_set_stream(MeshCriticGrad *g, void *stream) { return set_stream(g, stream); }
 
 int meshenv_critic_grad_bind(MeshCriticGrad *g, const float *const *q1_dev, const float *const *q2_dev, int n_critic,
                              float *grad_dev, int64_t n_grad)
@@ -2737,32 +2698,19 @@ int meshenv_critic_grad_bind(MeshCriticGrad *g, const float *const *q1_dev, cons
     int grads = 0, set = 0;
     cg_layout(g->kind, &grads, &set);
     if (!q1_dev || !q2_dev || n_critic != want)
-        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: kind " + std::to_string(g->kind) + " takes " + std::to_string(want) +
+        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: kind " + std::to_string(g->kind) + " takes " + std::to_string(want) +
                        " tensors per critic; " + kCriticGradKinds);
     if (!grad_dev || n_grad != grads)
-        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: the gradient buffer of kind " + std::to_string(g->kind) + " has " +
+        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: the gradient buffer of kind " + std::to_string(g->kind) + " has " +
                        std::to_string(grads) + " floats, got " + std::to_string((long long)n_grad));
-    for (int i = 0; i < want; i++) {
-        if (!q1_dev[i] || !q2_dev[i]) return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: null critic tensor");
-        // the hidden layers' [H][H] weights are read 16 bytes at a time
-        if (i % 2 == 0 && i >= 2 && (((uintptr_t)q1_dev[i] | (uintptr_t)q2_dev[i]) & 15))
-            return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
+    CgCritic c[2]{};
+    const std::string refusal = bind_critics(c, q1_dev, q2_dev, want, "weight");
+    if (!refusal.empty()) return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: " + refusal);
     DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: hipSetDevice failed");
-    if (!g->partial) {
-        const size_t bytes = (size_t)kCgMaxGroups * set * sizeof(float);
-        if (hipMalloc((void **)&g->partial, bytes) != hipSuccess || hipMemsetAsync(g->partial, 0, bytes, g->stream) != hipSuccess ||
-            hipStreamSynchronize(g->stream) != hipSuccess)   // the stream may change before the first backward
-            return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: allocation failed");
-    }
-    for (int k = 0; k < 2; k++) {
-        const float *const *p = k == 0 ? q1_dev : q2_dev;
-        for (int l = 0; l <= NL; l++) {
-            g->c[k].w[l] = p[2 * l];
-            g->c[k].b[l] = p[2 * l + 1];
-        }
-    }
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: hipSetDevice failed");
+    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * set))
+        return fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: allocation failed");
+    g->c[0] = c[0]; g->c[1] = c[1];
     g->grad = grad_dev;
     g->bound = true;
     return MESHENV_OK;
@@ -2772,18 +2720,17 @@ int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev,
                                  float *loss_dev, float *q1_dev, float *q2_dev, float *const *acts1_dev, float *const *acts2_dev)
 {
     if (!g) return MESHENV_E_ARG;
-    if (!g->bound) return cg_fail(g, MESHENV_E_STATE, "meshenv_critic_grad_backward: no tensors bound (meshenv_critic_grad_bind)");
+    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_critic_grad_backward: no tensors bound (meshenv_critic_grad_bind)");
     if (n <= 0 || !obs_dev || !actions_dev || !target_dev || !loss_dev)
-        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: n > 0, obs_dev, actions_dev, target_dev and loss_dev are required");
+        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: n > 0, obs_dev, actions_dev, target_dev and loss_dev are required");
     if ((acts1_dev == nullptr) != (acts2_dev == nullptr))
-        return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: acts1_dev and acts2_dev go together");
+        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: acts1_dev and acts2_dev go together");
     const int NL = g->kind == kTargetSAC ? 3 : 2;
     int grads = 0, set = 0;
     cg_layout(g->kind, &grads, &set);
     CgArgs A{};
-    const int tiles = (n + kCgRows - 1) / kCgRows;
     A.n = n;
-    A.nwg = tiles <= 512 ? (tiles < 64 ? tiles : 64) : kCgMaxGroups;
+    A.nwg = grad_groups(n);
     A.obs = obs_dev; A.actions = actions_dev; A.target = target_dev;
     A.c[0] = g->c[0]; A.c[1] = g->c[1];
     A.partial = g->partial;
@@ -2792,25 +2739,24 @@ int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev,
         A.acts[0][l] = acts1_dev ? acts1_dev[l] : nullptr;
         A.acts[1][l] = acts2_dev ? acts2_dev[l] : nullptr;
         if (acts1_dev && (!A.acts[0][l] || !A.acts[1][l]))
-            return cg_fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: null activation output");
+            return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: null activation output");
     }
     DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: hipSetDevice failed");
-    if (g->kind == kTargetSAC) hipLaunchKernelGGL(k_critic_grad<kTargetSAC>, dim3(A.nwg, 2), dim3(512), 0, g->stream, A);
-    else hipLaunchKernelGGL(k_critic_grad<kTargetTD3>, dim3(A.nwg, 2 * kCgSplitTD3), dim3(1024), 0, g->stream, A);
-    if (hipGetLastError() != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: launch failed");
-    hipLaunchKernelGGL(k_critic_grad_reduce, dim3((grads + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg, set,
-                       grads, n, g->grad, loss_dev);
-    if (hipGetLastError() != hipSuccess) return cg_fail(g, MESHENV_E_HIP, "meshenv_critic_grad_backward: reduction launch failed");
-    return MESHENV_OK;
+    const int rc = launch(g, guard, "meshenv_critic_grad_backward", [&] {
+        if (g->kind == kTargetSAC) hipLaunchKernelGGL(k_critic_grad<kTargetSAC>, dim3(A.nwg, 2), dim3(512), 0, g->stream, A);
+        else hipLaunchKernelGGL(k_critic_grad<kTargetTD3>, dim3(A.nwg, 2 * kCgSplitTD3), dim3(1024), 0, g->stream, A);
+    });
+    if (rc != MESHENV_OK) return rc;
+    return launch(g, guard, "meshenv_critic_grad_backward", [&] {
+        hipLaunchKernelGGL(k_critic_grad_reduce, dim3((grads + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg,
+                           set, grads, n, g->grad, loss_dev);
+    }, "reduction launch");
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ SAC actor / ent_coef loss gradients
-struct MeshActorGrad {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MeshActorGrad : HandleBase {
     float ent_coef = 0.0f, target_entropy = 0.0f;
     AgActor a{};
     CgCritic c[2]{};
@@ -2818,102 +2764,56 @@ struct MeshActorGrad {
     float *grad = nullptr;      // the caller's flat gradient buffer (AgLayout::stride floats)
     float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
     bool bound = false;
-    std::string err;
 };
-
-namespace {
-
-int ag_fail(MeshActorGrad *g, int rc, const std::string &msg)
-{
-    g->err = msg;
-    return rc;
-}
-
-}  // namespace
 
 extern "C" {
 
 int meshenv_actor_grad_create(int device, void *stream, float ent_coef, float target_entropy, MeshActorGrad **out)
 {
-    if (!out) return MESHENV_E_ARG;
-    *out = nullptr;
-    if (!std::isfinite(ent_coef) || !std::isfinite(target_entropy)) {
-        g_create_error = "meshenv_actor_grad_create: ent_coef and target_entropy must be finite";
-        return MESHENV_E_ARG;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "meshenv_actor_grad_create: no such HIP device";
-        return MESHENV_E_HIP;
-    }
-    MeshActorGrad *g = new MeshActorGrad();
-    g->device = device;
-    g->stream = (hipStream_t)stream;
-    g->ent_coef = ent_coef;
-    g->target_entropy = target_entropy;
-    *out = g;
+    const bool finite = std::isfinite(ent_coef) && std::isfinite(target_entropy);
+    const int rc = create_handle("meshenv_actor_grad_create", device, stream, out,
+                                 finite ? "" : "ent_coef and target_entropy must be finite");
+    if (rc != MESHENV_OK) return rc;
+    (*out)->ent_coef = ent_coef;
+    (*out)->target_entropy = target_entropy;
     return MESHENV_OK;
 }
 
-void meshenv_actor_grad_destroy(MeshActorGrad *g)
-{
-    if (!g) return;
-    DeviceGuard guard(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    if (g->partial) (void)hipFree(g->partial);
-    delete g;
-}
+void meshenv_actor_grad_destroy(MeshActorGrad *g) { destroy_handle(g, g ? g->partial : nullptr); }
 
-const char *meshenv_actor_grad_last_error(const MeshActorGrad *g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+const char *meshenv_actor_grad_last_error(const MeshActorGrad *g) { return last_error(g); }
 
-int meshenv_actor_grad_set_stream(MeshActorGrad *g, void *stream)
-{
-    if (!g) return MESHENV_E_ARG;
-    g->stream = (hipStream_t)stream;
-    return MESHENV_OK;
-}
+int meshenv_actor_grad_set_stream(MeshActorGrad *g, void *stream) { return set_stream(g, stream); }
 
 int meshenv_actor_grad_bind(MeshActorGrad *g, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
                             const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev, float *grad_dev, int64_t n_grad)
 {
     if (!g) return MESHENV_E_ARG;
     if (!actor_dev || !q1_dev || !q2_dev || n_actor != 10 || n_critic != 8)
-        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: takes 10 actor tensors and 8 tensors per critic (SAC: actor ReLU "
+        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: takes 10 actor tensors and 8 tensors per critic (SAC: actor ReLU "
                        "[128, 128, 128] with mu / log_std heads, twin ReLU [128, 128, 128] critics, float32)");
     if (!grad_dev || n_grad != AgLayout::stride)
-        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: the gradient buffer has " + std::to_string(AgLayout::stride) +
+        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: the gradient buffer has " + std::to_string(AgLayout::stride) +
                        " floats, got " + std::to_string((long long)n_grad));
     for (int i = 0; i < 10; i++) {
-        if (!actor_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: null actor tensor");
+        if (!actor_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: null actor tensor");
         // the [H][H] weights and the heads' [3][H] weights are read 16 bytes at a time
         if (i % 2 == 0 && i >= 2 && ((uintptr_t)actor_dev[i] & 15))
-            return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: actor weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+            return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: actor weight tensor " + std::to_string(i) + " is not 16-byte aligned");
     }
-    for (int i = 0; i < 8; i++) {
-        if (!q1_dev[i] || !q2_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: null critic tensor");
-        if (i % 2 == 0 && i >= 2 && (((uintptr_t)q1_dev[i] | (uintptr_t)q2_dev[i]) & 15))
-            return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: critic weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
+    CgCritic c[2]{};
+    const std::string refusal = bind_critics(c, q1_dev, q2_dev, 8, "critic weight");
+    if (!refusal.empty()) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: " + refusal);
     DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: hipSetDevice failed");
-    if (!g->partial) {
-        const size_t bytes = (size_t)kCgMaxGroups * AgLayout::set * sizeof(float);
-        if (hipMalloc((void **)&g->partial, bytes) != hipSuccess || hipMemsetAsync(g->partial, 0, bytes, g->stream) != hipSuccess ||
-            hipStreamSynchronize(g->stream) != hipSuccess)   // the stream may change before the first backward
-            return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: allocation failed");
-    }
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: hipSetDevice failed");
+    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * AgLayout::set))
+        return fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: allocation failed");
     for (int l = 0; l < 3; l++) {
         g->a.w[l] = actor_dev[2 * l];
         g->a.b[l] = actor_dev[2 * l + 1];
     }
     g->a.mu_w = actor_dev[6]; g->a.mu_b = actor_dev[7]; g->a.ls_w = actor_dev[8]; g->a.ls_b = actor_dev[9];
-    for (int k = 0; k < 2; k++) {
-        const float *const *p = k == 0 ? q1_dev : q2_dev;
-        for (int l = 0; l <= 3; l++) {
-            g->c[k].w[l] = p[2 * l];
-            g->c[k].b[l] = p[2 * l + 1];
-        }
-    }
+    g->c[0] = c[0]; g->c[1] = c[1];
     g->log_ent_coef = log_ent_coef_dev;
     g->grad = grad_dev;
     g->bound = true;
@@ -2924,17 +2824,16 @@ int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, c
                                 uint64_t counter, float *losses_dev, float *eps_out_dev, float *const *parts_dev, float *const *acts_dev)
 {
     if (!g) return MESHENV_E_ARG;
-    if (!g->bound) return ag_fail(g, MESHENV_E_STATE, "meshenv_actor_grad_backward: no tensors bound (meshenv_actor_grad_bind)");
+    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_actor_grad_backward: no tensors bound (meshenv_actor_grad_bind)");
     if (n <= 0 || !obs_dev || !losses_dev)
-        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: n > 0, obs_dev and losses_dev are required");
+        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: n > 0, obs_dev and losses_dev are required");
     if (noise_dev && sample)
-        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: noise_dev and sample are exclusive");
+        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: noise_dev and sample are exclusive");
     if (eps_out_dev && !noise_dev && !sample)
-        return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: eps_out_dev needs noise_dev or sample");
+        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: eps_out_dev needs noise_dev or sample");
     AgArgs A{};
-    const int tiles = (n + kCgRows - 1) / kCgRows;
     A.n = n;
-    A.nwg = tiles <= 512 ? (tiles < 64 ? tiles : 64) : kCgMaxGroups;
+    A.nwg = grad_groups(n);
     A.obs = obs_dev; A.noise = noise_dev; A.sample = sample ? 1 : 0; A.seed = seed; A.counter = counter;
     A.a = g->a; A.c[0] = g->c[0]; A.c[1] = g->c[1];
     A.log_ent_coef = g->log_ent_coef; A.ent_coef = g->ent_coef; A.target_entropy = g->target_entropy;
@@ -2942,24 +2841,23 @@ int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, c
     A.eps_out = eps_out_dev;
     if (parts_dev) {
         for (int i = 0; i < kAgParts; i++)
-            if (!parts_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null per-sample output");
+            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null per-sample output");
         A.actions = parts_dev[0]; A.log_prob = parts_dev[1]; A.q[0] = parts_dev[2]; A.q[1] = parts_dev[3];
         A.dq_da = parts_dev[4]; A.d_mu = parts_dev[5]; A.d_ls = parts_dev[6];
     }
     if (acts_dev) {
         for (int i = 0; i < 9; i++) {
-            if (!acts_dev[i]) return ag_fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null activation output");
+            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null activation output");
             A.acts[i / 3][i % 3] = acts_dev[i];
         }
     }
     DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: hipSetDevice failed");
-    hipLaunchKernelGGL(k_actor_grad, dim3(A.nwg), dim3(512), 0, g->stream, A);
-    if (hipGetLastError() != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: launch failed");
-    hipLaunchKernelGGL(k_actor_grad_reduce, dim3((AgLayout::ent + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg,
-                       n, g->log_ent_coef, g->grad, losses_dev);
-    if (hipGetLastError() != hipSuccess) return ag_fail(g, MESHENV_E_HIP, "meshenv_actor_grad_backward: reduction launch failed");
-    return MESHENV_OK;
+    const int rc = launch(g, guard, "meshenv_actor_grad_backward", [&] { hipLaunchKernelGGL(k_actor_grad, dim3(A.nwg), dim3(512), 0, g->stream, A); });
+    if (rc != MESHENV_OK) return rc;
+    return launch(g, guard, "meshenv_actor_grad_backward", [&] {
+        hipLaunchKernelGGL(k_actor_grad_reduce, dim3((AgLayout::ent + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial,
+                           A.nwg, n, g->log_ent_coef, g->grad, losses_dev);
+    }, "reduction launch");
 }
 
 }  // extern "C"
@@ -2980,41 +2878,17 @@ struct OptProgram {
     bool bound = false;
 };
 
-struct MeshOptim {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MeshOptim : HandleBase {
     hipStream_t last_stream = nullptr;   // the stream of the last upload or launch: what may still read a table
     bool used = false;
     OptProgram prog[MESHENV_OPTIM_PROGRAMS];
-    std::string err;
 };
-
-namespace {
-
-int opt_fail(MeshOptim *o, int rc, const std::string &msg)
-{
-    o->err = msg;
-    return rc;
-}
-
-}  // namespace
 
 extern "C" {
 
 int meshenv_optim_create(int device, void *stream, MeshOptim **out)
 {
-    if (!out) return MESHENV_E_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "meshenv_optim_create: no such HIP device";
-        return MESHENV_E_HIP;
-    }
-    MeshOptim *o = new MeshOptim();
-    o->device = device;
-    o->stream = (hipStream_t)stream;
-    *out = o;
-    return MESHENV_OK;
+    return create_handle("meshenv_optim_create", device, stream, out);
 }
 
 void meshenv_optim_destroy(MeshOptim *o)
@@ -3030,14 +2904,9 @@ void meshenv_optim_destroy(MeshOptim *o)
     delete o;
 }
 
-const char *meshenv_optim_last_error(const MeshOptim *o) { return o ? o->err.c_str() : g_create_error.c_str(); }
+const char *meshenv_optim_last_error(const MeshOptim *o) { return last_error(o); }
 
-int meshenv_optim_set_stream(MeshOptim *o, void *stream)
-{
-    if (!o) return MESHENV_E_ARG;
-    o->stream = (hipStream_t)stream;
-    return MESHENV_OK;
-}
+int meshenv_optim_set_stream(MeshOptim *o, void *stream) { return set_stream(o, stream); }
 
 int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param_dev, const float *const *grad_dev,
                        float *const *exp_avg_dev, float *const *exp_avg_sq_dev, float *const *target_dev, const int64_t *n,
@@ -3045,43 +2914,43 @@ int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param
 {
     if (!o) return MESHENV_E_ARG;
     if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS)
-        return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_bind: program " + std::to_string(program) + " out of range");
+        return fail(o, MESHENV_E_ARG, "meshenv_optim_bind: program " + std::to_string(program) + " out of range");
     if (n_seg < 1 || !param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !target_dev || !n || !op || !block || !vec)
-        return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_bind: n_seg > 0 and all nine arrays are required");
+        return fail(o, MESHENV_E_ARG, "meshenv_optim_bind: n_seg > 0 and all nine arrays are required");
     int64_t n_jobs = 0;
     for (int i = 0; i < n_seg; i++) {
         const std::string at = "meshenv_optim_bind: segment " + std::to_string(i) + ": ";
         if (op[i] != kOptAdam && op[i] != kOptPolyak && op[i] != kOptAdamPolyak)
-            return opt_fail(o, MESHENV_E_ARG, at + "op " + std::to_string(op[i]));
+            return fail(o, MESHENV_E_ARG, at + "op " + std::to_string(op[i]));
         if (n[i] < 1 || n[i] > INT32_MAX - kOptChunk)
-            return opt_fail(o, MESHENV_E_ARG, at + std::to_string((long long)n[i]) + " elements");
-        if (block[i] < 0 || block[i] >= kOptBlocks) return opt_fail(o, MESHENV_E_ARG, at + "block " + std::to_string(block[i]));
+            return fail(o, MESHENV_E_ARG, at + std::to_string((long long)n[i]) + " elements");
+        if (block[i] < 0 || block[i] >= kOptBlocks) return fail(o, MESHENV_E_ARG, at + "block " + std::to_string(block[i]));
         const bool adam = op[i] & kOptAdam, polyak = op[i] & kOptPolyak;
         if (!param_dev[i] || adam != (grad_dev[i] != nullptr) || adam != (exp_avg_dev[i] != nullptr) ||
             adam != (exp_avg_sq_dev[i] != nullptr) || polyak != (target_dev[i] != nullptr))
-            return opt_fail(o, MESHENV_E_ARG, at + "the pointers do not match op " + std::to_string(op[i]));
+            return fail(o, MESHENV_E_ARG, at + "the pointers do not match op " + std::to_string(op[i]));
         const uintptr_t all = (uintptr_t)param_dev[i] | (uintptr_t)grad_dev[i] | (uintptr_t)exp_avg_dev[i] |
                               (uintptr_t)exp_avg_sq_dev[i] | (uintptr_t)target_dev[i];
-        if (all & 3) return opt_fail(o, MESHENV_E_ARG, at + "a pointer is not 4-byte aligned");
+        if (all & 3) return fail(o, MESHENV_E_ARG, at + "a pointer is not 4-byte aligned");
         if (vec[i] != 0 && (vec[i] != 1 || (all & 15)))
-            return opt_fail(o, MESHENV_E_ARG, at + "vec = " + std::to_string(vec[i]) + " on pointers that are not all 16-byte aligned");
+            return fail(o, MESHENV_E_ARG, at + "vec = " + std::to_string(vec[i]) + " on pointers that are not all 16-byte aligned");
         n_jobs += (n[i] + kOptChunk - 1) / kOptChunk;
     }
-    if (n_jobs > INT32_MAX) return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_bind: more than 2^31 - 1 workgroups");
+    if (n_jobs > INT32_MAX) return fail(o, MESHENV_E_ARG, "meshenv_optim_bind: more than 2^31 - 1 workgroups");
     const size_t jobs_at = ((size_t)n_seg * sizeof(OptSeg) + 15) / 16 * 16;
     const size_t bytes = jobs_at + (size_t)n_jobs * sizeof(OptJob);
     OptProgram &P = o->prog[program];
     DeviceGuard guard(o->device);
-    if (guard.err != hipSuccess) return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipSetDevice failed");
+    if (guard.err != hipSuccess) return fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipSetDevice failed");
     // the staging block is free once its last upload is done; work on another stream may still read the tables
     if (o->used && o->last_stream != o->stream && hipStreamSynchronize(o->last_stream) != hipSuccess)
-        return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipStreamSynchronize failed");
+        return fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipStreamSynchronize failed");
     if (P.copied && hipEventSynchronize(P.copied) != hipSuccess)
-        return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipEventSynchronize failed");
+        return fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipEventSynchronize failed");
     P.bound = false;
     if (bytes > P.cap) {
         if (o->used && hipStreamSynchronize(o->stream) != hipSuccess)     // a launch in flight reads the old tables
-            return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipStreamSynchronize failed");
+            return fail(o, MESHENV_E_HIP, "meshenv_optim_bind: hipStreamSynchronize failed");
         if (P.dev) (void)hipFree(P.dev);
         if (P.host) (void)hipHostFree(P.host);
         P.dev = P.host = nullptr;
@@ -3089,7 +2958,7 @@ int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param
         const size_t cap = bytes + bytes / 2;
         if (hipMalloc((void **)&P.dev, cap) != hipSuccess || hipHostMalloc((void **)&P.host, cap, hipHostMallocDefault) != hipSuccess ||
             (!P.copied && hipEventCreateWithFlags(&P.copied, hipEventDisableTiming) != hipSuccess))
-            return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: allocation failed");
+            return fail(o, MESHENV_E_HIP, "meshenv_optim_bind: allocation failed");
         P.cap = cap;
     }
     OptSeg *segs = reinterpret_cast<OptSeg *>(P.host);
@@ -3101,7 +2970,7 @@ int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param
     }
     if (hipMemcpyAsync(P.dev, P.host, bytes, hipMemcpyHostToDevice, o->stream) != hipSuccess ||
         hipEventRecord(P.copied, o->stream) != hipSuccess)
-        return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_bind: upload failed");
+        return fail(o, MESHENV_E_HIP, "meshenv_optim_bind: upload failed");
     o->last_stream = P.ordered = o->stream;
     o->used = true;
     P.jobs_at = jobs_at;
@@ -3114,23 +2983,23 @@ int meshenv_optim_step(MeshOptim *o, int program, const MeshOptimScalars *scalar
 {
     if (!o) return MESHENV_E_ARG;
     if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || !scalars)
-        return opt_fail(o, MESHENV_E_ARG, "meshenv_optim_step: program out of range or no scalars");
+        return fail(o, MESHENV_E_ARG, "meshenv_optim_step: program out of range or no scalars");
     OptProgram &P = o->prog[program];
-    if (!P.bound) return opt_fail(o, MESHENV_E_STATE, "meshenv_optim_step: program " + std::to_string(program) + " is not bound (meshenv_optim_bind)");
+    if (!P.bound) return fail(o, MESHENV_E_STATE, "meshenv_optim_step: program " + std::to_string(program) + " is not bound (meshenv_optim_bind)");
     DeviceGuard guard(o->device);
-    if (guard.err != hipSuccess) return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipSetDevice failed");
+    if (guard.err != hipSuccess) return fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipSetDevice failed");
     if (P.ordered != o->stream) {           // the tables were uploaded on another stream: order this one after the upload
         if (hipStreamWaitEvent(o->stream, P.copied, 0) != hipSuccess)
-            return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipStreamWaitEvent failed");
+            return fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipStreamWaitEvent failed");
         P.ordered = o->stream;
     }
     o->last_stream = o->stream;
     OptScalars S;
     std::memcpy(&S, scalars, sizeof(S));
-    hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
-                       (const OptJob *)(P.dev + P.jobs_at), S);
-    if (hipGetLastError() != hipSuccess) return opt_fail(o, MESHENV_E_HIP, "meshenv_optim_step: launch failed");
-    return MESHENV_OK;
+    return launch(o, guard, "meshenv_optim_step", [&] {
+        hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
+                           (const OptJob *)(P.dev + P.jobs_at), S);
+    });
 }
 
 }  // extern "C"

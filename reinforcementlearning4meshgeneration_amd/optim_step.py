@@ -22,6 +22,8 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import _capi
+from ._handle import Handle
+from .sb3_nets import check_device
 
 CHUNK = _capi.OPTIM_CHUNK            # elements per workgroup
 THREADS = 256
@@ -313,16 +315,8 @@ class OptimStepSpec:
         return cls.sac(critic.optimizer, actor.optimizer, ent, _params(critic), _params(critic_target), model.tau)
 
     def check_device(self, device) -> None:
-        for opt in self.optimizers():
-            for p in opt.param_groups[0]["params"]:
-                if p.device != device:
-                    raise ValueError(f"a parameter of shape {tuple(p.shape)} is on {p.device}; FusedOptimStep binds float32 "
-                                     f"contiguous CUDA tensors on {device}")
-        for p, t in self.pairs:
-            for x in (p, t):
-                if x.device != device:
-                    raise ValueError(f"a Polyak tensor of shape {tuple(x.shape)} is on {x.device}; FusedOptimStep binds float32 "
-                                     f"contiguous CUDA tensors on {device}")
+        check_device([p for opt in self.optimizers() for p in opt.param_groups[0]["params"]], device, "FusedOptimStep")
+        check_device([x for pair in self.pairs for x in pair], device, "FusedOptimStep", "Polyak tensor")
 
 
 def _params(module) -> list:
@@ -349,25 +343,14 @@ def _no_batch_norm(model, name) -> None:
                 raise ValueError(f"{name}.{who} has batch-norm running statistics ({found[0]}, ...); networks with batch norm are not supported")
 
 
-class FusedOptimStep:
+class FusedOptimStep(Handle):
     """An OptimStepSpec bound on one GPU: critic_step(), actor_step(polyak=True), polyak(); one launch each on the current
     stream, no synchronisation while the tensors' pointers stay what they were."""
+    PREFIX = "meshenv_optim"
 
     def __init__(self, spec: OptimStepSpec, device: int = 0):
-        import torch
-        self._torch = torch
-        self._L = _capi.load()
-        if not torch.cuda.is_available():
-            raise _capi.MeshEnvError("FusedOptimStep needs a ROCm GPU")
         self.spec = spec
-        self.device = torch.device("cuda", device)
-        spec.check_device(self.device)
-        self._h = C.c_void_p()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.meshenv_optim_create(device, C.c_void_p(stream), C.byref(self._h))
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_optim_create failed ({rc}): {self._L.meshenv_optim_last_error(None).decode()}")
-        self._stream = stream
+        super().__init__(device, check_device=spec.check_device)
         self._bound = {}              # program -> the pointers its device tables hold
         self.binds = 0                # uploads so far: stays put in the steady state
 
@@ -385,18 +368,6 @@ class FusedOptimStep:
     @classmethod
     def from_sb3(cls, model, device: int = 0):
         return cls(OptimStepSpec.from_sb3(model), device)
-
-    # ---------------------------------------------------------------- plumbing
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self._L.meshenv_optim_last_error(self._h)
-            raise _capi.MeshEnvError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def _bind_stream(self):
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        if stream != self._stream:
-            self._check(self._L.meshenv_optim_set_stream(self._h, C.c_void_p(stream)), "meshenv_optim_set_stream")
-            self._stream = stream
 
     def _bind(self, plan: Plan, key) -> None:
         rows = plan.rows
@@ -435,14 +406,3 @@ class FusedOptimStep:
     def polyak(self) -> None:
         """``polyak_update`` of every pair alone.  One launch."""
         self._run("polyak")
-
-    def close(self):
-        if self._h:
-            self._L.meshenv_optim_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

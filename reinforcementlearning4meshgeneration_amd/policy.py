@@ -21,6 +21,8 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _capi
+from ._handle import Handle
+from .sb3_nets import _sequential
 from .vec_env import ACTION_HIGH, ACTION_LOW
 
 KIND_ACTOR_CRITIC, KIND_DETERMINISTIC = 0, 1
@@ -46,14 +48,6 @@ def _activation(act) -> str:
     if name not in ACTIVATIONS:
         raise ValueError(f"unsupported activation {act!r}; supported: {SUPPORTED}")
     return name
-
-
-def _sequential(seq):
-    """The Linear layers and the activation of an SB3 ``create_mlp`` nn.Sequential (Linear, act, Linear, act, ...)."""
-    mods = list(seq)
-    linears = [m for m in mods if type(m).__name__ == "Linear"]
-    acts = {type(m).__name__.lower() for m in mods if type(m).__name__ != "Linear"}
-    return linears, acts
 
 
 @dataclass
@@ -156,23 +150,14 @@ class PolicySpec:
         return ptrs + [self.low.ctypes.data, self.high.ctypes.data]
 
 
-class FusedPolicy:
+class FusedPolicy(Handle):
     """A PolicySpec loaded on one GPU.  forward / sample / value return dicts of float32 CUDA tensors."""
+    PREFIX = "meshenv_policy"
+    LAST_ERROR = "meshenv_last_error"
 
     def __init__(self, spec: PolicySpec, device: int = 0):
-        import torch
-        self._torch = torch
-        self._L = _capi.load()
-        if not torch.cuda.is_available():
-            raise _capi.MeshEnvError("FusedPolicy needs a ROCm GPU")
         self.spec = spec
-        self.device = torch.device("cuda", device)
-        self._h = C.c_void_p()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.meshenv_policy_create(device, C.c_void_p(stream), C.byref(self._h))
-        if rc != 0:
-            raise _capi.MeshEnvError(f"meshenv_policy_create failed ({rc}): {self._L.meshenv_last_error(None).decode()}")
-        self._stream = stream
+        super().__init__(device)
         rc = self._L.meshenv_policy_load(self._h, spec.kind, spec.hidden, ACTIVATIONS[spec.activation], *spec.load_args())
         self._check(rc, "meshenv_policy_load")
 
@@ -192,18 +177,6 @@ class FusedPolicy:
     @classmethod
     def from_sb3(cls, policy, sigma=None, device: int = 0, low=ACTION_LOW, high=ACTION_HIGH):
         return cls(PolicySpec.from_sb3(policy, sigma, low, high), device)
-
-    # ---------------------------------------------------------------- plumbing
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self._L.meshenv_policy_last_error(self._h)
-            raise _capi.MeshEnvError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def _bind_stream(self):
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        if stream != self._stream:
-            self._check(self._L.meshenv_policy_set_stream(self._h, C.c_void_p(stream)), "meshenv_policy_set_stream")
-            self._stream = stream
 
     def _obs(self, obs):
         t = self._torch
@@ -261,14 +234,3 @@ class FusedPolicy:
         obs = self._obs(obs)
         out = dict(value=self._torch.empty(obs.shape[0], dtype=self._torch.float32, device=self.device))
         return self._launch(obs, None, False, 0, 0, out)["value"]
-
-    def close(self):
-        if self._h:
-            self._L.meshenv_policy_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,0 +1,171 @@
+"""What the fused train-step classes recognise of SB3 2.x's SAC / TD3 objects, and the checks of the LIVE parameters they
+bind: one place for every refusal.  Duck-typed (SB3 is not imported; the tests use stand-ins): layers are
+``torch.nn.Linear``-like objects (``.weight [out][in]``, ``.bias``), networks are what ``create_mlp`` builds.
+
+The networks are the ones the reference trains (rl/baselines/RL_Mesh.py:179-222): ``SUPPORTED``."""
+from __future__ import annotations
+
+from . import _capi
+
+KIND_SAC, KIND_TD3 = 0, 1
+OBS_DIM, ACT_DIM = _capi.OBS_DIM, _capi.ACT_DIM
+Q_IN = OBS_DIM + ACT_DIM
+HIDDEN = {KIND_SAC: (128, 3), KIND_TD3: (256, 2)}     # width, hidden layers
+SUPPORTED = ("SAC: ReLU [128, 128, 128] actor (mu and log_std heads) with twin ReLU [128, 128, 128] critics and either the "
+             "learned log_ent_coef tensor or a fixed ent_coef; TD3: ReLU [256, 256] tanh actor with twin ReLU [256, 256] "
+             "critics; 18 observations, 3 actions, critic input cat(obs, action) = 21; float32 contiguous parameters")
+
+
+def _refuse(what):
+    raise ValueError(f"{what}; supported: {SUPPORTED}")
+
+
+def _sequential(seq):
+    """The Linear layers and the activations of an SB3 ``create_mlp`` nn.Sequential (Linear, act, Linear, act, ...)."""
+    mods = list(seq)
+    linears = [m for m in mods if type(m).__name__ == "Linear"]
+    acts = {type(m).__name__.lower() for m in mods if type(m).__name__ != "Linear"}
+    return linears, acts
+
+
+def _param(x, what, shape):
+    """A live parameter: float32, contiguous, of the expected shape (a torch tensor: its storage is what gets bound)."""
+    if not hasattr(x, "data_ptr") or not hasattr(x, "is_contiguous"):
+        _refuse(f"{what} is {type(x).__name__}, not a torch tensor")
+    if str(x.dtype) != "torch.float32":
+        _refuse(f"{what} has dtype {x.dtype}; parameters must be float32")
+    if tuple(x.shape) != tuple(shape):
+        _refuse(f"{what} has shape {tuple(x.shape)}, expected {tuple(shape)}")
+    if not x.is_contiguous():
+        _refuse(f"{what} is not contiguous")
+    return x
+
+
+def _mlp(layers, head_layers, n_in, kind, what):
+    """[w1, b1, ..., head_w, head_b, ...] of an MLP of the kind's width and depth; each head has (name, n_out, layer)."""
+    H, NL = HIDDEN[kind]
+    layers = list(layers)
+    widths = [tuple(getattr(l.weight, "shape", ())) for l in layers]
+    if len(layers) != NL or any(w[:1] != (H,) for w in widths):
+        _refuse(f"{what}: hidden layers {[w[0] if w else None for w in widths]}")
+    out, k = [], n_in
+    for i, l in enumerate(layers):
+        out += [_param(l.weight, f"{what}[{i}].weight", (H, k)), _param(l.bias, f"{what}[{i}].bias", (H,))]
+        k = H
+    for name, n_out, l in head_layers:
+        out += [_param(l.weight, f"{what} {name}.weight", (n_out, H)), _param(l.bias, f"{what} {name}.bias", (n_out,))]
+    return out
+
+
+def _relu_linears(seq, what, at_least=0):
+    linears, acts = _sequential(seq)
+    if acts - {"relu"}:
+        _refuse(f"{what}: activations {sorted(acts)}")
+    if len(linears) < at_least:
+        _refuse(f"{what}: {len(linears)} Linear layers")
+    return linears
+
+
+def _critic(q, kind, what):
+    """A q_network: an nn.Sequential(Linear, ReLU, ..., Linear) or a list of its Linear layers."""
+    linears = _relu_linears(q, what, 2)
+    return _mlp(linears[:-1], [("output", 1, linears[-1])], Q_IN, kind, what)
+
+
+def sac_actor_params(actor_layers, mu, log_std):
+    """The ten tensors of the SAC actor in bind order: w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w log_std_b."""
+    return _mlp(actor_layers, [("mu", ACT_DIM, mu), ("log_std", ACT_DIM, log_std)], OBS_DIM, KIND_SAC, "actor")
+
+
+def twin_params(kind, q1, q2):
+    return _critic(q1, kind, "q_networks[0]"), _critic(q2, kind, "q_networks[1]")
+
+
+def critic_kind(q, what):
+    """SAC or TD3 from the widths of a q_network (the refusals of a shape that is neither come from _critic)."""
+    linears, _ = _sequential(q)
+    widths = [tuple(getattr(l.weight, "shape", ()))[:1] for l in linears[:-1]]
+    for kind, (H, NL) in HIDDEN.items():
+        if widths == [(H,)] * NL:
+            return kind
+    _refuse(f"{what}: hidden layers {[w[0] if w else None for w in widths]}")
+
+
+def _flatten_only(owner, what, shared=False):
+    fe = getattr(owner, "features_extractor", None)
+    if fe is not None and type(fe).__name__ != "FlattenExtractor":
+        how = " (share_features_extractor=True)" if shared else ""
+        _refuse(f"{what}.features_extractor{how} is {type(fe).__name__}; only the MLP policies' FlattenExtractor is supported")
+
+
+def twin_critics(model, attr, who="SAC / TD3", ddpg=False):
+    """The two q_networks of ``model.<attr>`` (``critic``: the live ones, ``critic_target``).  who: the algorithms the caller
+    takes; ddpg: whether a single critic may be DDPG's, which the refusal then says."""
+    critic = getattr(model, attr, None)
+    if critic is None or not hasattr(critic, "q_networks"):
+        _refuse(f"{type(model).__name__} has no {attr}.q_networks: not an SB3 {who} model")
+    qs = list(critic.q_networks)
+    n_critics = int(getattr(critic, "n_critics", len(qs)))
+    if n_critics != 2 or len(qs) != 2:
+        hint = " (DDPG: one critic, no twin minimum)" if ddpg and n_critics == 1 else ""
+        _refuse(f"{attr}.n_critics = {n_critics}{hint}; the twin critics of {who} (n_critics = 2) are supported")
+    _flatten_only(critic, attr, shared=bool(getattr(critic, "share_features_extractor", False)))
+    return qs
+
+
+def sac_actor(actor, what="actor"):
+    """The hidden Linear layers of an SB3 SAC ``Actor`` (``latent_pi``; its heads are ``actor.mu`` / ``actor.log_std``)."""
+    _flatten_only(actor, what)
+    if getattr(actor, "use_sde", False):
+        _refuse(f"{what}.use_sde=True (gSDE actor) is not supported")
+    linears = _relu_linears(actor.latent_pi, f"{what}.latent_pi")
+    if type(actor.log_std).__name__ != "Linear":
+        _refuse(f"{what}.log_std is {type(actor.log_std).__name__}, not a Linear head (gSDE?)")
+    return linears
+
+
+def td3_actor(actor, what="actor_target"):
+    """(hidden Linear layers, output Linear) of an SB3 TD3 ``Actor``: ``mu`` = Sequential(Linear, ReLU, ..., Linear, Tanh)."""
+    _flatten_only(actor, what)
+    mods = list(actor.mu)
+    if not mods or type(mods[-1]).__name__ != "Tanh":
+        _refuse(f"{what}.mu must end in Tanh (SB3's TD3 actor)")
+    linears = _relu_linears(mods[:-1], f"{what}.mu", 2)
+    return linears[:-1], linears[-1]
+
+
+def finite(x, what) -> float:
+    v = float(x)
+    if not v == v or abs(v) == float("inf"):
+        raise ValueError(f"{what} must be finite, got {x!r}")
+    return v
+
+
+def ent_coef(log_ent_coef, ent_coef):
+    """(the learned [1] tensor or None, the fixed coefficient or 0.0): SAC takes exactly one of the two."""
+    if (log_ent_coef is None) == (ent_coef is None):
+        _refuse("SAC needs exactly one of log_ent_coef (the learned tensor) and ent_coef (a fixed float)")
+    if log_ent_coef is None:
+        return None, finite(ent_coef, "ent_coef")
+    if not hasattr(log_ent_coef, "numel") or log_ent_coef.numel() != 1:
+        _refuse(f"log_ent_coef must be a tensor of one element, got {log_ent_coef!r}")
+    return _param(log_ent_coef, "log_ent_coef", tuple(log_ent_coef.shape)), 0.0
+
+
+def model_ent_coef(model) -> dict:
+    """The keyword of an SB3 SAC model's entropy coefficient: ``log_ent_coef`` (ent_coef="auto") or ``ent_coef``."""
+    lec = getattr(model, "log_ent_coef", None)
+    if lec is not None:
+        return dict(log_ent_coef=lec)
+    fixed = getattr(model, "ent_coef_tensor", None)
+    if fixed is None:
+        _refuse("the SAC model has neither log_ent_coef nor ent_coef_tensor")
+    return dict(ent_coef=float(fixed))
+
+
+def check_device(tensors, device, who, what="parameter") -> None:
+    """Every bound tensor lives on `device` (a torch.device): the kernels read them through raw pointers."""
+    for x in tensors:
+        if x.device != device:
+            raise ValueError(f"a {what} of shape {tuple(x.shape)} is on {x.device}; {who} binds float32 contiguous CUDA tensors "
+                             f"on {device}")

@@ -519,10 +519,7 @@ class MeshVecEnv:
             self._act_pp = [t.empty((self.num_envs, 3), dtype=t.float32, device=self.device) for _ in range(2)]
         nxt = self._act_pp[0] if actions.data_ptr() != self._act_pp[0].data_ptr() else self._act_pp[1]
         self._bind_stream()
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        if stream != actor._stream:
-            actor._L.meshenv_actor_set_stream(actor._h, C.c_void_p(stream))
-            actor._stream = stream
+        actor._bind_stream()
         rc = self._L.meshenv_step_actor(self._handle, actor._h, actions.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
                                         self.done.data_ptr(), self.complete.data_ptr(), self.terminal_obs.data_ptr(),
                                         1 if self.auto_reset else 0, 1 if sample else 0, C.c_uint64(seed & (2 ** 64 - 1)),
@@ -551,10 +548,7 @@ class MeshVecEnv:
         if want_eps:
             out["eps"] = t.empty((T, n, 3), dtype=t.float32, device=self.device)
         self._bind_stream()
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        if stream != actor._stream:
-            actor._L.meshenv_actor_set_stream(actor._h, C.c_void_p(stream))
-            actor._stream = stream
+        actor._bind_stream()
         rc = self._L.meshenv_step_actor_multi(self._handle, actor._h, T, acts.data_ptr(), out["obs"].data_ptr(), out["reward"].data_ptr(),
                                           out["done"].data_ptr(), out["complete"].data_ptr(),
                                           out["terminal_obs"].data_ptr() if want_terminal_obs else None,
@@ -719,12 +713,7 @@ class MeshVecEnv:
         for k, v in buf.items():
             setattr(B, k, v.data_ptr())
         self._bind_stream()
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        if pol is not None:
-            pol._bind_stream()
-        elif stream != act._stream:
-            act._L.meshenv_actor_set_stream(act._h, C.c_void_p(stream))
-            act._stream = stream
+        (pol if pol is not None else act)._bind_stream()
         steps, short = C.c_int32(0), C.c_int32(0)
         rc = self._L.meshenv_evaluate(self._handle, pol._h if pol is not None else None, act._h if act is not None else None,
                                       0 if deterministic else 1, C.c_uint64(seed & (2 ** 64 - 1)),

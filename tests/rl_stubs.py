@@ -135,3 +135,54 @@ def wrap_env(env):
         if name in sys.modules and isinstance(env, sys.modules[name].Env):
             return "env"
     raise TypeError(f"{type(env).__name__} is neither a VecEnv nor a gym Env")
+
+
+# ---------------------------------------------------------------------------------------- SAC / TD3 models, as SB3 lays them out
+def _extractor(name="FlattenExtractor"):
+    import torch
+    return type(name, (torch.nn.Module,), {})()
+
+
+def _mlp_seq(n_in, H, nl, act):
+    import torch
+    dims = [n_in] + [H] * nl
+    return [m for i in range(nl) for m in (torch.nn.Linear(dims[i], dims[i + 1]), act())]
+
+
+def twin_critic(H=128, nl=3, n=2, act=None):
+    """What SB3's ContinuousCritic exposes: q_networks (Sequential(Linear, act, ..., Linear(H, 1))), n_critics, the extractor."""
+    import torch
+    act = act or torch.nn.ReLU
+    qs = [torch.nn.Sequential(*_mlp_seq(21, H, nl, act), torch.nn.Linear(H, 1)) for _ in range(n)]
+    return types.SimpleNamespace(q_networks=qs, n_critics=n, features_extractor=_extractor(), share_features_extractor=False)
+
+
+def sac_model(H=128, nl=3, act=None, learned=True, n_critics=2):
+    """An SB3-2.x-shaped SAC model: actor (latent_pi, mu, log_std), critic, critic_target, the entropy coefficient."""
+    import copy
+
+    import torch
+    act = act or torch.nn.ReLU
+    actor = types.SimpleNamespace(latent_pi=torch.nn.Sequential(*_mlp_seq(18, H, nl, act)), mu=torch.nn.Linear(H, 3),
+                                  log_std=torch.nn.Linear(H, 3), use_sde=False, features_extractor=_extractor())
+    critic = twin_critic(H, nl, n_critics)
+    m = types.SimpleNamespace(actor=actor, critic=critic, critic_target=copy.deepcopy(critic), gamma=0.99, target_entropy=-3.0,
+                              log_ent_coef=None, ent_coef_tensor=None)
+    if learned:
+        m.log_ent_coef = torch.zeros(1).requires_grad_(True)
+    else:
+        m.ent_coef_tensor = torch.tensor(0.1)
+    return m
+
+
+def td3_model(H=256, nl=2, n_critics=2):
+    """An SB3-2.x-shaped TD3 model: actor / actor_target (mu ending in Tanh), critic, critic_target."""
+    import copy
+
+    import torch
+    def actor():
+        return types.SimpleNamespace(mu=torch.nn.Sequential(*_mlp_seq(18, H, nl, torch.nn.ReLU), torch.nn.Linear(H, 3), torch.nn.Tanh()),
+                                     features_extractor=_extractor())
+    critic = twin_critic(H, nl, n_critics)
+    return types.SimpleNamespace(actor=actor(), actor_target=actor(), critic=critic, critic_target=copy.deepcopy(critic), gamma=0.98,
+                                 target_policy_noise=0.2, target_noise_clip=0.5)
