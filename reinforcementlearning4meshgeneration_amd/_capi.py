@@ -1,4 +1,4 @@
-"""ctypes binding of libmeshenv_hip.so (include/meshenv.h).  Fails loudly when the library is missing:
+"""ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -75,6 +75,13 @@ EXPORTS_OPTIM = [
 ]
 OPTIM_PROGRAMS, OPTIM_BLOCKS, OPTIM_CHUNK = 8, 4, 1024
 OPTIM_ADAM, OPTIM_POLYAK, OPTIM_ADAM_POLYAK = 1, 2, 3
+
+# every symbol include/meshenv_td3_actor_grad.h declares (meshenv_actor_grad_* of meshenv.h is the SAC statement)
+EXPORTS_TD3_ACTOR_GRAD = [
+    "meshenv_td3_actor_grad_create", "meshenv_td3_actor_grad_destroy", "meshenv_td3_actor_grad_set_stream",
+    "meshenv_td3_actor_grad_last_error", "meshenv_td3_actor_grad_bind", "meshenv_td3_actor_grad_backward",
+]
+TD3_ACTOR_GRAD_FLOATS = 71488
 
 
 class MeshOptimScalars(C.Structure):
@@ -179,7 +186,7 @@ def load():
     for prefix, extra, has_last_error in (("meshenv_actor", [], False), ("meshenv_policy", [], True),
                                           ("meshenv_target", [C.c_int, f32, f32, f32, f32], True),
                                           ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
-                                          ("meshenv_optim", [], True)):
+                                          ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -214,12 +221,15 @@ def load():
     L.meshenv_critic_grad_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.meshenv_actor_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, vp, vp, C.c_int64]
     L.meshenv_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    L.meshenv_td3_actor_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int64]
+    L.meshenv_td3_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.meshenv_optim_bind.argtypes = [vp, C.c_int, C.c_int] + [C.POINTER(vp)] * 5 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 3
     L.meshenv_optim_step.argtypes = [vp, C.c_int, C.POINTER(MeshOptimScalars)]
     for name in ("meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
                  "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",
-                 "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample"):
+                 "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample", "meshenv_td3_actor_grad_bind",
+                 "meshenv_td3_actor_grad_backward"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_reset_static", "meshenv_move", "meshenv_get_not_valid", "meshenv_set_stream", "meshenv_num_envs", "meshenv_max_ring", "meshenv_reset", "meshenv_step",
                  "meshenv_rollout", "meshenv_get_status", "meshenv_get_state", "meshenv_get_elements",

@@ -89,7 +89,7 @@ class ActorGradSpec:
         if not hasattr(actor, "latent_pi"):
             if hasattr(getattr(model, "actor_target", None), "mu") or hasattr(actor, "mu"):
                 raise ValueError(f"{type(model).__name__} is a TD3 / DDPG model (a deterministic actor without latent_pi): "
-                                 "not yet: SAC only")
+                                 "not yet: SAC only (FusedTD3ActorGrad computes TD3's actor loss gradient)")
             raise ValueError(f"{type(model).__name__} has no actor.latent_pi: not an SB3 SAC model")
         qs = N.twin_critics(model, "critic", who="SAC")
         te = getattr(model, "target_entropy", None)

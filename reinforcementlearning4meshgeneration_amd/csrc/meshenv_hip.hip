@@ -5,6 +5,7 @@
 // entry point fails with MESHENV_E_HIP.
 #include "../../include/meshenv.h"
 #include "../../include/meshenv_optim.h"
+#include "../../include/meshenv_td3_actor_grad.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -31,6 +32,7 @@
 #include "meshenv_target.h"
 #include "meshenv_critic_grad.h"
 #include "meshenv_actor_grad.h"
+#include "meshenv_td3_actor_grad.h"
 #include "meshenv_optim.h"
 
 using namespace meshenv;
@@ -232,7 +234,8 @@ int fail_arg(MeshEnv *h, const char *msg)
     return MESHENV_E_ARG;
 }
 
-// ---- what the handles of the fused networks share (MeshActor, MeshPolicy, MeshTarget, MeshCriticGrad, MeshActorGrad, MeshOptim)
+// ---- what the handles of the fused networks share (MeshActor, MeshPolicy, MeshTarget, MeshCriticGrad, MeshActorGrad, MeshTd3ActorGrad,
+// MeshOptim)
 struct HandleBase {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -2857,6 +2860,102 @@ int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, c
     return launch(g, guard, "meshenv_actor_grad_backward", [&] {
         hipLaunchKernelGGL(k_actor_grad_reduce, dim3((AgLayout::ent + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial,
                            A.nwg, n, g->log_ent_coef, g->grad, losses_dev);
+    }, "reduction launch");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ TD3 / DDPG actor loss gradients
+static_assert(MESHENV_TD3_ACTOR_GRAD_FLOATS == TaLayout::stride, "include/meshenv_td3_actor_grad.h and csrc/meshenv_td3_actor_grad.h disagree");
+
+struct MeshTd3ActorGrad : HandleBase {
+    const float *w[3]{}, *b[3]{};   // the actor
+    CgCritic c{};                   // the first critic
+    float *grad = nullptr;          // the caller's flat gradient buffer (TaLayout::stride floats)
+    float *partial = nullptr;       // kCgMaxGroups partial sets, zeroed once
+    bool bound = false;
+};
+
+extern "C" {
+
+int meshenv_td3_actor_grad_create(int device, void *stream, MeshTd3ActorGrad **out)
+{
+    return create_handle("meshenv_td3_actor_grad_create", device, stream, out);
+}
+
+void meshenv_td3_actor_grad_destroy(MeshTd3ActorGrad *g) { destroy_handle(g, g ? g->partial : nullptr); }
+
+const char *meshenv_td3_actor_grad_last_error(const MeshTd3ActorGrad *g) { return last_error(g); }
+
+int meshenv_td3_actor_grad_set_stream(MeshTd3ActorGrad *g, void *stream) { return set_stream(g, stream); }
+
+int meshenv_td3_actor_grad_bind(MeshTd3ActorGrad *g, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
+                                int n_critic, float *grad_dev, int64_t n_grad)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!actor_dev || !q1_dev || n_actor != 6 || n_critic != 6)
+        return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: takes 6 actor tensors and 6 tensors of the first critic (TD3 / "
+                       "DDPG: actor ReLU [256, 256] with a Linear(256, 3) + Tanh head, critic ReLU [256, 256], float32)");
+    if (!grad_dev || n_grad != TaLayout::stride)
+        return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: the gradient buffer has " + std::to_string(TaLayout::stride) +
+                       " floats, got " + std::to_string((long long)n_grad));
+    for (int i = 0; i < 6; i++) {
+        if (!actor_dev[i] || !q1_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: null tensor");
+        // the [H][H] weights, the head's [3][H] and the critic's output [1][H] weights are read 16 bytes at a time
+        if (i % 2 == 0 && i >= 2 && (((uintptr_t)actor_dev[i] | (uintptr_t)q1_dev[i]) & 15))
+            return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_td3_actor_grad_bind: hipSetDevice failed");
+    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * TaLayout::set))
+        return fail(g, MESHENV_E_HIP, "meshenv_td3_actor_grad_bind: allocation failed");
+    for (int l = 0; l < 3; l++) {
+        g->w[l] = actor_dev[2 * l];
+        g->b[l] = actor_dev[2 * l + 1];
+        g->c.w[l] = q1_dev[2 * l];
+        g->c.b[l] = q1_dev[2 * l + 1];
+    }
+    g->grad = grad_dev;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_td3_actor_grad_backward(MeshTd3ActorGrad *g, int n, const float *obs_dev, float *loss_dev, float *const *parts_dev,
+                                    float *const *acts_dev)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_td3_actor_grad_backward: no tensors bound (meshenv_td3_actor_grad_bind)");
+    if (n <= 0 || n > (1 << 24) - 16 || !obs_dev || !loss_dev)   // the kernel's 32-bit offsets reach row * 256
+        return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_backward: 0 < n <= 2^24 - 16, obs_dev and loss_dev are required");
+    TaArgs A{};
+    A.n = n;
+    A.nwg = grad_groups(n);
+    A.obs = obs_dev;
+    for (int l = 0; l < 3; l++) {
+        A.w[l] = g->w[l];
+        A.b[l] = g->b[l];
+    }
+    A.c = g->c;
+    A.partial = g->partial;
+    if (parts_dev) {
+        for (int i = 0; i < kTaParts; i++)
+            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_backward: null per-sample output");
+        A.actions = parts_dev[0]; A.q = parts_dev[1]; A.dq_da = parts_dev[2]; A.d_pre = parts_dev[3];
+    }
+    if (acts_dev) {
+        for (int i = 0; i < 4; i++) {
+            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_backward: null activation output");
+            A.acts[i / 2][i % 2] = acts_dev[i];
+        }
+    }
+    DeviceGuard guard(g->device);
+    const int rc = launch(g, guard, "meshenv_td3_actor_grad_backward", [&] {
+        hipLaunchKernelGGL(k_td3_actor_grad, dim3(A.nwg, kCgSplitTD3), dim3(1024), 0, g->stream, A);
+    });
+    if (rc != MESHENV_OK) return rc;
+    return launch(g, guard, "meshenv_td3_actor_grad_backward", [&] {
+        hipLaunchKernelGGL(k_td3_actor_grad_reduce, dim3((TaLayout::params + 255) / 256), dim3(256), 0, g->stream,
+                           (const float *)g->partial, A.nwg, n, g->grad, loss_dev);
     }, "reduction launch");
 }
 

@@ -113,6 +113,39 @@ def twin_critics(model, attr, who="SAC / TD3", ddpg=False):
     return qs
 
 
+def first_critic(model, attr="critic", who="FusedTD3ActorGrad"):
+    """``q_networks[0]`` of ``model.<attr>`` for n_critics >= 1: what TD3's / DDPG's ``critic.q1_forward`` evaluates."""
+    critic = getattr(model, attr, None)
+    if critic is None or not hasattr(critic, "q_networks"):
+        _refuse(f"{type(model).__name__} has no {attr}.q_networks: not an SB3 TD3 / DDPG model")
+    qs = list(critic.q_networks)
+    n_critics = int(getattr(critic, "n_critics", len(qs)))
+    if n_critics < 1 or len(qs) < 1:
+        _refuse(f"{attr}.n_critics = {n_critics}; {who} reads q_networks[0]")
+    _flatten_only(critic, attr, shared=bool(getattr(critic, "share_features_extractor", False)))
+    return qs[0]
+
+
+def td3_live_actor(model):
+    """(hidden Linear layers, output Linear) of the LIVE actor of an SB3 TD3 / DDPG model (``model.actor``, not
+    ``actor_target``); a SAC model is refused with the name of the class that takes it."""
+    actor = getattr(model, "actor", None)
+    if hasattr(actor, "latent_pi"):
+        _refuse(f"{type(model).__name__} is a SAC model (actor.latent_pi): FusedActorGrad computes SAC's actor loss gradient")
+    if not hasattr(actor, "mu"):
+        _refuse(f"{type(model).__name__} has no actor.mu: not an SB3 TD3 / DDPG model")
+    mods = list(actor.mu)
+    tail = type(mods[-1]).__name__ if mods else "nothing"
+    if tail != "Tanh":
+        _refuse(f"actor.mu ends in {tail}; SB3's TD3 actor ends in Tanh")
+    return td3_actor(actor, "actor")
+
+
+def td3_actor_params(actor_layers, mu):
+    """The six tensors of the TD3 actor in bind order: w1 b1 w2 b2 w3 b3."""
+    return _mlp(actor_layers, [("mu", ACT_DIM, mu)], OBS_DIM, KIND_TD3, "actor")
+
+
 def sac_actor(actor, what="actor"):
     """The hidden Linear layers of an SB3 SAC ``Actor`` (``latent_pi``; its heads are ``actor.mu`` / ``actor.log_std``)."""
     _flatten_only(actor, what)

@@ -1,0 +1,235 @@
+"""Host only: the fp64 restatement of the TD3 / DDPG actor-loss kernel (tests/td3_actor_grad_ref.py) against torch float64
+autograd of SB3's statement; its bound against a second fp32 evaluation and against named mistakes; the conditions of every
+case the GPU test uses; TD3ActorGradSpec on SB3-shaped stub models; the exports of the header of its own."""
+import copy
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import policy_ref as R
+import td3_actor_grad_ref as A
+
+GPU_BS = (1, 15, 16, 17, 100, 256, 4101)          # tests/test_gpu_td3_actor_grad.py
+STRESS_MAX_B = 256
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def rows():
+    return R.input_rows()
+
+
+def _torch_f64(m, obs):
+    """SB3's statement transcribed in float64 on copies of the CPU modules, with autograd."""
+    d = lambda l: copy.deepcopy(l).double()   # noqa: E731
+    lin, mu, q1 = [d(l) for l in m["lin"]], d(m["mu"]), [d(l) for l in m["q1"]]
+    x = torch.from_numpy(obs).double()
+    h = x
+    for l in lin:
+        h = torch.relu(l(h))
+    pre = mu(h)
+    pre.retain_grad()
+    a = torch.tanh(pre)
+    a.retain_grad()
+    hc = torch.cat([x, a], dim=1)
+    for l in q1[:-1]:
+        hc = torch.relu(l(hc))
+    q = q1[-1](hc)
+    actor_loss = -q.mean()
+    actor_loss.backward()
+    B = obs.shape[0]
+    out = {"actor_loss": actor_loss.detach().numpy(), "actions_pi": a.detach().numpy(), "q1_pi": q.detach().numpy()[:, 0],
+           "dq_da": -a.grad.numpy() * B, "d_pre": pre.grad.numpy(), "mu.w": mu.weight.grad.numpy(), "mu.b": mu.bias.grad.numpy()}
+    for i, l in enumerate(lin):
+        out[f"a.w{i}"], out[f"a.b{i}"] = l.weight.grad.numpy(), l.bias.grad.numpy()
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------- 1. autograd
+@pytest.mark.parametrize("stress", [False, True], ids=["default", "stress"])
+@pytest.mark.parametrize("B", [1, 17, 100])
+def test_restatement_equals_float64_autograd(rows, B, stress):
+    m = A.modules(stress)
+    obs, _ = A.batch(B, rows)
+    ref, _ = A.td3_actor_grad(m, obs)
+    want = _torch_f64(m, obs)
+    assert set(want) == set(ref)
+    for k, v in want.items():
+        r = ref[k][0]
+        scale = max(float(np.abs(r).max()), float(np.abs(v).max()), 1e-30)
+        diff = float(np.abs(v.reshape(r.shape) - r).max())
+        assert diff <= 1e-9 * scale, (k, diff, scale)
+
+
+# ----------------------------------------------------------------------------------------------------------- 2. admits fp32
+@pytest.mark.parametrize("stress", [False, True], ids=["default", "stress"])
+def test_bound_admits_a_pairwise_fp32_evaluation_and_the_conditions_hold(rows, stress):
+    """At every B of the GPU test: the conditions from the reference alone, then the second fp32 evaluation inside the bound."""
+    m = A.modules(stress)
+    top_a = top_c = 0.0
+    for B in GPU_BS:
+        if stress and B > STRESS_MAX_B:
+            continue
+        what = f"{'stress' if stress else 'default'} B={B}"
+        obs, _ = A.batch(B, rows)
+        got = A.td3_actor_grad_f32(m, obs)
+        ref, info = A.td3_actor_grad(m, obs, other=got)
+        print(f"{what}: {A.describe(info)}")
+        A.assert_conditions(info, what, stress=stress)
+        A.assert_choices(info, got, what)
+        worst = {}
+        A.assert_all_within(got, ref, f"{what} fp32", worst)
+        assert set(worst) == set(ref) and max(worst.values()) > 0.0          # not a comparison of the reference with itself
+        top_a, top_c = max(top_a, info["actor_share"]), max(top_c, info["critic_share"])
+        if stress:
+            a = ref["actions_pi"][0]
+            assert (1.0 - a[:, [0, 2]] ** 2 < 1e-9).all() and (np.abs(a[:, 1]) < 0.9999).any()     # saturated, and not
+    # what the issue recorded for these inputs
+    assert top_a <= 5.4e-5 * 1.0001 and top_c <= (4.9e-4 if stress else 2.8e-4) * 1.0001, (top_a, top_c)
+
+
+# ----------------------------------------------------------------------------------------------------------- 3. rejects mistakes
+@pytest.mark.parametrize("mutant", A.MUTANTS)
+def test_bound_rejects_mistakes(rows, mutant):
+    B = 17 if mutant == "tail_rows" else 100
+    m = A.modules(stress=mutant in A.STRESS_MUTANTS)
+    obs, _ = A.batch(B, rows)
+    ref, _ = A.td3_actor_grad(m, obs)
+    bad, _ = A.td3_actor_grad(m, obs, mutant=mutant)
+    out = A.outside({k: v[0] for k, v in bad.items()}, ref)
+    assert out, f"the bound admits the mutant {mutant}"
+    assert not A.outside({k: v[0] for k, v in ref.items()}, ref)
+
+
+def test_chain_lengths_are_the_kernels():
+    """_back's chain: ta_da walks the 16 groups of 16 neurons two at a time, one accumulator each, so an accumulator takes
+    8 groups x 16 = 128 = H / 2 products; the header says so in its own words."""
+    assert A.BACK_CHAIN == 129 and A.HEAD_CHAIN == 3
+    src = open(os.path.join(ROOT, "reinforcementlearning4meshgeneration_amd", "csrc", "meshenv_td3_actor_grad.h")).read()
+    assert "for (int g = 0; g < G; g += 2)" in src and "one product and two fmaf" in src
+
+
+# ----------------------------------------------------------------------------------------------------------- 4. TD3ActorGradSpec
+class FlattenExtractor(torch.nn.Module):
+    pass
+
+
+class NatureCNN(torch.nn.Module):
+    pass
+
+
+def _q(Hq=256, nl=2):
+    dims = [21] + [Hq] * nl
+    mods = [x for i in range(nl) for x in (torch.nn.Linear(dims[i], dims[i + 1]), torch.nn.ReLU())]
+    return torch.nn.Sequential(*mods, torch.nn.Linear(Hq, 1))
+
+
+def _critic(Hq=256, nl=2, n=2):
+    return types.SimpleNamespace(q_networks=[_q(Hq, nl) for _ in range(n)], n_critics=n, features_extractor=FlattenExtractor(),
+                                 share_features_extractor=False)
+
+
+def _td3_model(n_critics=2, Ha=256, nl=2, tail=torch.nn.Tanh, act=torch.nn.ReLU, **kw):
+    dims = [18] + [Ha] * nl
+    mods = [x for i in range(nl) for x in (torch.nn.Linear(dims[i], dims[i + 1]), act())]
+
+    def actor():
+        return types.SimpleNamespace(mu=torch.nn.Sequential(*copy.deepcopy(mods), torch.nn.Linear(Ha, 3), tail()),
+                                     features_extractor=FlattenExtractor())
+    critic = _critic(n=n_critics, **kw)
+    return types.SimpleNamespace(actor=actor(), actor_target=actor(), critic=critic, critic_target=copy.deepcopy(critic), gamma=0.98)
+
+
+def _sac_model():
+    latent = torch.nn.Sequential(*[x for i in range(3) for x in (torch.nn.Linear(18 if i == 0 else 128, 128), torch.nn.ReLU())])
+    actor = types.SimpleNamespace(latent_pi=latent, mu=torch.nn.Linear(128, 3), log_std=torch.nn.Linear(128, 3), use_sde=False,
+                                  features_extractor=FlattenExtractor())
+    critic = _critic(128, 3)
+    return types.SimpleNamespace(actor=actor, critic=critic, critic_target=copy.deepcopy(critic), gamma=0.99,
+                                 log_ent_coef=torch.zeros(1, requires_grad=True), target_entropy=-3.0)
+
+
+def test_spec_accepts_td3_and_ddpg_and_lays_out_the_buffer():
+    from reinforcementlearning4meshgeneration_amd.td3_actor_grad import TD3ActorGradSpec
+    for n_critics in (2, 1):                                                      # TD3, and DDPG with its one critic
+        m = _td3_model(n_critics)
+        s = TD3ActorGradSpec.from_sb3(m)
+        assert len(s.actor) == 6 and len(s.q1) == 6 and len(s.tensors()) == 12
+        assert s.actor[0] is m.actor.mu[0].weight and s.actor[4] is m.actor.mu[4].weight and s.actor[5] is m.actor.mu[4].bias
+        assert s.actor[0] is not m.actor_target.mu[0].weight                      # the LIVE actor
+        assert s.q1[0] is m.critic.q_networks[0][0].weight and s.q1[5] is m.critic.q_networks[0][4].bias
+        assert s.q1[0] is not m.critic_target.q_networks[0][0].weight            # and the LIVE critic
+        assert [at for _, at in s.offsets()] == [0, 4608, 4864, 70400, 70656, 71424] and s.n_grad == 71488
+        assert [p for p, _ in s.offsets()] == s.actor
+    t = A.modules()
+    s = TD3ActorGradSpec.td3(t["lin"], t["mu"], t["q1"])
+    assert s.actor[0] is t["lin"][0].weight and s.q1[4] is t["q1"][2].weight and s.n_grad == 71488
+    from reinforcementlearning4meshgeneration_amd import _capi
+    assert _capi.TD3_ACTOR_GRAD_FLOATS == s.n_grad
+    header = open(os.path.join(ROOT, "include", "meshenv_td3_actor_grad.h")).read()
+    assert "#define MESHENV_TD3_ACTOR_GRAD_FLOATS 71488" in header
+
+
+def _refused(model, *words):
+    from reinforcementlearning4meshgeneration_amd.td3_actor_grad import TD3ActorGradSpec
+    with pytest.raises(ValueError) as e:
+        TD3ActorGradSpec.from_sb3(model)
+    for w in words:
+        assert w in str(e.value), (w, str(e.value))
+
+
+def test_spec_refusals_name_what_was_found():
+    from reinforcementlearning4meshgeneration_amd.td3_actor_grad import FusedTD3ActorGrad, TD3ActorGradSpec
+    _refused(_sac_model(), "SAC", "FusedActorGrad")
+    _refused(_td3_model(Ha=128, nl=3), "[128, 128, 128]")                          # other widths
+    _refused(_td3_model(Ha=400, nl=2), "[400, 400]")
+    _refused(_td3_model(Hq=128, nl=2), "[128, 128]")
+    _refused(_td3_model(tail=torch.nn.Sigmoid), "Sigmoid", "Tanh")                 # a non-Tanh head
+    _refused(_td3_model(act=torch.nn.Tanh), "tanh")
+    _refused(_td3_model(n_critics=0), "n_critics = 0")
+    m = _td3_model(); m.actor.features_extractor = NatureCNN(); _refused(m, "NatureCNN", "actor.features_extractor")
+    m = _td3_model(); m.critic.features_extractor = NatureCNN(); _refused(m, "NatureCNN", "critic.features_extractor")
+    _refused(types.SimpleNamespace(policy=None), "actor.mu")
+    m = _td3_model(); del m.critic; _refused(m, "critic.q_networks")
+    m = _td3_model(); m.actor.mu = m.actor.mu.double(); _refused(m, "float64")
+    m = _td3_model(); m.critic.q_networks[0] = m.critic.q_networks[0].double(); _refused(m, "float64")
+    m = _td3_model(); m.actor.mu[2].weight = torch.nn.Parameter(torch.zeros(256, 512)[:, ::2]); _refused(m, "not contiguous")
+    m = _td3_model(); m.actor.mu[4].weight = torch.nn.Parameter(torch.zeros(3, 64)); _refused(m, "(3, 64)")
+    m = _td3_model(); m.critic.q_networks[1] = m.critic.q_networks[1].double()     # the second critic is not read
+    TD3ActorGradSpec.from_sb3(m)
+    spec = TD3ActorGradSpec.from_sb3(_td3_model())
+    with pytest.raises(ValueError, match="is on cpu"):
+        spec.check_device(torch.device("cuda", 0))
+    if not torch.cuda.is_available():
+        from reinforcementlearning4meshgeneration_amd import _capi
+        with pytest.raises(_capi.MeshEnvError):      # no CPU fallback
+            FusedTD3ActorGrad(spec)
+
+
+def test_the_sac_class_still_refuses_td3():
+    from reinforcementlearning4meshgeneration_amd.actor_grad import ActorGradSpec
+    for n in (2, 1):
+        with pytest.raises(ValueError, match="not yet: SAC only"):
+            ActorGradSpec.from_sb3(_td3_model(n))
+
+
+# ----------------------------------------------------------------------------------------------------------- 5. packaging
+def test_exported_lazily_declared_and_built():
+    import reinforcementlearning4meshgeneration_amd as pkg
+    from reinforcementlearning4meshgeneration_amd import _capi, build
+    assert pkg.FusedTD3ActorGrad.__name__ == "FusedTD3ActorGrad" and pkg.TD3ActorGradSpec.__name__ == "TD3ActorGradSpec"
+    assert "FusedTD3ActorGrad" in pkg.__all__ and "TD3ActorGradSpec" in pkg.__all__
+    names = _capi.EXPORTS_TD3_ACTOR_GRAD
+    assert sorted(names) == sorted("meshenv_td3_actor_grad_" + s for s in ("create", "destroy", "set_stream", "last_error", "bind", "backward"))
+    assert not set(names) & set(_capi.EXPORTS) and not set(names) & set(_capi.EXPORTS_OPTIM)
+    header = open(os.path.join(ROOT, "include", "meshenv_td3_actor_grad.h")).read()
+    assert sorted(set(re.findall(r"\b(meshenv_td3_actor_grad_[a-z_]+)\s*\(", header))) == sorted(names)
+    L = _capi.load()
+    for name in names:
+        assert hasattr(L, name), name
+        assert getattr(L, name).argtypes is not None or name.endswith("last_error"), name
+    assert "meshenv_td3_actor_grad.h" in build.PUBLIC_HEADERS

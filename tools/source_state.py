@@ -1,4 +1,4 @@
-"""What library a profile describes: sha256 over csrc/ + include/meshenv.h + include/meshenv_optim.h, the library's own hash, and whether the library
+"""What library a profile describes: sha256 over csrc/ + the public headers of include/, the library's own hash, and whether the library
 is older than its sources.  `python tools/source_state.py` prints it as JSON; `--require-fresh` exits 1 when the shipped .so is
 older than any source (tools/profile_round.sh / profile_set.sh refuse to profile such a library).  tools/summarize_profile.py and
 summarize_set.py compare the recorded source hash with the working tree and, where .git exists, refuse to summarise when
@@ -8,7 +8,7 @@ import hashlib, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "reinforcementlearning4meshgeneration_amd")
 CSRC = os.path.join(PKG, "csrc")
-PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h"]      # build.py's list
+PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h", "meshenv_td3_actor_grad.h"]      # build.py's list
 
 
 def source_files():
