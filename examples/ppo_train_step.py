@@ -1,0 +1,91 @@
+#!/usr/bin/env python
+"""One PPO (or A2C) iteration that stays on the device: rollout -> GAE -> epochs x minibatches of loss gradient and optimiser
+step -> refresh of the rollout policy.
+
+    env.collect_rollout(policy, T, gamma=...)     FusedPolicy + k_gae: what SB3's RolloutBuffer stores
+    pg.backward(...)                              FusedPPOGrad: evaluate_actions, the losses, backward, clip_grad_norm_
+    model.policy.optimizer.step()                 the stock torch optimiser on the p.grad the call left
+    policy.refresh()                              the stepped parameters into the rollout policy's packed weights
+
+``model`` is anything shaped like SB3 2.x's PPO / A2C (``.policy`` an ActorCriticPolicy with ``.optimizer``); the
+hyper-parameters are read from it at every call, as SB3 reads its schedules.  Without stable_baselines3 installed the script
+builds a stand-in of the reference's PPO recipe (rl/baselines/RL_Mesh.py:113-139: ReLU [128, 128] x 2).
+
+    python examples/ppo_train_step.py [--a2c] [--iterations 3] [--n-envs 256] [--n-steps 32]"""
+import argparse
+import os
+import sys
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from reinforcementlearning4meshgeneration_amd import FusedPolicy, FusedPPOGrad, MeshVecEnv, boundary  # noqa: E402
+
+
+def stand_in(a2c: bool):
+    """An SB3-shaped model on the GPU: PPO ReLU [128, 128] x 2, or SB3's default A2C Tanh [64, 64]."""
+    H, act = (64, torch.nn.Tanh) if a2c else (128, torch.nn.ReLU)
+    seq = lambda: torch.nn.Sequential(torch.nn.Linear(18, H), act(), torch.nn.Linear(H, H), act()).cuda()   # noqa: E731
+    fe = type("FlattenExtractor", (torch.nn.Module,), {})()
+    pol = types.SimpleNamespace(mlp_extractor=types.SimpleNamespace(policy_net=seq(), value_net=seq()),
+                                action_net=torch.nn.Linear(H, 3).cuda(), value_net=torch.nn.Linear(H, 1).cuda(),
+                                log_std=torch.nn.Parameter(torch.zeros(3, device="cuda")), use_sde=False, squash_output=False,
+                                features_extractor=fe, pi_features_extractor=fe, vf_features_extractor=fe,
+                                share_features_extractor=True)
+    params = [p for m in (pol.mlp_extractor.policy_net, pol.mlp_extractor.value_net, pol.action_net, pol.value_net)
+              for p in m.parameters()] + [pol.log_std]
+    pol.optimizer = (torch.optim.RMSprop(params, lr=7e-4, alpha=0.99, eps=1e-5) if a2c else torch.optim.Adam(params, lr=3e-4, eps=1e-5))
+    return types.SimpleNamespace(policy=pol, gamma=0.99, gae_lambda=1.0 if a2c else 0.95, clip_range=None if a2c else (lambda _: 0.2),
+                                 clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=not a2c,
+                                 n_epochs=1 if a2c else 10, batch_size=None if a2c else 256, target_kl=None,
+                                 _current_progress_remaining=1.0)
+
+
+def train_iteration(model, env, policy, pg, n_steps, counter):
+    """SB3's collect_rollouts + train() for one rollout.  Nothing in here synchronises with the host."""
+    out = env.collect_rollout(policy, n_steps, seed=0, counter=counter, gamma=model.gamma, gae_lambda=model.gae_lambda)
+    rows = n_steps * env.num_envs
+    flat = {k: out[k].reshape(rows, *out[k].shape[2:]) for k in ("obs", "buffer_actions", "log_prob", "advantages", "returns")}
+    clip_range = None if model.clip_range is None else float(model.clip_range(model._current_progress_remaining))
+    batch = model.batch_size or rows
+    last = None
+    for _ in range(model.n_epochs):
+        perm = torch.randperm(rows, device=flat["obs"].device)                  # RolloutBuffer.get's shuffle
+        for start in range(0, rows, batch):
+            idx = perm[start:start + batch]
+            last = pg.backward(observations=flat["obs"][idx], actions=flat["buffer_actions"][idx], old_log_prob=flat["log_prob"][idx],
+                               advantages=flat["advantages"][idx], returns=flat["returns"][idx], clip_range=clip_range,
+                               ent_coef=model.ent_coef, vf_coef=model.vf_coef, normalize_advantage=model.normalize_advantage,
+                               max_grad_norm=model.max_grad_norm)
+            if model.target_kl is not None and float(last["approx_kl"]) > 1.5 * model.target_kl:    # A SYNCHRONISATION (SB3's early stop)
+                policy.refresh()
+                return last
+            model.policy.optimizer.step()
+    policy.refresh()                                                            # after the last minibatch of the last epoch
+    return last
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--a2c", action="store_true")
+    ap.add_argument("--iterations", type=int, default=3)
+    ap.add_argument("--n-envs", type=int, default=256)
+    ap.add_argument("--n-steps", type=int, default=32)
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    model = stand_in(args.a2c)
+    env = MeshVecEnv([boundary(0)], n_envs=args.n_envs)
+    env.reset()
+    policy = FusedPolicy.from_sb3(model)
+    policy.bind_live(model)
+    pg = FusedPPOGrad.from_sb3(model)
+    for it in range(args.iterations):
+        last = train_iteration(model, env, policy, pg, args.n_steps, counter=it * args.n_steps)
+        print(f"iteration {it}: " + " ".join(f"{k}={float(v):.5f}" for k, v in last.items()))     # outside the loop: reads back
+    pg.close(); policy.close(); env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -8,7 +8,8 @@ from .domains import boundary, domain_constants, generate_polygon, random_domain
 __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygon", "domain_constants", "generate_polygon",
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
            "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
-           "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec"]
+           "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
+           "FusedPPOGrad", "PPOGradSpec"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -51,4 +52,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedTD3ActorGrad", "TD3ActorGradSpec"):
         from . import td3_actor_grad
         return getattr(td3_actor_grad, name)
+    if name in ("FusedPPOGrad", "PPOGradSpec"):
+        from . import ppo_grad
+        return getattr(ppo_grad, name)
     raise AttributeError(name)

@@ -1,4 +1,5 @@
-"""ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h).  Fails loudly when the library is missing:
+"""ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
+meshenv_ppo_grad.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -82,6 +83,14 @@ EXPORTS_TD3_ACTOR_GRAD = [
     "meshenv_td3_actor_grad_last_error", "meshenv_td3_actor_grad_bind", "meshenv_td3_actor_grad_backward",
 ]
 TD3_ACTOR_GRAD_FLOATS = 71488
+
+# every symbol include/meshenv_ppo_grad.h declares: the PPO / A2C statement, and the refresh of a loaded policy from its live tensors
+EXPORTS_PPO_GRAD = [
+    "meshenv_ppo_grad_create", "meshenv_ppo_grad_destroy", "meshenv_ppo_grad_set_stream", "meshenv_ppo_grad_last_error",
+    "meshenv_ppo_grad_bind", "meshenv_ppo_grad_backward", "meshenv_policy_bind", "meshenv_policy_refresh",
+]
+PPO_GRAD_FLOATS = {64: 11072, 128: 38464}
+PPO_GRAD_OUTPUTS, PPO_GRAD_PARTS = 8, 5
 
 
 class MeshOptimScalars(C.Structure):
@@ -186,7 +195,8 @@ def load():
     for prefix, extra, has_last_error in (("meshenv_actor", [], False), ("meshenv_policy", [], True),
                                           ("meshenv_target", [C.c_int, f32, f32, f32, f32], True),
                                           ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
-                                          ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True)):
+                                          ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True),
+                                          ("meshenv_ppo_grad", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -223,13 +233,19 @@ def load():
     L.meshenv_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.meshenv_td3_actor_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int64]
     L.meshenv_td3_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    L.meshenv_ppo_grad_bind.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int64]
+    L.meshenv_ppo_grad_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_double, f32, f32, C.c_int, C.c_int, f32, vp,
+                                            C.POINTER(vp), C.POINTER(vp)]
+    L.meshenv_policy_bind.argtypes = [vp, C.POINTER(vp), C.c_int]
+    L.meshenv_policy_refresh.argtypes = [vp]
     L.meshenv_optim_bind.argtypes = [vp, C.c_int, C.c_int] + [C.POINTER(vp)] * 5 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 3
     L.meshenv_optim_step.argtypes = [vp, C.c_int, C.POINTER(MeshOptimScalars)]
     for name in ("meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
                  "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",
                  "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample", "meshenv_td3_actor_grad_bind",
-                 "meshenv_td3_actor_grad_backward"):
+                 "meshenv_td3_actor_grad_backward", "meshenv_ppo_grad_bind", "meshenv_ppo_grad_backward", "meshenv_policy_bind",
+                 "meshenv_policy_refresh"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_reset_static", "meshenv_move", "meshenv_get_not_valid", "meshenv_set_stream", "meshenv_num_envs", "meshenv_max_ring", "meshenv_reset", "meshenv_step",
                  "meshenv_rollout", "meshenv_get_status", "meshenv_get_state", "meshenv_get_elements",

@@ -6,6 +6,7 @@
 #include "../../include/meshenv.h"
 #include "../../include/meshenv_optim.h"
 #include "../../include/meshenv_td3_actor_grad.h"
+#include "../../include/meshenv_ppo_grad.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -33,6 +34,7 @@
 #include "meshenv_critic_grad.h"
 #include "meshenv_actor_grad.h"
 #include "meshenv_td3_actor_grad.h"
+#include "meshenv_ppo_grad.h"
 #include "meshenv_optim.h"
 
 using namespace meshenv;
@@ -1966,6 +1968,9 @@ struct MeshPolicy : HandleBase {
     PolicyWeights W{};
     int kind = -1, hidden = 0, activation = 0;
     bool loaded = false;
+    PackTable table{};     // meshenv_policy_bind: the live tensors and where meshenv_policy_refresh packs them
+    int n_copies = 0;
+    bool live = false;
 };
 
 namespace {
@@ -2082,6 +2087,7 @@ int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, con
     if (p->buf) (void)hipFree(p->buf);
     p->buf = nullptr;
     p->loaded = false;
+    p->live = false;       // the copy table points into the buffer that was freed
     if (hipMalloc((void **)&p->buf, h.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(p->buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(p, MESHENV_E_HIP, "meshenv_policy_load: upload failed");
@@ -2957,6 +2963,200 @@ int meshenv_td3_actor_grad_backward(MeshTd3ActorGrad *g, int n, const float *obs
         hipLaunchKernelGGL(k_td3_actor_grad_reduce, dim3((TaLayout::params + 255) / 256), dim3(256), 0, g->stream,
                            (const float *)g->partial, A.nwg, n, g->grad, loss_dev);
     }, "reduction launch");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ PPO / A2C loss gradients
+static_assert(MESHENV_PPO_GRAD_FLOATS_64 == PgLayout<64>::stride && MESHENV_PPO_GRAD_FLOATS_128 == PgLayout<128>::stride,
+              "include/meshenv_ppo_grad.h and csrc/meshenv_ppo_grad.h disagree");
+static_assert(MESHENV_PPO_GRAD_OUTPUTS == kPgOut && MESHENV_PPO_GRAD_PARTS == kPgParts, "include/meshenv_ppo_grad.h and csrc/meshenv_ppo_grad.h disagree");
+
+struct MeshPpoGrad : HandleBase {
+    PgTower t[2]{};
+    const float *log_std = nullptr;
+    float *grad = nullptr;          // the caller's flat gradient buffer (PgLayout::stride floats)
+    float *partial = nullptr;       // kCgMaxGroups partial sets of the widest layout, then the advantage statistics; zeroed once
+    int hidden = 0, activation = 0;
+    bool bound = false;
+};
+
+namespace {
+
+typedef void (*PpoGradKernel)(PgArgs);
+
+// the four instantiations: [hidden 64 / 128][activation]
+PpoGradKernel ppo_grad_kernel(int hidden, int activation)
+{
+    static const PpoGradKernel table[2][2] = {{k_ppo_grad<64, kPolicyReLU>, k_ppo_grad<64, kPolicyTanh>},
+                                              {k_ppo_grad<128, kPolicyReLU>, k_ppo_grad<128, kPolicyTanh>}};
+    return table[hidden == 64 ? 0 : 1][activation];
+}
+
+const char *kPpoGradShapes = "supported: pi and vf towers of two hidden layers of the same width 64 or 128, activation 0 (ReLU) or 1 "
+                             "(Tanh), action_net [3], value_net [1], log_std [3], 18 observations, float32";
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_ppo_grad_create(int device, void *stream, MeshPpoGrad **out)
+{
+    return create_handle("meshenv_ppo_grad_create", device, stream, out);
+}
+
+void meshenv_ppo_grad_destroy(MeshPpoGrad *g) { destroy_handle(g, g ? g->partial : nullptr); }
+
+const char *meshenv_ppo_grad_last_error(const MeshPpoGrad *g) { return last_error(g); }
+
+int meshenv_ppo_grad_set_stream(MeshPpoGrad *g, void *stream) { return set_stream(g, stream); }
+
+int meshenv_ppo_grad_bind(MeshPpoGrad *g, int hidden, int activation, const float *const *tensors_dev, int n_tensors,
+                          float *grad_dev, int64_t n_grad)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (hidden == 256)
+        return fail(g, MESHENV_E_ARG, std::string("meshenv_ppo_grad_bind: width 256 is not supported (its dW_2 needs the column split "
+                                                  "of the TD3 critic kernel); ") + kPpoGradShapes);
+    if ((hidden != 64 && hidden != 128) || (activation != kPolicyReLU && activation != kPolicyTanh))
+        return fail(g, MESHENV_E_ARG, std::string("meshenv_ppo_grad_bind: unsupported shape; ") + kPpoGradShapes);
+    if (!tensors_dev || n_tensors != kPgTensors)
+        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: takes 13 tensors: pi w1 b1 w2 b2 wh bh, vf w1 b1 w2 b2 wh bh, log_std");
+    const int want = hidden == 64 ? PgLayout<64>::stride : PgLayout<128>::stride;
+    if (!grad_dev || n_grad != want)
+        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: the gradient buffer has " + std::to_string(want) + " floats at width " +
+                       std::to_string(hidden) + ", got " + std::to_string((long long)n_grad));
+    for (int i = 0; i < kPgTensors; i++) {
+        if (!tensors_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: null tensor");
+        // the [H][H] weights and the heads' [n_out][H] weights are read 16 bytes at a time
+        if ((i == 2 || i == 4 || i == 8 || i == 10) && ((uintptr_t)tensors_dev[i] & 15))
+            return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_ppo_grad_bind: hipSetDevice failed");
+    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * PgLayout<128>::set + 64))
+        return fail(g, MESHENV_E_HIP, "meshenv_ppo_grad_bind: allocation failed");
+    for (int tower = 0; tower < 2; tower++)
+        for (int l = 0; l < 3; l++) {
+            g->t[tower].w[l] = tensors_dev[6 * tower + 2 * l];
+            g->t[tower].b[l] = tensors_dev[6 * tower + 2 * l + 1];
+        }
+    g->log_std = tensors_dev[12];
+    g->grad = grad_dev;
+    g->hidden = hidden;
+    g->activation = activation;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_ppo_grad_backward(MeshPpoGrad *g, int n, const float *obs_dev, const float *actions_dev, const float *old_log_prob_dev,
+                              const float *advantages_dev, const float *returns_dev, int a2c, double clip_range, float ent_coef,
+                              float vf_coef, int normalize_advantage, int clip_grad, float max_grad_norm, float *out_dev,
+                              float *const *parts_dev, float *const *acts_dev)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_ppo_grad_backward: no tensors bound (meshenv_ppo_grad_bind)");
+    if (n <= 0 || n > (1 << 24) - 16 || !obs_dev || !actions_dev || !advantages_dev || !returns_dev || !out_dev)   // 32-bit offsets reach row * 128
+        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: 0 < n <= 2^24 - 16 and obs, actions, advantages, returns and out are required");
+    if (!a2c && !old_log_prob_dev) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: PPO's loss needs old_log_prob_dev");
+    if (!std::isfinite(clip_range) || !std::isfinite(ent_coef) || !std::isfinite(vf_coef) || !std::isfinite(max_grad_norm) ||
+        (!a2c && !(clip_range > 0.0)) || (clip_grad && !(max_grad_norm > 0.0f)))
+        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: clip_range and max_grad_norm must be finite and > 0, ent_coef and vf_coef finite");
+    const int H = g->hidden;
+    const int set = H == 64 ? PgLayout<64>::set : PgLayout<128>::set, stride = H == 64 ? PgLayout<64>::stride : PgLayout<128>::stride;
+    const int params = H == 64 ? PgLayout<64>::params : PgLayout<128>::params;
+    float *stats = g->partial + (size_t)kCgMaxGroups * PgLayout<128>::set;
+    PgArgs A{};
+    A.n = n;
+    A.nwg = grad_groups(n);
+    A.a2c = a2c ? 1 : 0;
+    A.normalize = normalize_advantage && n > 1 ? 1 : 0;
+    A.obs = obs_dev; A.actions = actions_dev; A.old_log_prob = old_log_prob_dev; A.adv = advantages_dev; A.returns = returns_dev;
+    A.stats = stats;
+    // torch clamps a float32 tensor against the Python floats 1 - clip_range and 1 + clip_range, formed in double and then
+    // rounded to float32, and compares |ratio - 1| with float32(clip_range): clip_range arrives as the double SB3 holds
+    A.lo = (float)(1.0 - clip_range); A.hi = (float)(1.0 + clip_range); A.clip = (float)clip_range; A.vf_coef = vf_coef;
+    A.t[0] = g->t[0]; A.t[1] = g->t[1];
+    A.log_std = g->log_std;
+    A.partial = g->partial;
+    if (parts_dev) {
+        for (int i = 0; i < kPgParts; i++)
+            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: null per-row output");
+        A.log_prob = parts_dev[0]; A.ratio = parts_dev[1]; A.values = parts_dev[2]; A.advn = parts_dev[3]; A.pass = parts_dev[4];
+    }
+    if (acts_dev) {
+        for (int i = 0; i < 4; i++) {
+            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: null activation output");
+            A.acts[i / 2][i % 2] = acts_dev[i];
+        }
+    }
+    DeviceGuard guard(g->device);
+    const char *fn = "meshenv_ppo_grad_backward";
+    int rc = MESHENV_OK;
+    if (A.normalize) {
+        rc = launch(g, guard, fn, [&] {
+            hipLaunchKernelGGL(k_ppo_adv_stats, dim3(1), dim3(kPgStatThreads), 0, g->stream, advantages_dev, n, stats);
+        }, "statistics launch");
+        if (rc != MESHENV_OK) return rc;
+    }
+    rc = launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(ppo_grad_kernel(H, g->activation), dim3(A.nwg, 2), dim3(4 * H), 0, g->stream, A);
+    });
+    if (rc != MESHENV_OK) return rc;
+    rc = launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((params + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg, set,
+                           stride, params, n, ent_coef, vf_coef, g->log_std, clip_grad ? 1 : 0, g->grad, out_dev);
+    }, "reduction launch");
+    if (rc != MESHENV_OK || !clip_grad) return rc;
+    return launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(k_ppo_grad_clip, dim3(1), dim3(kPgStatThreads), 0, g->stream, g->grad, H, max_grad_norm, out_dev);
+    }, "clip launch");
+}
+
+// ---- live weights into a loaded FusedPolicy (the on-policy twin of meshenv_target_bind / meshenv_target_refresh)
+int meshenv_policy_bind(MeshPolicy *p, const float *const *tensors_dev, int n_tensors)
+{
+    if (!p) return MESHENV_E_ARG;
+    if (!p->loaded) return fail(p, MESHENV_E_STATE, "meshenv_policy_bind: no weights loaded (meshenv_policy_load lays the buffer out)");
+    const bool ac = p->kind == kPolicyActorCritic;
+    const int want = ac ? kPgTensors : 6;
+    if (!tensors_dev || n_tensors != want)
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_bind: the " + std::string(ac ? "actor-critic" : "deterministic") + " kind takes " +
+                       std::to_string(want) + " tensors (pi w1 b1 w2 b2 wh bh" + (ac ? ", vf likewise, log_std)" : ")"));
+    for (int i = 0; i < want; i++)
+        if (!tensors_dev[i]) return fail(p, MESHENV_E_ARG, "meshenv_policy_bind: null tensor");
+    const int H = p->hidden, G = H / 16;
+    p->n_copies = 0;
+    auto add = [&](const float *src, const float *dst, int out, int in, int groups, int tiles, int kind) {
+        PackCopy &c = p->table.c[p->n_copies++];
+        c.src = src; c.dst = const_cast<float *>(dst); c.out = out; c.in = in; c.groups = groups; c.tiles = tiles; c.n_off = 0; c.kind = kind;
+    };
+    auto tower = [&](const PolicyTower &T, const float *const *t, int n_out) {
+        add(t[0], T.w1p, H, kObsDim, kPolInPad / 16, G, kPackMatrix); add(t[1], T.b1, H, 0, 0, 0, kPackVector);
+        add(t[2], T.w2p, H, H, G, G, kPackMatrix); add(t[3], T.b2, H, 0, 0, 0, kPackVector);
+        add(t[4], T.whp, n_out, H, G, 1, kPackMatrix); add(t[5], T.bh, n_out, 0, 0, 0, kPackVector);
+    };
+    tower(p->W.pi, tensors_dev, 3);
+    if (ac) {
+        tower(p->W.vf, tensors_dev + 6, 1);
+        add(tensors_dev[12], p->W.aux, 3, 0, 0, 0, kPackVector);
+    }
+    static_assert(kPgTensors <= kTgtMaxCopies, "the copy table holds the 13 sources");
+    p->live = true;
+    return MESHENV_OK;
+}
+
+int meshenv_policy_refresh(MeshPolicy *p)
+{
+    if (!p) return MESHENV_E_ARG;
+    if (!p->loaded || !p->live) return fail(p, MESHENV_E_STATE, "meshenv_policy_refresh: no tensors bound (meshenv_policy_bind)");
+    const int H = p->hidden;   // the largest copy is an H x H matrix: H * H / 256 blocks cover it in one pass
+    DeviceGuard guard(p->device);
+    // k_target_pack (meshenv_target.h) is the pack kernel: the table of meshenv_policy_bind has every n_off = 0, and what it
+    // does not write (the padding of K and of the head tile) meshenv_policy_load left zero
+    return launch(p, guard, "meshenv_policy_refresh", [&] {
+        hipLaunchKernelGGL(k_target_pack, dim3(H * H / 256, p->n_copies), dim3(256), 0, p->stream, p->table);
+    });
 }
 
 }  // extern "C"

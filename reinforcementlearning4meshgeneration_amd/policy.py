@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _capi
 from ._handle import Handle
+from . import sb3_nets as N
 from .sb3_nets import _sequential
 from .vec_env import ACTION_HIGH, ACTION_LOW
 
@@ -177,6 +178,31 @@ class FusedPolicy(Handle):
     @classmethod
     def from_sb3(cls, policy, sigma=None, device: int = 0, low=ACTION_LOW, high=ACTION_HIGH):
         return cls(PolicySpec.from_sb3(policy, sigma, low, high), device)
+
+    # ---------------------------------------------------------------- live parameters
+    def bind_live(self, policy) -> None:
+        """Record the LIVE parameters of ``policy`` (an SB3 ActorCriticPolicy, or a PPO / A2C object through ``.policy``) so
+        that refresh() can carry them into this object's packed weights: what SB3 does implicitly when collect_rollouts reads
+        the parameters ``policy.optimizer.step()`` has just written.  The shapes and the activation must be the loaded ones
+        and the tensors on this device.  Again after anything that reallocates the parameters (``.to()``)."""
+        if self.spec.kind != KIND_ACTOR_CRITIC:
+            raise ValueError("bind_live takes an actor-critic policy; the deterministic kind is rebuilt with from_sb3")
+        H, act, params = N.actor_critic_live(policy, widths=HIDDEN_WIDTHS)
+        if H != self.spec.hidden or act != self.spec.activation:
+            raise ValueError(f"the live policy is {act} [{H}, {H}]; this FusedPolicy was loaded as {self.spec.activation} "
+                             f"[{self.spec.hidden}, {self.spec.hidden}]")
+        N.check_device(params, self.device, "FusedPolicy.bind_live")
+        rc = self._L.meshenv_policy_bind(self._h, self._ptrs(params), len(params))
+        self._check(rc, "meshenv_policy_bind")
+        self._live = params      # keeps the storages alive
+
+    def refresh(self) -> None:
+        """The bound parameters, as they are now, into the packed weights: one launch on the current stream, no host copy, no
+        synchronisation.  Launches that follow on the same stream see the new weights."""
+        if getattr(self, "_live", None) is None:
+            raise ValueError("refresh() needs bind_live(policy) first")
+        self._bind_stream()
+        self._check(self._L.meshenv_policy_refresh(self._h), "meshenv_policy_refresh")
 
     def _obs(self, obs):
         t = self._torch

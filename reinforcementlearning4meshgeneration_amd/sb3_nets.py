@@ -1,5 +1,5 @@
-"""What the fused train-step classes recognise of SB3 2.x's SAC / TD3 objects, and the checks of the LIVE parameters they
-bind: one place for every refusal.  Duck-typed (SB3 is not imported; the tests use stand-ins): layers are
+"""What the fused train-step classes recognise of SB3 2.x's SAC / TD3 / PPO / A2C objects, and the checks of the LIVE
+parameters they bind: one place for every refusal.  Duck-typed (SB3 is not imported; the tests use stand-ins): layers are
 ``torch.nn.Linear``-like objects (``.weight [out][in]``, ``.bias``), networks are what ``create_mlp`` builds.
 
 The networks are the ones the reference trains (rl/baselines/RL_Mesh.py:179-222): ``SUPPORTED``."""
@@ -28,16 +28,17 @@ def _sequential(seq):
     return linears, acts
 
 
-def _param(x, what, shape):
+def _param(x, what, shape, refuse=None):
     """A live parameter: float32, contiguous, of the expected shape (a torch tensor: its storage is what gets bound)."""
+    refuse = refuse or _refuse
     if not hasattr(x, "data_ptr") or not hasattr(x, "is_contiguous"):
-        _refuse(f"{what} is {type(x).__name__}, not a torch tensor")
+        refuse(f"{what} is {type(x).__name__}, not a torch tensor")
     if str(x.dtype) != "torch.float32":
-        _refuse(f"{what} has dtype {x.dtype}; parameters must be float32")
+        refuse(f"{what} has dtype {x.dtype}; parameters must be float32")
     if tuple(x.shape) != tuple(shape):
-        _refuse(f"{what} has shape {tuple(x.shape)}, expected {tuple(shape)}")
+        refuse(f"{what} has shape {tuple(x.shape)}, expected {tuple(shape)}")
     if not x.is_contiguous():
-        _refuse(f"{what} is not contiguous")
+        refuse(f"{what} is not contiguous")
     return x
 
 
@@ -165,6 +166,92 @@ def td3_actor(actor, what="actor_target"):
         _refuse(f"{what}.mu must end in Tanh (SB3's TD3 actor)")
     linears = _relu_linears(mods[:-1], f"{what}.mu", 2)
     return linears[:-1], linears[-1]
+
+
+# ---------------------------------------------------------------------------------------- PPO / A2C: ActorCriticPolicy
+AC_GRAD_WIDTHS = (64, 128)            # what k_ppo_grad is built for; k_policy_forward also takes 256
+AC_SUPPORTED = ("an SB3 ActorCriticPolicy (PPO, A2C) with a FlattenExtractor, pi and vf towers of two hidden layers of the same "
+                "width 64 or 128 and one activation (ReLU or Tanh), action_net [3], value_net [1] and a state-independent "
+                "log_std [3] (DiagGaussianDistribution, no gSDE, no squash_output); 18 observations; float32 contiguous "
+                "parameters")
+
+
+def _refuse_ac(what):
+    raise ValueError(f"{what}; supported: {AC_SUPPORTED}")
+
+
+def actor_critic_params(pi_layers, vf_layers, action_net, value_net, log_std, activation, widths=AC_GRAD_WIDTHS):
+    """(hidden, 'relu' / 'tanh', the 13 live tensors in bind order: pi w1 b1 w2 b2 wh bh, vf likewise, log_std) of an
+    actor-critic MLP policy.  widths: the hidden widths the caller's kernels are built for."""
+    name = activation if isinstance(activation, str) else (activation.__name__ if isinstance(activation, type) else type(activation).__name__)
+    name = name.lower()
+    if name not in ("relu", "tanh"):
+        _refuse_ac(f"activation {activation!r}")
+    towers = []
+    for what, layers, head, n_out in (("pi", pi_layers, action_net, ACT_DIM), ("vf", vf_layers, value_net, 1)):
+        layers = list(layers)
+        shapes = [tuple(getattr(getattr(l, "weight", None), "shape", ())) for l in layers]
+        if len(layers) != 2 or any(len(sh) != 2 for sh in shapes):
+            _refuse_ac(f"{what} tower: hidden layers {[sh[0] if sh else None for sh in shapes]}")
+        towers.append((what, layers, head, n_out, shapes[0][0]))
+    H, Hv = towers[0][4], towers[1][4]
+    if H != Hv:
+        _refuse_ac(f"pi width {H} and vf width {Hv} differ")
+    if H == 256 and 256 not in widths:
+        _refuse_ac("width 256 is not supported by the gradient kernel (its dW_2 needs a column split that is not built)")
+    if H not in widths:
+        _refuse_ac(f"hidden width {H}")
+    out = []
+    for what, layers, head, n_out, _ in towers:
+        k = OBS_DIM
+        for i, l in enumerate(layers):
+            out += [_param(l.weight, f"{what}[{i}].weight", (H, k), _refuse_ac), _param(l.bias, f"{what}[{i}].bias", (H,), _refuse_ac)]
+            k = H
+        hn = "action_net" if what == "pi" else "value_net"
+        out += [_param(head.weight, f"{hn}.weight", (n_out, H), _refuse_ac), _param(head.bias, f"{hn}.bias", (n_out,), _refuse_ac)]
+    out.append(_param(log_std, "log_std", (ACT_DIM,), _refuse_ac))
+    return H, name, out
+
+
+def actor_critic_live(model, widths=AC_GRAD_WIDTHS):
+    """(hidden, activation, 13 tensors) of a live SB3 ``ActorCriticPolicy``: ``mlp_extractor.policy_net`` / ``.value_net``,
+    ``action_net``, ``value_net``, ``log_std``.  A ``PPO`` / ``A2C`` object is taken through its ``.policy``."""
+    policy = model
+    if not hasattr(policy, "mlp_extractor") and hasattr(policy, "policy"):
+        policy = policy.policy
+    if not hasattr(policy, "mlp_extractor"):
+        _refuse_ac(f"{type(model).__name__} has no mlp_extractor: not an SB3 ActorCriticPolicy")
+    if getattr(policy, "use_sde", False):
+        _refuse_ac("use_sde=True (gSDE: a state-dependent noise matrix in place of log_std [3])")
+    if getattr(policy, "squash_output", False):
+        _refuse_ac("squash_output=True")
+    fes = {a: getattr(policy, a, None) for a in ("features_extractor", "pi_features_extractor", "vf_features_extractor")}
+    for attr, fe in fes.items():
+        if fe is not None and type(fe).__name__ != "FlattenExtractor":
+            _refuse_ac(f"{attr} is {type(fe).__name__}; only the MLP policies' FlattenExtractor is supported")
+    if not getattr(policy, "share_features_extractor", True):
+        pf, vf = fes["pi_features_extractor"], fes["vf_features_extractor"]
+        if type(pf) is not type(vf):
+            _refuse_ac(f"share_features_extractor=False with differing extractors ({type(pf).__name__}, {type(vf).__name__})")
+    ext = policy.mlp_extractor
+    pi, pi_acts = _sequential(ext.policy_net)
+    vf, vf_acts = _sequential(ext.value_net)
+    acts = pi_acts | vf_acts
+    if len(acts) != 1:
+        _refuse_ac(f"mixed activations {sorted(acts)}")
+    for attr in ("action_net", "value_net", "log_std"):
+        if not hasattr(policy, attr):
+            _refuse_ac(f"the policy has no {attr}")
+    if type(policy.action_net).__name__ != "Linear":
+        _refuse_ac(f"action_net is {type(policy.action_net).__name__}, not a Linear (DiagGaussianDistribution's mean head)")
+    return actor_critic_params(pi, vf, policy.action_net, policy.value_net, policy.log_std, acts.pop(), widths)
+
+
+def no_value_clip(model):
+    """PPO's ``clip_range_vf`` must be None: the kernel's value loss is the plain mse_loss."""
+    crv = getattr(model, "clip_range_vf", None)
+    if crv is not None:
+        _refuse_ac(f"clip_range_vf = {crv!r} (a clipped value loss); clip_range_vf must be None")
 
 
 def finite(x, what) -> float:
