@@ -14,11 +14,26 @@ sys.path.insert(0, ROOT)
 from oracle import ref_harness as H  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
-# (fixture, domain, seed, steps, (n_neighbor, n_radius, radius, index, quality_threshold)): the two parameter sets of the callers
+# (fixture, domain, seed, steps, (n_neighbor, n_radius, radius, index, quality_threshold)): first the two parameter sets of the callers
 CASES = [
     ("samples_boundary0_ebrd", "boundary0", 1, 260, (2, 3, 4, 1, 0.7)),          # general/EBRD.py:414
     ("samples_boundary0_post", "boundary0", 9, 200, (3, 3, 6, 5, 0.7)),          # general/post_processing.py:532
     ("samples_star_ebrd", "star", 5, 120, (2, 3, 4, 1, 0.5)),
+    # every (n_neighbor, n_radius) pair, both indices, thresholds 0.0 / 0.5 / 0.7, radii 0.5 .. 6, meshes of 20 .. 66 elements,
+    # three more domains (rings of 62 / 66 / 68 vertices); radii chosen with tests/samples_host.reach so that no sector holds
+    # more than 32 vertices (n1r1 holds exactly 32) and no recording more than 20 000 samples
+    ("samples_boundary0_n1r1", "boundary0", 3, 200, (1, 1, 4, 1, 0.0)),
+    ("samples_boundary7_n1r2", "boundary7", 0, 200, (1, 2, 6, 5, 0.5)),
+    ("samples_halfwheel1_n1r3", "half_wheel1", 3, 200, (1, 3, 5, 1, 0.7)),
+    ("samples_boundary0_n1r4", "boundary0", 2, 200, (1, 4, 0.5, 5, 0.0)),
+    ("samples_boundary11_n2r1", "boundary11", 3, 200, (2, 1, 4, 1, 0.5)),
+    ("samples_boundary0_n2r2", "boundary0", 4, 200, (2, 2, 2.5, 1, 0.0)),
+    ("samples_boundary7_n2r3", "boundary7", 2, 200, (2, 3, 6, 5, 0.7)),
+    ("samples_halfwheel1_n2r4", "half_wheel1", 0, 200, (2, 4, 2.5, 1, 0.5)),
+    ("samples_boundary0_n3r1", "boundary0", 1, 200, (3, 1, 2.5, 5, 0.5)),
+    ("samples_boundary7_n3r2", "boundary7", 7, 200, (3, 2, 4, 1, 0.7)),
+    ("samples_halfwheel1_n3r3", "half_wheel1", 1, 200, (3, 3, 2, 1, 0.0)),
+    ("samples_boundary11_n3r4", "boundary11", 7, 200, (3, 4, 3, 5, 0.5)),
 ]
 
 

@@ -37,6 +37,14 @@ def _cw(s: Point, p1: Point, p2: Point) -> float:
     return round(theta, 4) if math.copysign(1, theta) >= 0 else round(2 * math.pi + theta, 4)
 
 
+def _cw_unrounded(s: Point, p1: Point, p2: Point) -> float:
+    """The value _cw rounds to 4 places."""
+    v1x, v1y = p1[0] - s[0], p1[1] - s[1]
+    v2x, v2y = p2[0] - s[0], p2[1] - s[1]
+    theta = -math.atan2(v1x * v2y - v1y * v2x, v1x * v2x + v1y * v2y)
+    return theta if math.copysign(1, theta) >= 0 else 2 * math.pi + theta
+
+
 def segment_lists(quads: np.ndarray, n_vert: int, n0: int) -> List[List[int]]:
     """get_connected_vertices() of every vertex, in the reference's order."""
     adj: List[List[int]] = [[] for _ in range(n_vert)]
@@ -136,10 +144,12 @@ def _radius_neighbors(xy, base: int, start: int, end: int, exclusion: Sequence[i
 
 
 def extract_samples_2(quads, vertex_xy, n0: int, n_neighbor: int, n_radius: int, radius: float, index: int = 1,
-                      quality_threshold: float = 0.7):
+                      quality_threshold: float = 0.7, trace=None):
     """(all_samples, types, outputs) of MeshGeneration.extract_samples_2(meshes, n_neighbor, n_radius, radius, index,
     quality_threshold) for the mesh `quads` [n_elem, 4] (global vertex ids) over `vertex_xy` [n_vert, 2] whose first n0
-    rows are the domain ring."""
+    rows are the domain ring.  trace: a list that receives, per sample, (base_length * radius, the unrounded clockwise
+    angles of the n_radius sector-tuple entries, nan where the entry is a real vertex) -- what a test needs to bound the
+    entries of the synthetic sector points."""
     quads = np.asarray(quads, np.int64).reshape(-1, 4)
     xy = [(float(x), float(y)) for x, y in np.asarray(vertex_xy, np.float64).reshape(-1, 2)]
     adj = segment_lists(quads, len(xy), n0)
@@ -171,5 +181,109 @@ def extract_samples_2(quads, vertex_xy, n0: int, n_neighbor: int, n_radius: int,
                     sample.extend([_dist(xy[rp], P(p)) / (base_length * radius), _cw(xy[rp], P(p), xy[r_p]) % two_pi])
                 outputs.append([_dist(xy[rp], xy[target]) / (base_length * radius), _cw(xy[rp], xy[target], xy[r_p]) % two_pi])
                 types.append([1] if target in rr else ([0] if target in ll else [0.5]))
+                if trace is not None:
+                    trace.append((base_length * radius, [math.nan if isinstance(p, (int, np.integer)) else
+                                                         _cw_unrounded(xy[rp], p, xy[r_p]) for p in mm]))
                 all_samples.append(sample)
     return all_samples, types, outputs
+
+
+# ------------------------------------------------------------------------------------------------ what an input reaches
+# Counting helpers for the tests: which sample counts, sector sizes and edge classes a mesh produces for given
+# parameters, without building the rows.  They restate the sector filter in its flat form (the one the kernel uses) on
+# the values _dist and _cw return; tests/test_samples_cpu.py holds `rows` against len(extract_samples_2(...)) on every
+# recording.
+def scan_corners(quads, vertex_xy, n0: int):
+    """Per (element, corner), everything that does not depend on the parameters: the four roles, the corner's angle, the
+    mean of rp's two edges, and per vertex its distance to rp (`d`) and its quantised clockwise angle from l_p (`a`; nan
+    for rp and the three excluded vertices, which no comparison then admits)."""
+    quads = np.asarray(quads, np.int64).reshape(-1, 4)
+    xy = [(float(x), float(y)) for x, y in np.asarray(vertex_xy, np.float64).reshape(-1, 2)]
+    adj = segment_lists(quads, len(xy), n0)
+    out = []
+    for e, q in enumerate(quads):
+        ev = [int(v) for v in q]
+        for i in range(4):
+            rp, l_p, r_p, target = ev[i], ev[(i + 1) % 4], ev[i - 1], ev[i - 2]
+            pb, ps = xy[rp], xy[l_p]
+            d = np.array([_dist(pb, p) for p in xy], np.float64)
+            a = np.array([_cw(pb, ps, p) for p in xy], np.float64)
+            a[[rp, l_p, r_p, target]] = np.nan
+            out.append(dict(e=e, first=i == 0, rp=rp, l_p=l_p, r_p=r_p, target=target, angle=_cw(pb, ps, xy[r_p]),
+                            edge=0.5 * _dist(pb, ps) + 0.5 * _dist(pb, xy[r_p]), d=d, a=a))
+    return dict(quads=quads, xy=xy, adj=adj, corners=out, quality={}, paths={})
+
+
+def scan_quality(scan, index: int):
+    if index not in scan["quality"]:
+        scan["quality"][index] = [element_quality([scan["xy"][int(v)] for v in q], index) for q in scan["quads"]]
+    return scan["quality"][index]
+
+
+def sector_lists(corner, n_radius: int, radius: float):
+    """The close vertices of each sector of one corner, nearest first (stable)."""
+    bl = radius * corner["edge"]
+    d, a = corner["d"], corner["a"]
+    near = d <= bl
+    out = []
+    for j in range(1, n_radius + 1):
+        sa, ea = (j - 1) * corner["angle"] / n_radius, j * corner["angle"] / n_radius
+        m = np.flatnonzero(near & (sa < a) & (a < ea))
+        out.append(m[np.argsort(d[m], kind="stable")])
+    return out
+
+
+def largest_sector(scan, n_radius: int, radius: float, index: int = 1, quality_threshold: float = -math.inf) -> int:
+    """The largest sector over the corners of the elements that extract_samples_2 takes."""
+    qual = scan_quality(scan, index)
+    return max((len(sec) for c in scan["corners"] if qual[c["e"]] >= quality_threshold
+                for sec in sector_lists(c, n_radius, radius)), default=0)
+
+
+def first_child_dead(adj, root: int, excluded: Sequence[int]) -> bool:
+    """get_nodes' shared-list case: the first second-level node has no admissible child and another node follows it."""
+    level1 = [a for a in adj[root] if a not in excluded and a != root]
+    if len(level1) < 2:
+        return False
+    a = level1[0]
+    return not [b for b in adj[a] if b not in excluded and b != root and b != a]
+
+
+def _path_counts(scan, k: int, n_neighbor: int):
+    """(right paths x left paths that make a sample, shared-list case on either side) of corner k."""
+    key = (k, n_neighbor)
+    if key not in scan["paths"]:
+        adj, c = scan["adj"], scan["corners"][k]
+        rp, l_p, r_p, target = c["rp"], c["l_p"], c["r_p"], c["target"]
+        r_paths = [p for p in neighbour_paths(adj, r_p, [rp, l_p], n_neighbor) if len(p) == n_neighbor]
+        l_paths = [p for p in neighbour_paths(adj, l_p, [rp, r_p], n_neighbor) if len(p) == n_neighbor]
+        scan["paths"][key] = (len(r_paths) * len(l_paths) - sum(target in p for p in r_paths) * sum(target in p for p in l_paths),
+                              first_child_dead(adj, r_p, [rp, l_p]) or first_child_dead(adj, l_p, [rp, r_p]))
+    return scan["paths"][key]
+
+
+def reach(scan, n_neighbor: int, n_radius: int, radius: float, index: int, quality_threshold: float):
+    """dict(rows, max_sector, dead_first, ties, edge_angles, zero_quality, min_gap) of extract_samples_2 with these
+    parameters on scan_corners(...)'s mesh: the number of samples; the largest sector; items with the shared-list case on
+    either side (it changes rows only at n_neighbor = 3); pairs of consecutive equidistant vertices in one sector;
+    within-radius vertices whose angle equals a sector's start or end angle; taken elements of quality exactly 0; the
+    smallest |quality - threshold| over the elements."""
+    qual = scan_quality(scan, index)
+    res = dict(rows=0, max_sector=0, dead_first=0, ties=0, edge_angles=0, zero_quality=0,
+               min_gap=min((abs(q - quality_threshold) for q in qual), default=math.inf))
+    for k, c in enumerate(scan["corners"]):
+        if qual[c["e"]] < quality_threshold:
+            continue
+        res["zero_quality"] += int(c["first"] and qual[c["e"]] == 0)
+        pairs, dead = _path_counts(scan, k, n_neighbor)
+        res["dead_first"] += int(dead)
+        near = c["d"] <= radius * c["edge"]
+        for j in range(n_radius + 1):
+            res["edge_angles"] += int(np.count_nonzero(near & (c["a"] == j * c["angle"] / n_radius)))
+        fans = 1
+        for sec in sector_lists(c, n_radius, radius):
+            fans *= len(sec) + 1
+            res["max_sector"] = max(res["max_sector"], len(sec))
+            res["ties"] += int(np.count_nonzero(np.diff(c["d"][sec]) == 0))
+        res["rows"] += fans * pairs
+    return res
