@@ -55,11 +55,14 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// standard normal number `which` (0..2) of environment `env` at draw `counter`: Box-Muller on two Philox words
+// standard normal number `which` (0..2) of environment (or sample) `env` at draw `counter`: Box-Muller on two Philox words.
+// TAG is the fourth counter word, one per stream: 0 the rollout noise (here and meshenv_policy.h), kReplayDrawTag the replay
+// draw, kTgtPhiloxTag the TD target's noise, kAgPhiloxTag the SAC actor gradient's
+template <uint32_t TAG>
 __device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t counter, uint32_t env, int which)
 {
     uint32_t r[4];
-    philox4x32(env, (uint32_t)counter, (uint32_t)(counter >> 32), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    philox4x32(env, (uint32_t)counter, (uint32_t)(counter >> 32), TAG, (uint32_t)seed, (uint32_t)(seed >> 32), r);
     const uint32_t a = which < 2 ? r[0] : r[2], b = which < 2 ? r[1] : r[3];
     const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
     const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
@@ -158,7 +161,7 @@ __device__ __forceinline__ void actor_forward_tile(const ActorWeights &W, ActorH
     if (wave < 4 && (lane & 15) < kActOut && (noise || sample)) {
         const int row = 4 * (lane >> 4) + wave, env = env0 + row;
         float eps = 0.0f;
-        if (env < n) eps = sample ? philox_normal(seed, counter, (uint32_t)env, lane & 15) : noise[(size_t)env * 3 + (lane & 15)];
+        if (env < n) eps = sample ? philox_normal<0u>(seed, counter, (uint32_t)env, lane & 15) : noise[(size_t)env * 3 + (lane & 15)];
         eps_lds[row * 4 + (lane & 15)] = eps;
     }
     // observations -> bufA in the K = 32 layout (zero for k >= 18 and for envs past n)

@@ -20,7 +20,7 @@
 // activation in LDS with row stride H + 4.  Workgroup g walks the tiles g, g + nwg, ... with its accumulators in registers.
 // Per tile:
 //
-//   actor     a_l = relu(W_l a_{l-1} + b_l), all three kept in LDS; a_0 = the critic kernel's input row (18 observations,
+//   actor     a_l = relu(W_l a_{l-1} + b_l), all three kept in LDS; a_0 = cg_stage's input row (18 observations,
 //             columns 18..20 for the action, a_0[21] = 1; the actor's weights of columns >= 18 are read as 0)
 //   heads     wave 0, one 16-wide tile: columns 0..2 mu, 3..5 log_std; then k_td_target<SAC>'s elementwise tail in SB3's
 //             order: ls = clamp(raw, -20, 2); std = expf(ls); g = mu + std eps; a = tanhf(g); the Normal log-prob from
@@ -35,7 +35,7 @@
 //             the closed form of what autograd computes: the two eps^2 terms of the Normal log-prob (through g and through
 //             the variance) cancel analytically and are not evaluated; what is left of it is -1 per component from
 //             -log(std).  Rows past B get 0.  Loss terms alpha log_prob - min(q1, q2) and log_prob + target_entropy.
-//   actor     backward as k_critic_grad does it from a head gradient, the head being 6 wide: dW_head += d_head^T a_3 (one
+//   actor     backward from a head gradient through cg_da of meshenv_grad_tile.h, the head being 6 wide: dW_head += d_head^T a_3 (one
 //             accumulator tile per wave, rows 6..15 zero) and db_head against a column of ones; dz_3 = a_3 > 0 ?
 //             sum_i d_head[i] W_head[i][n] : 0 (one product and five fmaf, i in order); then dW_l, db_l, da_{l-1} for
 //             l = 3, 2, 1.
@@ -54,7 +54,7 @@
 namespace meshenv {
 
 constexpr uint32_t kAgPhiloxTag = 3u;
-constexpr int kAgObs = 18;          // actor inputs
+constexpr int kAgObs = kCgObs;      // actor inputs
 constexpr int kAgHeadStride = 16;   // LDS row stride of d_head (6 columns used, the rest stay 0)
 constexpr int kAgParts = 7;         // optional per-sample outputs: actions log_prob q1 q2 dq_da d_mu d_log_std
 
@@ -99,20 +99,6 @@ struct AgArgs {
     float *acts[3][3];           // [actor, critic 1, critic 2][layer]: [n][H] post-ReLU activations, nullable
 };
 
-// standard normal number `which` (0..2) of sample `idx`: target_normal with this kernel's tag
-__device__ __forceinline__ float ag_normal(uint64_t seed, uint64_t counter, uint32_t idx, int which)
-{
-    uint32_t r[4];
-    philox4x32(idx, (uint32_t)counter, (uint32_t)(counter >> 32), kAgPhiloxTag, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const uint32_t a = which < 2 ? r[0] : r[2], b = which < 2 ? r[1] : r[3];
-    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-    const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.2831853071795864f * u2, &sn, &cs);
-    return rad * (which == 1 ? sn : cs);
-}
-
 // Three ReLU layers over the tile's 16 rows: act[l] = relu(W_l act[l - 1] + b_l), act[-1] = x0 (KIN valid columns; the rest
 // of W_1's K = 32 is read as 0).  Every thread calls it; x0 is complete at entry (a barrier has passed), act[2] at exit.
 template <int KIN>
@@ -123,22 +109,10 @@ __device__ __forceinline__ void ag_forward(const float *const *w, const float *c
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int l = 0; l < 3; l++) {
+        // the epilogue stays inline: through cg_bias_act / cg_store k_actor_grad's SGPR spill count changes (55 -> 53)
         f32x4 acc0 = zero, acc1 = zero;
-        if (l == 0) {
-            const float *w1 = w[0];
-            const unsigned o1 = (unsigned)(n0 * KIN + 4 * q);
-            const float *xr = x0 + e * kCgInStride + 4 * q;
-            const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr), a1 = *reinterpret_cast<const f32x4 *>(xr + 16);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float b0 = (w1 + j)[o1];                                      // k = 4 q + j < 16
-                const float b1 = 16 + 4 * q + j < KIN ? (w1 + 16 + j)[o1] : 0.0f;   // the padding and the column of ones
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-            }
-        } else {
-            cg_dense<G>(w[l], (unsigned)(n0 * H + 4 * q), true, act[l - 1] + e * S + 4 * q, acc0, acc1);
-        }
+        if (l == 0) cg_first<KIN>(w[0], x0, e, q, n0, acc0, acc1);
+        else cg_dense<G>(w[l], (unsigned)(n0 * H + 4 * q), true, act[l - 1] + e * S + 4 * q, acc0, acc1);
         const float bias = b[l][(unsigned)n0];
         float *o = out[l];
 #pragma unroll
@@ -150,33 +124,6 @@ __device__ __forceinline__ void ag_forward(const float *const *w, const float *c
         }
         __syncthreads();
     }
-}
-
-// da[row = 4 q + reg][k = n0] = sum_n dz[row][n] W[n][k] for the wave's 16 columns (k_critic_grad's da: two accumulators
-// over even / odd 16-groups of n, W [H][H] read by columns through one buffer descriptor and one lane offset)
-__device__ __forceinline__ f32x4 ag_da(const float *w, const float *dz, int e, int q, int n0)
-{
-    constexpr int H = 128, G = H / 16, S = H + 4;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    const float *xr = dz + e * S + 4 * q;
-    const __amdgpu_buffer_rsrc_t wl = __builtin_amdgcn_make_buffer_rsrc((void *)w, 0, H * H * 4, kCgBufferFlags);
-    const int voff = (4 * q * H + n0) * 4;
-#pragma unroll
-    for (int g = 0; g < G; g += 2) {
-        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr + 16 * g);
-        const f32x4 a1 = *reinterpret_cast<const f32x4 *>(xr + 16 * g + 16);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + j) * H * 4, 0));
-            const float b1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + 16 + j) * H * 4, 0));
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-        }
-    }
-    f32x4 r;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) r[reg] = acc0[reg] + acc1[reg];
-    return r;
 }
 
 __global__ void __launch_bounds__(512)
@@ -213,17 +160,11 @@ k_actor_grad(AgArgs A)
         if (t < kCgRows * 3) {
             const int row = t / 3, c = t - 3 * row, r = row0 + row;
             float eps = 0.0f;
-            if (noisy && r < A.n) eps = A.sample ? ag_normal(A.seed, A.counter, (uint32_t)r, c) : A.noise[(unsigned)(r * 3 + c)];
+            if (noisy && r < A.n) eps = A.sample ? philox_normal<kAgPhiloxTag>(A.seed, A.counter, (uint32_t)r, c) : A.noise[(unsigned)(r * 3 + c)];
             eps_l[row * 4 + c] = eps;
             if (A.eps_out && r < A.n) A.eps_out[(unsigned)(r * 3 + c)] = eps;
         }
-        for (int i = t; i < kCgRows * 32; i += NT) {
-            const int r = i >> 5, k = i & 31, gr = row0 + r;
-            float v = 0.0f;
-            if (k == kCgOnes) v = 1.0f;
-            else if (gr < A.n && k < kAgObs) v = A.obs[(unsigned)(gr * kAgObs + k)];
-            x0[r * kCgInStride + k] = v;
-        }
+        cg_stage<NT, false>(x0, A.obs, nullptr, row0, A.n, t);
         __syncthreads();
         // ---- actor forward, heads and the elementwise tail (wave 0)
         ag_forward<kAgObs>(A.a.w, A.a.b, x0, aa, A.acts[0], row0, A.n, e, q, n0);
@@ -297,7 +238,7 @@ k_actor_grad(AgArgs A)
             __syncthreads();
 #pragma unroll
             for (int l = 2; l >= 1; l--) {
-                const f32x4 da = ag_da(C.w[l], ca[l], e, q, n0);
+                const f32x4 da = cg_da<H>(C.w[l], ca[l], e, q, n0);
 #pragma unroll
                 for (int reg = 0; reg < 4; reg++) {
                     float *p = ca[l - 1] + (4 * q + reg) * S + n0;
@@ -423,7 +364,7 @@ k_actor_grad(AgArgs A)
                 __syncthreads();   // x0, aa and dh are free for the next tile
                 break;
             }
-            const f32x4 da = ag_da(A.a.w[l], aa[l], e, q, n0);
+            const f32x4 da = cg_da<H>(A.a.w[l], aa[l], e, q, n0);
             __syncthreads();   // every wave has read a_{l-1} (dW_l) and dz_l
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
@@ -445,12 +386,7 @@ k_actor_grad(AgArgs A)
             for (int kt = 0; kt < G; kt++) P[L::hw(l) + n * H + 16 * kt + e] = dwl[l - 1][kt][reg];
             if (e == 0) P[L::hb(l) + n] = dbl[l - 1][reg];
         }
-#pragma unroll
-        for (int kt = 0; kt < 2; kt++) {
-            const int k = 16 * kt + e;
-            if (k < kAgObs) P[n * kAgObs + k] = dw1[kt][reg];
-            else if (k == kCgOnes) P[L::b1 + n] = dw1[kt][reg];
-        }
+        cg_put_dw1<kAgObs>(P, L::b1, dw1, reg, n, e);
         const int i = 4 * q + reg;               // row of the head tile: 0..2 mu, 3..5 log_std
         if (i < 6) {
             const int hr = i < 3 ? i : i - 3;
@@ -473,20 +409,16 @@ k_actor_grad_reduce(const float *__restrict__ partial, int nwg, int n, const flo
     using L = AgLayout;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < L::ent) {
-        float s = partial[i];
-#pragma unroll 4
-        for (int w = 1; w < nwg; w++) s = s + partial[(size_t)w * L::set + i];
-        grad[i] = s;
+        float s[1];
+        cg_sum_sets<1, true>(partial, nwg, L::set, i, s);
+        grad[i] = s[0];
     }
     if (i == 0) {
-        float s1 = partial[L::stride], s2 = partial[L::stride + 1];
-        for (int w = 1; w < nwg; w++) {
-            s1 = s1 + partial[(size_t)w * L::set + L::stride];
-            s2 = s2 + partial[(size_t)w * L::set + L::stride + 1];
-        }
-        loss[0] = s1 / (float)n;
+        float s[2];
+        cg_sum_sets<2, false>(partial, nwg, L::set, L::stride, s);
+        loss[0] = s[0] / (float)n;
         if (log_ent_coef) {
-            const float m = s2 / (float)n;
+            const float m = s[1] / (float)n;
             grad[L::ent] = -m;
             loss[1] = -(log_ent_coef[0] * m);
         }

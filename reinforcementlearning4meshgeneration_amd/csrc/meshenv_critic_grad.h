@@ -33,19 +33,17 @@
 // of the workgroup's tiles, 16 T roundings for T = ceil(tiles / nwg) tiles, then nwg - 1 additions over the partial sets in
 // index order.  nwg = min(tiles, 64) up to 512 tiles, 128 beyond (kCgMaxGroups); no floating-point atomics anywhere, so two
 // calls on the same inputs give the same bits.
+//
+// The per-tile pieces (staging, cg_first, cg_dense, cg_da, the dW_1 write-out, the sum over the partial sets) are the shared
+// helpers of meshenv_grad_tile.h.
 #pragma once
 
-#include "meshenv_target.h"
+#include "meshenv_grad_tile.h"
 
 namespace meshenv {
 
-constexpr int kCgRows = 16;       // samples per tile = MFMA K of the weight gradient
-constexpr int kCgInStride = 36;   // LDS row stride of the input rows (21 inputs padded to 32)
-constexpr int kCgOnes = 21;       // the column of ones in the input rows: the first layer's bias gradient
-constexpr int kCgMaxGroups = 128; // workgroups per critic; the workspace holds that many partial sets
 constexpr int kCgMaxLayers = 4;   // hidden layers + head
 constexpr int kCgSplitTD3 = 2;    // TD3: workgroups per critic and tile set, each accumulating half the columns of dW_2
-constexpr int kCgBufferFlags = 0x00020000;   // word 3 of a raw 32-bit buffer descriptor on gfx9
 
 // One gradient set: per critic w1 [H][21], b1 [H], then w_l [H][H], b_l [H] per further hidden layer, wh [H], bh [1], padded
 // to a multiple of 64 floats; the partial sets carry the two loss sums after the second critic.
@@ -76,27 +74,6 @@ struct CgArgs {
     float *q[2];                           // [n], nullable
     float *acts[2][kCgMaxLayers - 1];      // [n][H] post-ReLU activations per hidden layer, nullable
 };
-
-// acc0 / acc1 += x W^T over K = 16 G inputs for the lane's neuron n: w = W (uniform), off = n * K + 4 q (one 32-bit lane
-// offset against a scalar base per load), valid: false reads a zero row; xr = &x[e][4 q]
-template <int G>
-__device__ __forceinline__ void cg_dense(const float *__restrict__ w, unsigned off, bool valid, const float *xr, f32x4 &acc0,
-                                         f32x4 &acc1)
-{
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < G; g += 2) {
-        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr + 16 * g);
-        const f32x4 a1 = *reinterpret_cast<const f32x4 *>(xr + 16 * g + 16);
-        const f32x4 b0 = valid ? *reinterpret_cast<const f32x4 *>((w + 16 * g) + off) : zero;
-        const f32x4 b1 = valid ? *reinterpret_cast<const f32x4 *>((w + 16 * g + 16) + off) : zero;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0[j], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1[j], acc1, 0, 0, 0);
-        }
-    }
-}
 
 template <int KIND>
 __global__ void __launch_bounds__(KIND == kTargetSAC ? 512 : 1024)
@@ -129,34 +106,15 @@ k_critic_grad(CgArgs A)
 
     for (int tile = blockIdx.x; tile < tiles; tile += A.nwg) {
         const int row0 = tile * kCgRows;
-        for (int i = t; i < kCgRows * 32; i += NT) {
-            const int r = i >> 5, k = i & 31, gr = row0 + r;
-            float v = 0.0f;
-            if (k == kCgOnes) v = 1.0f;
-            else if (gr < A.n && k < 18) v = A.obs[(unsigned)(gr * 18 + k)];
-            else if (gr < A.n && k < kTgtIn) v = A.actions[(unsigned)(gr * 3 + (k - 18))];
-            x0[r * kCgInStride + k] = v;
-        }
+        cg_stage<NT, true>(x0, A.obs, A.actions, row0, A.n, t);
         __syncthreads();
         // ---- forward
 #pragma unroll
         for (int l = 0; l < NL; l++) {
+            // the epilogue stays inline: through cg_bias_act / cg_store this kernel allocates more VGPRs (168 -> 170, 124 -> 128)
             f32x4 acc0 = zero, acc1 = zero;
-            if (l == 0) {
-                const float *w1 = C.w[0];
-                const unsigned o1 = (unsigned)(n0 * kTgtIn + 4 * q);
-                const float *xr = x0 + e * kCgInStride + 4 * q;
-                const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr), a1 = *reinterpret_cast<const f32x4 *>(xr + 16);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float b0 = (w1 + j)[o1];                                         // k = 4 q + j < 16
-                    const float b1 = 16 + 4 * q + j < kTgtIn ? (w1 + 16 + j)[o1] : 0.0f;   // the padding and the column of ones
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-                }
-            } else {
-                cg_dense<G>(C.w[l], (unsigned)(n0 * H + 4 * q), true, act[l - 1] + e * S + 4 * q, acc0, acc1);
-            }
+            if (l == 0) cg_first<kTgtIn>(C.w[0], x0, e, q, n0, acc0, acc1);
+            else cg_dense<G>(C.w[l], (unsigned)(n0 * H + 4 * q), true, act[l - 1] + e * S + 4 * q, acc0, acc1);
             const float b = C.b[l][(unsigned)n0];
             float *out = A.acts[c][l];
 #pragma unroll
@@ -232,31 +190,12 @@ k_critic_grad(CgArgs A)
                 __syncthreads();   // x0 and act[0] are free for the next tile
                 break;
             }
-            // da_{l-1}[row][k = n0] = sum_n dz_l[row][n] W_l[n][k]
-            f32x4 acc0 = zero, acc1 = zero;
-            const float *xr = act[l] + e * S + 4 * q;
-            // buffer loads: one descriptor and one lane offset for all 4 G of them (a flat address per load would cost
-            // two registers each); reads past the H x H matrix cannot happen and would return 0
-            const __amdgpu_buffer_rsrc_t wl = __builtin_amdgcn_make_buffer_rsrc((void *)C.w[l], 0, H * H * 4, kCgBufferFlags);
-            const int voff = (4 * q * H + n0) * 4;
-#pragma unroll
-            for (int g = 0; g < G; g += 2) {
-                const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr + 16 * g);
-                const f32x4 a1 = *reinterpret_cast<const f32x4 *>(xr + 16 * g + 16);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    // W_l[16 g + 4 q + j][n0]; the builtin returns the 32 bits as an integer
-                    const float b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + j) * H * 4, 0));
-                    const float b1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + 16 + j) * H * 4, 0));
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-                }
-            }
+            const f32x4 da = cg_da<H>(C.w[l], act[l], e, q, n0);   // da_{l-1}[row][k = n0] = sum_n dz_l[row][n] W_l[n][k]
             __syncthreads();   // every wave has read a_{l-1} (dW_l) and dz_l
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
                 float *p = act[l - 1] + (4 * q + reg) * S + n0;
-                *p = *p > 0.0f ? acc0[reg] + acc1[reg] : 0.0f;
+                *p = *p > 0.0f ? da[reg] : 0.0f;
             }
             __syncthreads();
         }
@@ -274,12 +213,7 @@ k_critic_grad(CgArgs A)
             if (e == 0 && half == 0) P[L::hb(l) + n] = dbl[l - 1][reg];
         }
         if (half != 0) continue;
-#pragma unroll
-        for (int kt = 0; kt < 2; kt++) {
-            const int k = 16 * kt + e;
-            if (k < kTgtIn) P[n * kTgtIn + k] = dw1[kt][reg];
-            else if (k == kCgOnes) P[L::b1 + n] = dw1[kt][reg];
-        }
+        cg_put_dw1<kTgtIn>(P, L::b1, dw1, reg, n, e);
     }
     if (half != 0) return;   // everything but its columns of the hidden dW is the first workgroup's to write
     if (t < H) P[L::wh + t] = dwo;
@@ -296,18 +230,14 @@ k_critic_grad_reduce(const float *__restrict__ partial, int nwg, int set, int gr
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < grads) {
-        float s = partial[i];
-#pragma unroll 4
-        for (int w = 1; w < nwg; w++) s = s + partial[(size_t)w * set + i];
-        grad[i] = s;
+        float s[1];
+        cg_sum_sets<1, true>(partial, nwg, set, i, s);
+        grad[i] = s[0];
     }
     if (i == 0 && loss) {
-        float s1 = partial[grads], s2 = partial[grads + 1];
-        for (int w = 1; w < nwg; w++) {
-            s1 = s1 + partial[(size_t)w * set + grads];
-            s2 = s2 + partial[(size_t)w * set + grads + 1];
-        }
-        loss[0] = 0.5f * (s1 / (float)n + s2 / (float)n);
+        float s[2];
+        cg_sum_sets<2, false>(partial, nwg, set, grads, s);
+        loss[0] = 0.5f * (s[0] / (float)n + s[1] / (float)n);
     }
 }
 

@@ -116,7 +116,7 @@ __device__ __forceinline__ void policy_pass(const PolicyTower &T, const float *_
         for (int i = t; i < kPolEnvs * 3; i += 64 * G2) {
             const int row = i / 3, c = i - 3 * row, env = env0 + row;
             float eps = 0.0f;
-            if (env < A.n) eps = A.sample ? philox_normal(A.seed, A.counter, (uint32_t)env, c) : A.noise[(size_t)env * 3 + c];
+            if (env < A.n) eps = A.sample ? philox_normal<0u>(A.seed, A.counter, (uint32_t)env, c) : A.noise[(size_t)env * 3 + c];
             eps_lds[row * 4 + c] = eps;
         }
     }

@@ -51,7 +51,7 @@
 
 namespace meshenv {
 
-constexpr int kPgObs = 18;       // inputs of both towers
+constexpr int kPgObs = kCgObs;   // inputs of both towers
 constexpr int kPgTensors = 13;   // pi w1 b1 w2 b2 wh bh, vf likewise, log_std
 constexpr int kPgSums = 4;       // row sums behind a partial set: surrogate, squared value error, kl term, clipped rows
 constexpr int kPgParts = 5;      // optional per-row outputs: log_prob ratio values advantages pass
@@ -113,48 +113,6 @@ __device__ __forceinline__ float pg_back(float a, float g)
     return ACT == kPolicyTanh ? g * (1.0f - a * a) : (a > 0.0f ? g : 0.0f);
 }
 
-// da[row = 4 q + reg][k = n0] = sum_n dz[row][n] W[n][k] for the wave's 16 columns (k_critic_grad's da: two accumulators over
-// even / odd 16-groups of n, W [H][H] read by columns through one buffer descriptor and one lane offset; reads past the H x H
-// matrix cannot happen and would return 0)
-template <int H>
-__device__ __forceinline__ f32x4 pg_da(const float *w, const float *dz, int e, int q, int n0)
-{
-    constexpr int G = H / 16, S = H + 4;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    const float *xr = dz + e * S + 4 * q;
-    const __amdgpu_buffer_rsrc_t wl = __builtin_amdgcn_make_buffer_rsrc((void *)w, 0, H * H * 4, kCgBufferFlags);
-    const int voff = (4 * q * H + n0) * 4;
-#pragma unroll
-    for (int g = 0; g < G; g += 2) {
-        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr + 16 * g);
-        const f32x4 a1 = *reinterpret_cast<const f32x4 *>(xr + 16 * g + 16);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + j) * H * 4, 0));
-            const float b1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + 16 + j) * H * 4, 0));
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-        }
-    }
-    f32x4 r;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) r[reg] = acc0[reg] + acc1[reg];
-    return r;
-}
-
-// v[reg] = act(z) -> buf[row = 4 q + reg][n0], and to out [n][H] (nullable) for the rows below n
-template <int H>
-__device__ __forceinline__ void pg_store(float *buf, float *out, const f32x4 &v, int row0, int n, int q, int n0)
-{
-    constexpr int S = H + 4;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {   // D[row = 4 q + reg][col = e]
-        const int row = 4 * q + reg;
-        buf[row * S + n0] = v[reg];
-        if (out && row0 + row < n) out[(unsigned)((row0 + row) * H + n0)] = v[reg];
-    }
-}
-
 template <int H, int ACT>
 __global__ void __launch_bounds__(4 * H)
 k_ppo_grad(PgArgs A)
@@ -181,44 +139,12 @@ k_ppo_grad(PgArgs A)
 
     for (int tile = blockIdx.x; tile < tiles; tile += A.nwg) {
         const int row0 = tile * kCgRows;
-        for (int i = t; i < kCgRows * 32; i += NT) {
-            const int r = i >> 5, k = i & 31, gr = row0 + r;
-            float v = 0.0f;
-            if (k == kCgOnes) v = 1.0f;
-            else if (gr < A.n && k < kPgObs) v = A.obs[(unsigned)(gr * kPgObs + k)];
-            x0[r * kCgInStride + k] = v;
-        }
+        cg_stage<NT, false>(x0, A.obs, nullptr, row0, A.n, t);
         __syncthreads();
         // ---- forward
-        {
-            f32x4 acc0 = zero, acc1 = zero;
-            const float *w1 = T.w[0];
-            const unsigned o1 = (unsigned)(n0 * kPgObs + 4 * q);
-            const float *xr = x0 + e * kCgInStride + 4 * q;
-            const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr), a1 = *reinterpret_cast<const f32x4 *>(xr + 16);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float b0 = (w1 + j)[o1];                                         // k = 4 q + j < 16
-                const float b1 = 16 + 4 * q + j < kPgObs ? (w1 + 16 + j)[o1] : 0.0f;   // the padding and the column of ones
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-            }
-            const float bias = T.b[0][(unsigned)n0];
-            f32x4 v;
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++) v[reg] = policy_act<ACT>((acc0[reg] + acc1[reg]) + bias);
-            pg_store<H>(aa[0], A.acts[tower][0], v, row0, A.n, q, n0);
-        }
+        cg_store<H>(aa[0], A.acts[tower][0], cg_first_layer<kPgObs, ACT>(T.w[0], T.b[0], x0, e, q, n0), row0, A.n, q, n0);
         __syncthreads();
-        {
-            f32x4 acc0 = zero, acc1 = zero;
-            cg_dense<G>(T.w[1], (unsigned)(n0 * H + 4 * q), true, aa[0] + e * S + 4 * q, acc0, acc1);
-            const float bias = T.b[1][(unsigned)n0];
-            f32x4 v;
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++) v[reg] = policy_act<ACT>((acc0[reg] + acc1[reg]) + bias);
-            pg_store<H>(aa[1], A.acts[tower][1], v, row0, A.n, q, n0);
-        }
+        cg_store<H>(aa[1], A.acts[tower][1], cg_hidden_layer<H, ACT>(T.w[1], T.b[1], aa[0], e, q, n0), row0, A.n, q, n0);
         __syncthreads();
         // ---- the head and its gradient (wave 0)
         if (wave == 0) {
@@ -348,7 +274,7 @@ k_ppo_grad(PgArgs A)
             db2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, 1.0f, db2, 0, 0, 0);
         }
         {
-            const f32x4 da = pg_da<H>(T.w[1], aa[1], e, q, n0);
+            const f32x4 da = cg_da<H>(T.w[1], aa[1], e, q, n0);
             __syncthreads();   // every wave has read a_1 (dW_2) and dz_2
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
@@ -378,12 +304,7 @@ k_ppo_grad(PgArgs A)
 #pragma unroll
         for (int kt = 0; kt < G; kt++) P[L::w2 + n * H + 16 * kt + e] = dw2[kt][reg];
         if (e == 0) P[L::b2 + n] = db2[reg];
-#pragma unroll
-        for (int kt = 0; kt < 2; kt++) {
-            const int k = 16 * kt + e;
-            if (k < kPgObs) P[n * kPgObs + k] = dw1[kt][reg];
-            else if (k == kCgOnes) P[L::b1 + n] = dw1[kt][reg];
-        }
+        cg_put_dw1<kPgObs>(P, L::b1, dw1, reg, n, e);
     }
     if (pi) {
         if (t < 3 * H + 3) P[L::wh + t] = hacc;                         // wh [3][H] and bh [3] are adjacent
@@ -406,17 +327,14 @@ k_ppo_grad_reduce(const float *__restrict__ partial, int nwg, int set, int strid
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < params) {
-        float s = partial[i];
-#pragma unroll 4
-        for (int w = 1; w < nwg; w++) s = s + partial[(size_t)w * set + i];
-        if (i >= params - 3) s = s - ent_coef;
-        grad[i] = s;
+        float s[1];
+        cg_sum_sets<1, true>(partial, nwg, set, i, s);
+        if (i >= params - 3) s[0] = s[0] - ent_coef;
+        grad[i] = s[0];
     }
     if (i == 0) {
         float s[kPgSums];
-        for (int k = 0; k < kPgSums; k++) s[k] = partial[stride + k];
-        for (int w = 1; w < nwg; w++)
-            for (int k = 0; k < kPgSums; k++) s[k] = s[k] + partial[(size_t)w * set + stride + k];
+        cg_sum_sets<kPgSums, false>(partial, nwg, set, stride, s);
         const float fn = (float)n, c = 1.4189385332046727f;   // 0.5 + 0.5 log(2 pi)
         const float policy_loss = -(s[0] / fn), value_loss = s[1] / fn;
         const float entropy_loss = -(((c + log_std[0]) + (c + log_std[1])) + (c + log_std[2]));

@@ -60,20 +60,6 @@ struct TargetArgs {
     float *target, *next_actions, *next_log_prob, *q1, *q2, *eps_out;   // every one nullable
 };
 
-// standard normal number `which` (0..2) of sample `idx`: Box-Muller on two Philox words, as philox_normal with tag 2
-__device__ __forceinline__ float target_normal(uint64_t seed, uint64_t counter, uint32_t idx, int which)
-{
-    uint32_t r[4];
-    philox4x32(idx, (uint32_t)counter, (uint32_t)(counter >> 32), kTgtPhiloxTag, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const uint32_t a = which < 2 ? r[0] : r[2], b = which < 2 ? r[1] : r[3];
-    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-    const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.2831853071795864f * u2, &sn, &cs);
-    return rad * (which == 1 ? sn : cs);
-}
-
 // One network over the workgroup's 16 rows: NL ReLU layers of width H, then the head tile on wave 0, whose lane (col e, rows
 // 4 q + reg) receives out[reg] = head[row][e] + bias (other waves: unspecified).  x0: the input rows (K = 32 layout, stride
 // kPolInStride); ha, hb: activation buffers of stride H + 4.  Every thread calls it: the first barrier waits for x0 and for
@@ -136,7 +122,7 @@ k_td_target(TargetWeights W, TargetArgs A)
     if (t < kTgtRows * 3) {
         const int row = t / 3, c = t - 3 * row, r = row0 + row;
         float eps = 0.0f;
-        if (noisy && r < A.n) eps = A.sample ? target_normal(A.seed, A.counter, (uint32_t)r, c) : A.noise[(size_t)r * 3 + c];
+        if (noisy && r < A.n) eps = A.sample ? philox_normal<kTgtPhiloxTag>(A.seed, A.counter, (uint32_t)r, c) : A.noise[(size_t)r * 3 + c];
         eps_lds[row * 4 + c] = eps;
     }
     // next observations -> x0 in the K = 32 layout; columns 18..20 receive the action below, the rest is zero

@@ -17,7 +17,7 @@
 // as in k_critic_grad<TD3> (kCgSplitTD3) two workgroups per tile set each do the whole forward and critic pass and accumulate
 // half the columns of dW_2; half 0 writes everything else.  Per tile:
 //
-//   actor     a_l = relu(W_l a_{l-1} + b_l), l = 1, 2, both kept in LDS; a_0 = the critic kernel's input row (18
+//   actor     a_l = relu(W_l a_{l-1} + b_l), l = 1, 2, both kept in LDS; a_0 = cg_stage's input row (18
 //             observations, columns 18..20 for the action, a_0[21] = 1; the actor's weights of columns >= 18 are read as 0)
 //   head      wave 0, one 16-wide tile of which columns 0..2 are used: pre = W_3 a_2 + b_3, a = tanhf(pre) (k_td_target<TD3>'s
 //             call); a goes into columns 18..20 of the input row, 0 for rows past B
@@ -28,7 +28,7 @@
 //             dQ/da = dz_1 W^q_1[:, 18..20].  No weight gradient.
 //   head grad wave 0: d_pre = (-((dQ/da) / B)) * (1 - a a), autograd's order (tanh's backward is grad * (1 - out * out));
 //             exactly 0 for rows past B
-//   actor     backward as k_critic_grad<TD3> does it from a head gradient, the head being 3 wide: thread t < 768 owns
+//   actor     backward from a head gradient through cg_da of meshenv_grad_tile.h, the head being 3 wide: thread t < 768 owns
 //             dW_3[t / 256][t % 256] += d_pre[row][i] a_2[row][n] (fmaf, rows in order), threads 768..770 db_3 (plain adds),
 //             thread 771 the sum of q; dz_2 = a_2 > 0 ? sum_i d_pre[i] W_3[i][n] : 0 (one product and two fmaf, i in order);
 //             then dW_2 (this half's columns), db_2, da_1 = dz_2 W_2, dz_1 = a_1 > 0 ? da_1 : 0, dW_1, db_1.
@@ -43,7 +43,7 @@
 
 namespace meshenv {
 
-constexpr int kTaObs = 18;     // actor inputs
+constexpr int kTaObs = kCgObs; // actor inputs
 constexpr int kTaParts = 4;    // optional per-sample outputs: actions q1 dq_da d_pre
 
 // The gradient set, torch layout, in TD3ActorGradSpec's parameter order: w1 [H][18], b1 [H], w2 [H][H], b2 [H], w3 [3][H],
@@ -69,82 +69,6 @@ struct TaArgs {
     float *actions, *q, *dq_da, *d_pre;   // [n][3] [n] [n][3] [n][3], every one nullable
     float *acts[2][2];             // [actor, critic][layer]: [n][H] post-ReLU activations, nullable
 };
-
-// relu(W_1 x + b_1) of the lane's neuron n0 for rows 4 q + reg; x0: the input rows (K = 32, KIN valid columns, the rest of
-// W_1's K is read as 0)
-template <int KIN>
-__device__ __forceinline__ f32x4 ta_first(const float *w1, const float *b1, const float *x0, int e, int q, int n0)
-{
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    const unsigned o1 = (unsigned)(n0 * KIN + 4 * q);
-    const float *xr = x0 + e * kCgInStride + 4 * q;
-    const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr), a1 = *reinterpret_cast<const f32x4 *>(xr + 16);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const float b0 = (w1 + j)[o1];                                      // k = 4 q + j < 16
-        const float bb = 16 + 4 * q + j < KIN ? (w1 + 16 + j)[o1] : 0.0f;   // the padding and the column of ones
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], bb, acc1, 0, 0, 0);
-    }
-    const float bias = b1[(unsigned)n0];
-    f32x4 r;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) r[reg] = fmaxf((acc0[reg] + acc1[reg]) + bias, 0.0f);
-    return r;
-}
-
-// relu(W x + b) of the lane's neuron n0 for rows 4 q + reg; x: 16 rows of H activations in LDS
-__device__ __forceinline__ f32x4 ta_hidden(const float *w, const float *b, const float *x, int e, int q, int n0)
-{
-    constexpr int H = TaLayout::H, G = H / 16, S = H + 4;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    cg_dense<G>(w, (unsigned)(n0 * H + 4 * q), true, x + e * S + 4 * q, acc0, acc1);
-    const float bias = b[(unsigned)n0];
-    f32x4 r;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) r[reg] = fmaxf((acc0[reg] + acc1[reg]) + bias, 0.0f);
-    return r;
-}
-
-// v[reg] -> buf[row = 4 q + reg][n0], and to out [n][H] (nullable) for the rows below n
-__device__ __forceinline__ void ta_store(float *buf, float *out, const f32x4 &v, int row0, int n, int q, int n0)
-{
-    constexpr int H = TaLayout::H, S = H + 4;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {   // D[row = 4 q + reg][col = e]
-        const int row = 4 * q + reg;
-        buf[row * S + n0] = v[reg];
-        if (out && row0 + row < n) out[(unsigned)((row0 + row) * H + n0)] = v[reg];
-    }
-}
-
-// da[row = 4 q + reg][k = n0] = sum_n dz[row][n] W[n][k] for the wave's 16 columns (k_critic_grad's da: two accumulators
-// over even / odd 16-groups of n, W [H][H] read by columns through one buffer descriptor and one lane offset; reads past
-// the H x H matrix cannot happen and would return 0)
-__device__ __forceinline__ f32x4 ta_da(const float *w, const float *dz, int e, int q, int n0)
-{
-    constexpr int H = TaLayout::H, G = H / 16, S = H + 4;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    const float *xr = dz + e * S + 4 * q;
-    const __amdgpu_buffer_rsrc_t wl = __builtin_amdgcn_make_buffer_rsrc((void *)w, 0, H * H * 4, kCgBufferFlags);
-    const int voff = (4 * q * H + n0) * 4;
-#pragma unroll
-    for (int g = 0; g < G; g += 2) {
-        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xr + 16 * g);
-        const f32x4 a1 = *reinterpret_cast<const f32x4 *>(xr + 16 * g + 16);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + j) * H * 4, 0));
-            const float b1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wl, voff, (16 * g + 16 + j) * H * 4, 0));
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1, acc1, 0, 0, 0);
-        }
-    }
-    f32x4 r;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) r[reg] = acc0[reg] + acc1[reg];
-    return r;
-}
 
 __global__ void __launch_bounds__(1024)
 k_td3_actor_grad(TaArgs A)
@@ -178,21 +102,15 @@ k_td3_actor_grad(TaArgs A)
         int tt = threadIdx.x;
         asm volatile("" : "+v"(tt));
         const int t = tt, lane = t & 63, e = lane & 15, q = lane >> 4, n0 = 16 * wave + e;
-        for (int i = t; i < kCgRows * 32; i += NT) {
-            const int r = i >> 5, k = i & 31, gr = row0 + r;
-            float v = 0.0f;
-            if (k == kCgOnes) v = 1.0f;
-            else if (gr < A.n && k < kTaObs) v = A.obs[(unsigned)(gr * kTaObs + k)];
-            x0[r * kCgInStride + k] = v;
-        }
+        cg_stage<NT, false>(x0, A.obs, nullptr, row0, A.n, t);
         __syncthreads();
         // ---- actor forward and its head (wave 0)
         {
-            f32x4 v = ta_first<kTaObs>(A.w[0], A.b[0], x0, e, q, n0);
-            ta_store(aa[0], first ? A.acts[0][0] : nullptr, v, row0, A.n, q, n0);
+            f32x4 v = cg_first_layer<kTaObs, kPolicyReLU>(A.w[0], A.b[0], x0, e, q, n0);
+            cg_store<H>(aa[0], first ? A.acts[0][0] : nullptr, v, row0, A.n, q, n0);
             __syncthreads();
-            v = ta_hidden(A.w[1], A.b[1], aa[0], e, q, n0);
-            ta_store(aa[1], first ? A.acts[0][1] : nullptr, v, row0, A.n, q, n0);
+            v = cg_hidden_layer<H, kPolicyReLU>(A.w[1], A.b[1], aa[0], e, q, n0);
+            cg_store<H>(aa[1], first ? A.acts[0][1] : nullptr, v, row0, A.n, q, n0);
             __syncthreads();
         }
         if (wave == 0) {
@@ -215,16 +133,16 @@ k_td3_actor_grad(TaArgs A)
         __syncthreads();
         // ---- the critic through one buffer: forward, q, then dQ/da from dq = 1
         {
-            f32x4 v = ta_first<kTgtIn>(A.c.w[0], A.c.b[0], x0, e, q, n0);
+            f32x4 v = cg_first_layer<kTgtIn, kPolicyReLU>(A.c.w[0], A.c.b[0], x0, e, q, n0);
             bool m1[4];
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) m1[reg] = v[reg] > 0.0f;
-            ta_store(ca, first ? A.acts[1][0] : nullptr, v, row0, A.n, q, n0);
+            cg_store<H>(ca, first ? A.acts[1][0] : nullptr, v, row0, A.n, q, n0);
             __syncthreads();
-            v = ta_hidden(A.c.w[1], A.c.b[1], ca, e, q, n0);
+            v = cg_hidden_layer<H, kPolicyReLU>(A.c.w[1], A.c.b[1], ca, e, q, n0);
             const float wo = A.c.w[2][(unsigned)n0];
             __syncthreads();   // every wave has read c_1
-            ta_store(ca, first ? A.acts[1][1] : nullptr, v, row0, A.n, q, n0);
+            cg_store<H>(ca, first ? A.acts[1][1] : nullptr, v, row0, A.n, q, n0);
             __syncthreads();
             if (wave == 0) {
                 f32x4 acc0 = zero, acc1 = zero;
@@ -244,7 +162,7 @@ k_td3_actor_grad(TaArgs A)
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) ca[(4 * q + reg) * S + n0] = v[reg] > 0.0f ? wo : 0.0f;   // dz_2
             __syncthreads();
-            const f32x4 da = ta_da(A.c.w[1], ca, e, q, n0);
+            const f32x4 da = cg_da<H>(A.c.w[1], ca, e, q, n0);
             __syncthreads();   // every wave has read dz_2
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) ca[(4 * q + reg) * S + n0] = m1[reg] ? da[reg] : 0.0f;    // dz_1
@@ -253,7 +171,7 @@ k_td3_actor_grad(TaArgs A)
         if (wave == 0) {   // dQ/da[row][k] = sum_n dz_1[row][n] W^q_1[n][18 + k], then the head gradient
             f32x4 acc0 = zero, acc1 = zero;
             const float *xr = ca + e * S + 4 * q;
-            // buffer loads as in ta_da: lanes e >= 3 read column 18 and drop it
+            // buffer loads as in cg_da: lanes e >= 3 read column 18 and drop it
             const __amdgpu_buffer_rsrc_t w1 = __builtin_amdgcn_make_buffer_rsrc((void *)A.c.w[0], 0, H * kTgtIn * 4, kCgBufferFlags);
             const int voff = (4 * q * kTgtIn + kTaObs + (e < 3 ? e : 0)) * 4;
 #pragma unroll
@@ -326,7 +244,7 @@ k_td3_actor_grad(TaArgs A)
             db2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, 1.0f, db2, 0, 0, 0);
         }
         {
-            const f32x4 da = ta_da(A.w[1], aa[1], e, q, n0);
+            const f32x4 da = cg_da<H>(A.w[1], aa[1], e, q, n0);
             __syncthreads();   // every wave has read a_1 (dW_2) and dz_2
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
@@ -357,12 +275,7 @@ k_td3_actor_grad(TaArgs A)
         for (int kt = 0; kt < GH; kt++) P[L::w2 + n * H + 16 * (half * GH + kt) + e] = dw2[kt][reg];
         if (!first) continue;
         if (e == 0) P[L::b2 + n] = db2[reg];
-#pragma unroll
-        for (int kt = 0; kt < 2; kt++) {
-            const int k = 16 * kt + e;
-            if (k < kTaObs) P[n * kTaObs + k] = dw1[kt][reg];
-            else if (k == kCgOnes) P[L::b1 + n] = dw1[kt][reg];
-        }
+        cg_put_dw1<kTaObs>(P, L::b1, dw1, reg, n, e);
     }
     if (!first) return;   // everything but its columns of dW_2 is the first workgroup's to write
     if (t < 3 * H + 3) P[L::w3 + t] = hacc;   // w3 [3][H] and b3 [3] are adjacent
@@ -376,15 +289,14 @@ k_td3_actor_grad_reduce(const float *__restrict__ partial, int nwg, int n, float
     using L = TaLayout;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < L::params) {
-        float s = partial[i];
-#pragma unroll 4
-        for (int w = 1; w < nwg; w++) s = s + partial[(size_t)w * L::set + i];
-        grad[i] = s;
+        float s[1];
+        cg_sum_sets<1, true>(partial, nwg, L::set, i, s);
+        grad[i] = s[0];
     }
     if (i == 0) {
-        float s = partial[L::stride];
-        for (int w = 1; w < nwg; w++) s = s + partial[(size_t)w * L::set + L::stride];
-        loss[0] = -(s / (float)n);
+        float s[1];
+        cg_sum_sets<1, false>(partial, nwg, L::set, L::stride, s);
+        loss[0] = -(s[0] / (float)n);
     }
 }
 

@@ -18,7 +18,7 @@ The chain, in the kernel's order, each bound built from the one before (u = 2^-2
   a           = tanhf(pre)                            td_target_ref's: the slope 1 - tanh^2 on [pre - e, pre + e], + 4 ulp
   c_l, q      = the first critic on cat(obs, a)       layers again, input error (0, e_a)
   dz_2^q      = mask^q_2 * w_out                      from dq = 1: exact
-  da_1^q      = dz_2^q W^q_2                          ta_da: two accumulators, each one fma chain over the H / 2 = 128 neurons
+  da_1^q      = dz_2^q W^q_2                          cg_da: two accumulators, each one fma chain over the H / 2 = 128 neurons
                                                       of its eight 16-groups, then their sum: gamma_{H/2+1} = gamma_129
   dz_1^q      = mask^q_1 * da_1^q                     a select: exact
   dQ/da       = dz_1^q W^q_1[:, 18..20]               the same two chains of 128 and their sum: gamma_129
@@ -56,7 +56,7 @@ from critic_grad_ref import _bsum, _bsum32, reduction_roundings
 from policy_ref import U, _f64, _np32, gamma, layer, relu_err, tanh_err
 
 H = 256
-BACK_CHAIN = H // 2 + 1              # ta_da: a chain of 128 fma per accumulator, then acc0 + acc1
+BACK_CHAIN = H // 2 + 1              # cg_da: a chain of 128 fma per accumulator, then acc0 + acc1
 HEAD_CHAIN = 3                       # dz_2 of the actor: one product and two fmaf
 STRESS_BIAS = (12.0, 0.0, -12.0)     # added to mu.bias of td3_modules(head_scale=8.0)
 STRESS_MIN_PRE = 9.0                 # |pre| - e_pre on components 0 and 2 of the stress set: 1 - tanh(9)^2 = 6e-8 < u
