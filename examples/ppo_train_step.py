@@ -3,8 +3,11 @@
 step -> refresh of the rollout policy.
 
     env.collect_rollout(policy, T, gamma=...)     FusedPolicy + k_gae: what SB3's RolloutBuffer stores
-    pg.backward(...)                              FusedPPOGrad: evaluate_actions, the losses, backward, clip_grad_norm_
-    model.policy.optimizer.step()                 the stock torch optimiser on the p.grad the call left
+    rb.get(batch_size)                            DeviceRolloutBuffer: RolloutBuffer.get's shuffle, ONE launch per epoch; the
+                                                  minibatches are views
+    pg.backward(rollout_data, ...)                FusedPPOGrad: evaluate_actions, the losses, backward, clip_grad_norm_
+    fo.policy_step()                              FusedOptimStep: model.policy.optimizer.step() (PPO's Adam, A2C's RMSprop) in
+                                                  place on the optimiser's own state, one launch
     policy.refresh()                              the stepped parameters into the rollout policy's packed weights
 
 ``model`` is anything shaped like SB3 2.x's PPO / A2C (``.policy`` an ActorCriticPolicy with ``.optimizer``); the
@@ -21,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from reinforcementlearning4meshgeneration_amd import FusedPolicy, FusedPPOGrad, MeshVecEnv, boundary  # noqa: E402
+from reinforcementlearning4meshgeneration_amd import (DeviceRolloutBuffer, FusedOptimStep, FusedPolicy, FusedPPOGrad,  # noqa: E402
+                                                      MeshVecEnv, boundary)
 
 
 def stand_in(a2c: bool):
@@ -43,26 +47,20 @@ def stand_in(a2c: bool):
                                  _current_progress_remaining=1.0)
 
 
-def train_iteration(model, env, policy, pg, n_steps, counter):
+def train_iteration(model, env, policy, pg, rb, fo, n_steps, counter):
     """SB3's collect_rollouts + train() for one rollout.  Nothing in here synchronises with the host."""
     out = env.collect_rollout(policy, n_steps, seed=0, counter=counter, gamma=model.gamma, gae_lambda=model.gae_lambda)
-    rows = n_steps * env.num_envs
-    flat = {k: out[k].reshape(rows, *out[k].shape[2:]) for k in ("obs", "buffer_actions", "log_prob", "advantages", "returns")}
+    rb.load(out)                                                                # references: nothing is copied
     clip_range = None if model.clip_range is None else float(model.clip_range(model._current_progress_remaining))
-    batch = model.batch_size or rows
     last = None
     for _ in range(model.n_epochs):
-        perm = torch.randperm(rows, device=flat["obs"].device)                  # RolloutBuffer.get's shuffle
-        for start in range(0, rows, batch):
-            idx = perm[start:start + batch]
-            last = pg.backward(observations=flat["obs"][idx], actions=flat["buffer_actions"][idx], old_log_prob=flat["log_prob"][idx],
-                               advantages=flat["advantages"][idx], returns=flat["returns"][idx], clip_range=clip_range,
-                               ent_coef=model.ent_coef, vf_coef=model.vf_coef, normalize_advantage=model.normalize_advantage,
-                               max_grad_norm=model.max_grad_norm)
+        for rollout_data in rb.get(model.batch_size):                           # RolloutBuffer.get: one gather launch, then views
+            last = pg.backward(rollout_data, clip_range=clip_range, ent_coef=model.ent_coef, vf_coef=model.vf_coef,
+                               normalize_advantage=model.normalize_advantage, max_grad_norm=model.max_grad_norm)
             if model.target_kl is not None and float(last["approx_kl"]) > 1.5 * model.target_kl:    # A SYNCHRONISATION (SB3's early stop)
                 policy.refresh()
                 return last
-            model.policy.optimizer.step()
+            fo.policy_step()                                                    # model.policy.optimizer.step()
     policy.refresh()                                                            # after the last minibatch of the last epoch
     return last
 
@@ -81,10 +79,12 @@ def main():
     policy = FusedPolicy.from_sb3(model)
     policy.bind_live(model)
     pg = FusedPPOGrad.from_sb3(model)
+    rb = DeviceRolloutBuffer()
+    fo = FusedOptimStep.from_sb3(model)                                         # binds model.policy.optimizer: Adam or RMSprop
     for it in range(args.iterations):
-        last = train_iteration(model, env, policy, pg, args.n_steps, counter=it * args.n_steps)
+        last = train_iteration(model, env, policy, pg, rb, fo, args.n_steps, counter=it * args.n_steps)
         print(f"iteration {it}: " + " ".join(f"{k}={float(v):.5f}" for k, v in last.items()))     # outside the loop: reads back
-    pg.close(); policy.close(); env.close()
+    fo.close(); rb.close(); pg.close(); policy.close(); env.close()
 
 
 if __name__ == "__main__":

@@ -14,6 +14,9 @@
  *     op     MESHENV_OPTIM_ADAM         param, grad, exp_avg, exp_avg_sq       (target NULL)
  *            MESHENV_OPTIM_POLYAK       param (read), target                   (grad, exp_avg, exp_avg_sq NULL)
  *            MESHENV_OPTIM_ADAM_POLYAK  all five: the target sees the stepped parameter (TD3's actor -> actor_target)
+ *            MESHENV_OPTIM_RMSPROP      param, grad, exp_avg_sq = square_avg   (exp_avg, target NULL): torch.optim.RMSprop with
+ *                                       momentum = 0 and centered = False, A2C's default optimiser.  There is no RMSprop +
+ *                                       Polyak op: nothing on-policy has a target network
  *     n      elements, float32, contiguous
  *     block  which block of per-optimiser scalars the Adam update reads (0 .. MESHENV_OPTIM_BLOCKS - 1)
  *     vec    1 when every pointer of the segment is 16-byte aligned (128-bit loads and stores), 0 for the scalar path;
@@ -35,11 +38,12 @@ extern "C" {
 #define MESHENV_OPTIM_BLOCKS 4
 #define MESHENV_OPTIM_CHUNK 1024 /* elements per workgroup */
 
-enum { MESHENV_OPTIM_ADAM = 1, MESHENV_OPTIM_POLYAK = 2, MESHENV_OPTIM_ADAM_POLYAK = 3 };
+enum { MESHENV_OPTIM_ADAM = 1, MESHENV_OPTIM_POLYAK = 2, MESHENV_OPTIM_ADAM_POLYAK = 3, MESHENV_OPTIM_RMSPROP = 4 };
 
 /* The scalars of one step, computed on the host in doubles exactly as torch.optim.adam._single_tensor_adam does from the
  * incremented step, then rounded to float: step_size = lr / (1 - beta1^step), bc2_sqrt = (1 - beta2^step)^0.5,
- * w1 = 1 - beta1, w2 = 1 - beta2. */
+ * w1 = 1 - beta1, w2 = 1 - beta2.  A block read by MESHENV_OPTIM_RMSPROP segments holds alpha in beta2, 1 - alpha in w2, lr in
+ * step_size, and eps; its w1 and bc2_sqrt are not read. */
 typedef struct MeshOptimScalars {
     float step_size[MESHENV_OPTIM_BLOCKS];
     float bc2_sqrt[MESHENV_OPTIM_BLOCKS];

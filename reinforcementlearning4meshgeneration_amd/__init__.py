@@ -9,7 +9,7 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
            "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
            "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
-           "FusedPPOGrad", "PPOGradSpec"]
+           "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -55,4 +55,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedPPOGrad", "PPOGradSpec"):
         from . import ppo_grad
         return getattr(ppo_grad, name)
+    if name in ("DeviceRolloutBuffer", "RolloutBufferSamples"):
+        from . import rollout_buffer
+        return getattr(rollout_buffer, name)
     raise AttributeError(name)

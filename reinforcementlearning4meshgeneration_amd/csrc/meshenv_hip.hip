@@ -7,6 +7,7 @@
 #include "../../include/meshenv_optim.h"
 #include "../../include/meshenv_td3_actor_grad.h"
 #include "../../include/meshenv_ppo_grad.h"
+#include "../../include/meshenv_rollout.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -36,6 +37,7 @@
 #include "meshenv_td3_actor_grad.h"
 #include "meshenv_ppo_grad.h"
 #include "meshenv_optim.h"
+#include "meshenv_rollout.h"
 
 using namespace meshenv;
 
@@ -237,7 +239,7 @@ int fail_arg(MeshEnv *h, const char *msg)
 }
 
 // ---- what the handles of the fused networks share (MeshActor, MeshPolicy, MeshTarget, MeshCriticGrad, MeshActorGrad, MeshTd3ActorGrad,
-// MeshOptim)
+// MeshOptim, MeshRolloutBuffer)
 struct HandleBase {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -3165,6 +3167,7 @@ int meshenv_policy_refresh(MeshPolicy *p)
 static_assert(sizeof(MeshOptimScalars) == sizeof(OptScalars), "include/meshenv_optim.h and csrc/meshenv_optim.h disagree");
 static_assert(MESHENV_OPTIM_BLOCKS == kOptBlocks && MESHENV_OPTIM_CHUNK == kOptChunk, "include/meshenv_optim.h and csrc/meshenv_optim.h disagree");
 static_assert(MESHENV_OPTIM_ADAM == kOptAdam && MESHENV_OPTIM_POLYAK == kOptPolyak && MESHENV_OPTIM_ADAM_POLYAK == kOptAdamPolyak, "ops");
+static_assert(MESHENV_OPTIM_RMSPROP == kOptRmsprop, "ops");
 
 struct OptProgram {
     char *dev = nullptr;        // the segment table, then the job table
@@ -3219,14 +3222,15 @@ int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param
     int64_t n_jobs = 0;
     for (int i = 0; i < n_seg; i++) {
         const std::string at = "meshenv_optim_bind: segment " + std::to_string(i) + ": ";
-        if (op[i] != kOptAdam && op[i] != kOptPolyak && op[i] != kOptAdamPolyak)
+        if (op[i] != kOptAdam && op[i] != kOptPolyak && op[i] != kOptAdamPolyak && op[i] != kOptRmsprop)
             return fail(o, MESHENV_E_ARG, at + "op " + std::to_string(op[i]));
         if (n[i] < 1 || n[i] > INT32_MAX - kOptChunk)
             return fail(o, MESHENV_E_ARG, at + std::to_string((long long)n[i]) + " elements");
         if (block[i] < 0 || block[i] >= kOptBlocks) return fail(o, MESHENV_E_ARG, at + "block " + std::to_string(block[i]));
-        const bool adam = op[i] & kOptAdam, polyak = op[i] & kOptPolyak;
-        if (!param_dev[i] || adam != (grad_dev[i] != nullptr) || adam != (exp_avg_dev[i] != nullptr) ||
-            adam != (exp_avg_sq_dev[i] != nullptr) || polyak != (target_dev[i] != nullptr))
+        // RMSprop takes the gradient and square_avg (in exp_avg_sq_dev) and no first moment
+        const bool adam = op[i] & kOptAdam, polyak = op[i] & kOptPolyak, steps = adam || op[i] == kOptRmsprop;
+        if (!param_dev[i] || steps != (grad_dev[i] != nullptr) || adam != (exp_avg_dev[i] != nullptr) ||
+            steps != (exp_avg_sq_dev[i] != nullptr) || polyak != (target_dev[i] != nullptr))
             return fail(o, MESHENV_E_ARG, at + "the pointers do not match op " + std::to_string(op[i]));
         const uintptr_t all = (uintptr_t)param_dev[i] | (uintptr_t)grad_dev[i] | (uintptr_t)exp_avg_dev[i] |
                               (uintptr_t)exp_avg_sq_dev[i] | (uintptr_t)target_dev[i];
@@ -3298,6 +3302,75 @@ int meshenv_optim_step(MeshOptim *o, int program, const MeshOptimScalars *scalar
     return launch(o, guard, "meshenv_optim_step", [&] {
         hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
                            (const OptJob *)(P.dev + P.jobs_at), S);
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the on-policy rollout buffer
+static_assert(MESHENV_ROLLOUT_CHUNK == kRgChunk && MESHENV_ROLLOUT_FIELDS == 2 + kRgScalars, "include/meshenv_rollout.h and csrc/meshenv_rollout.h disagree");
+static_assert((long long)MESHENV_ROLLOUT_MAX_ROWS * kRgObs + kRgChunk <= INT32_MAX, "k_rollout_gather indexes in int32");
+
+struct MeshRolloutBuffer : HandleBase {};
+
+extern "C" {
+
+int meshenv_rollout_create(int device, void *stream, MeshRolloutBuffer **out)
+{
+    return create_handle("meshenv_rollout_create", device, stream, out);
+}
+
+void meshenv_rollout_destroy(MeshRolloutBuffer *r) { destroy_handle(r, nullptr); }
+
+const char *meshenv_rollout_last_error(const MeshRolloutBuffer *r) { return last_error(r); }
+
+int meshenv_rollout_set_stream(MeshRolloutBuffer *r, void *stream) { return set_stream(r, stream); }
+
+int meshenv_rollout_gather(MeshRolloutBuffer *r, int T, int n_envs, const void *perm_dev, int perm_bytes,
+                           const float *const *in_dev, float *const *out_dev, int variant)
+{
+    if (!r) return MESHENV_E_ARG;
+    const char *fn = "meshenv_rollout_gather";
+    if (T < 1 || n_envs < 1 || (long long)T * n_envs > MESHENV_ROLLOUT_MAX_ROWS)
+        return fail(r, MESHENV_E_ARG, std::string(fn) + ": T >= 1, n_envs >= 1 and T * n_envs <= 2^24 - 16 are required");
+    if (perm_bytes != 4 && perm_bytes != 8) return fail(r, MESHENV_E_ARG, std::string(fn) + ": perm_bytes is 4 (int32) or 8 (int64)");
+    if (variant != 0 && variant != 1) return fail(r, MESHENV_E_ARG, std::string(fn) + ": variant is 0 or 1");
+    if (!perm_dev || !in_dev || !out_dev) return fail(r, MESHENV_E_ARG, std::string(fn) + ": perm_dev, in_dev and out_dev are required");
+    if ((uintptr_t)perm_dev & (uintptr_t)(perm_bytes - 1)) return fail(r, MESHENV_E_ARG, std::string(fn) + ": perm_dev is off the alignment of its indices");
+    const int rows = T * n_envs;
+    const size_t width[MESHENV_ROLLOUT_FIELDS] = {kRgObs, kRgAct, 1, 1, 1, 1};
+    for (int f = 0; f < MESHENV_ROLLOUT_FIELDS; f++) {
+        if (!in_dev[f] || !out_dev[f]) return fail(r, MESHENV_E_ARG, std::string(fn) + ": null pointer for field " + std::to_string(f));
+        if (((uintptr_t)in_dev[f] | (uintptr_t)out_dev[f]) & 3)
+            return fail(r, MESHENV_E_ARG, std::string(fn) + ": a pointer of field " + std::to_string(f) + " is not 4-byte aligned");
+    }
+    // every output against every input and every other output: a thread reads rows that other threads write
+    for (int f = 0; f < MESHENV_ROLLOUT_FIELDS; f++) {
+        const uintptr_t o0 = (uintptr_t)out_dev[f], o1 = o0 + width[f] * rows * sizeof(float);
+        for (int k = 0; k < MESHENV_ROLLOUT_FIELDS; k++) {
+            const uintptr_t i0 = (uintptr_t)in_dev[k], i1 = i0 + width[k] * rows * sizeof(float);
+            const uintptr_t p0 = (uintptr_t)out_dev[k], p1 = p0 + width[k] * rows * sizeof(float);
+            if ((o0 < i1 && i0 < o1) || (k != f && o0 < p1 && p0 < o1))
+                return fail(r, MESHENV_E_ARG, std::string(fn) + ": the output of field " + std::to_string(f) + " overlaps field " + std::to_string(k));
+        }
+        const uintptr_t q0 = (uintptr_t)perm_dev, q1 = q0 + (size_t)perm_bytes * rows;
+        if (o0 < q1 && q0 < o1) return fail(r, MESHENV_E_ARG, std::string(fn) + ": the output of field " + std::to_string(f) + " overlaps perm_dev");
+    }
+    if (variant == 1 && (((uintptr_t)in_dev[0] | (uintptr_t)out_dev[0]) & 7))
+        return fail(r, MESHENV_E_ARG, std::string(fn) + ": variant 1 needs both observation pointers 8-byte aligned");
+    RolloutGatherArgs A{};
+    A.obs = in_dev[0]; A.act = in_dev[1]; A.obs_out = out_dev[0]; A.act_out = out_dev[1];
+    for (int f = 0; f < kRgScalars; f++) { A.scalar[f] = in_dev[2 + f]; A.scalar_out[f] = out_dev[2 + f]; }
+    A.perm = perm_dev; A.perm64 = perm_bytes == 8;
+    A.T = T; A.n = n_envs; A.rows = rows;
+    A.obs_blocks = (rows * kRgObs + kRgChunk - 1) / kRgChunk;
+    A.act_blocks = (rows * kRgAct + kRgChunk - 1) / kRgChunk;
+    A.scalar_blocks = (rows + kRgChunk - 1) / kRgChunk;
+    const int grid = A.obs_blocks + A.act_blocks + kRgScalars * A.scalar_blocks;
+    DeviceGuard guard(r->device);
+    return launch(r, guard, fn, [&] {
+        if (variant == 1) hipLaunchKernelGGL(k_rollout_gather<true>, dim3(grid), dim3(kRgThreads), 0, r->stream, A);
+        else hipLaunchKernelGGL(k_rollout_gather<false>, dim3(grid), dim3(kRgThreads), 0, r->stream, A);
     });
 }
 

@@ -1,4 +1,4 @@
-// k_optim_step: the Adam steps of SAC / TD3 and SB3's polyak_update over any mix of tensors in one launch
+// k_optim_step: the Adam steps of SAC / TD3 / PPO, A2C's RMSprop step and SB3's polyak_update over any mix of tensors in one launch
 // (include/meshenv_optim.h).
 //
 // A launch is driven by two tables in device memory, written by meshenv_optim_bind: the SEGMENTS, one per tensor (its
@@ -21,6 +21,12 @@
 //     d  = sqrtf(v) / bias_correction2_sqrt + eps          (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
 //     p  = p + (-step_size) * (m / d)                      param.addcdiv_(exp_avg, denom, value=-step_size)
 //     t  = t * (1 - tau) + tau * p                         target.mul_(1 - tau); target.add_(param, alpha=tau)
+// and, for the on-policy recipes (A2C's default optimiser), torch.optim.rmsprop._single_tensor_rmsprop
+// with momentum = 0 and centered = False: kOptRmsprop, whose block of scalars carries alpha in beta2, 1 - alpha in w2 and lr
+// in step_size, and whose v is square_avg (no first moment: m is NULL):
+//     v  = v * alpha + ((1 - alpha) * g) * g               square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+//     d  = sqrtf(v) + eps                                  square_avg.sqrt().add_(eps)
+//     p  = p + (-lr) * (g / d)                             param.addcdiv_(grad, avg, value=-lr)
 // Non-finite gradients go through the same operations and propagate as they do there.
 #pragma once
 
@@ -33,15 +39,15 @@ constexpr int kOptChunk = 1024;     // elements per workgroup: 256 threads x 4
 constexpr int kOptThreads = 256;
 constexpr int kOptBlocks = 4;       // blocks of per-optimiser scalars a launch can carry
 
-enum { kOptAdam = 1, kOptPolyak = 2, kOptAdamPolyak = 3 };
+enum { kOptAdam = 1, kOptPolyak = 2, kOptAdamPolyak = 3, kOptRmsprop = 4 };
 
 struct OptSeg {
     float *p;           // the parameter: written by Adam, read by Polyak
     const float *g;     // its gradient (Adam)
-    float *m, *v;       // exp_avg, exp_avg_sq (Adam)
+    float *m, *v;       // exp_avg, exp_avg_sq (Adam); RMSprop: NULL, square_avg
     float *t;           // the target parameter (Polyak)
     int32_t n;          // elements
-    int32_t op;         // kOptAdam, kOptPolyak, kOptAdamPolyak
+    int32_t op;         // kOptAdam, kOptPolyak, kOptAdamPolyak, kOptRmsprop
     int32_t block;      // which OptScalars block (Adam)
     int32_t vec;        // 1: all of this segment's pointers are 16-byte aligned
 };
@@ -76,6 +82,11 @@ __device__ __forceinline__ void opt_element(const OptCoef &c, float &p, float g,
         p = p + c.neg_step * (m / d);
     }
     if (OP & kOptPolyak) t = t * c.omt + c.tau * p;
+    if (OP == kOptRmsprop) {
+        v = v * c.beta2 + (c.w2 * g) * g;
+        const float d = sqrtf(v) + c.eps;
+        p = p + c.neg_step * (g / d);
+    }
 }
 
 template <int OP>
@@ -84,8 +95,10 @@ __device__ __forceinline__ void opt_one(const OptSeg &s, const OptCoef &c, int i
     float p = s.p[i], g = 0.0f, m = 0.0f, v = 0.0f, t = 0.0f;
     if (OP & kOptAdam) { g = s.g[i]; m = s.m[i]; v = s.v[i]; }
     if (OP & kOptPolyak) t = s.t[i];
+    if (OP == kOptRmsprop) { g = s.g[i]; v = s.v[i]; }
     opt_element<OP>(c, p, g, m, v, t);
     if (OP & kOptAdam) { s.p[i] = p; s.m[i] = m; s.v[i] = v; }
+    if (OP == kOptRmsprop) { s.p[i] = p; s.v[i] = v; }
     if (OP & kOptPolyak) s.t[i] = t;
 }
 
@@ -102,6 +115,10 @@ __device__ __forceinline__ void opt_chunk(const OptSeg &s, const OptCoef &c, int
             v = *reinterpret_cast<const float4 *>(s.v + i4);
         }
         if (OP & kOptPolyak) t = *reinterpret_cast<const float4 *>(s.t + i4);
+        if (OP == kOptRmsprop) {
+            g = *reinterpret_cast<const float4 *>(s.g + i4);
+            v = *reinterpret_cast<const float4 *>(s.v + i4);
+        }
         opt_element<OP>(c, p.x, g.x, m.x, v.x, t.x);
         opt_element<OP>(c, p.y, g.y, m.y, v.y, t.y);
         opt_element<OP>(c, p.z, g.z, m.z, v.z, t.z);
@@ -112,6 +129,10 @@ __device__ __forceinline__ void opt_chunk(const OptSeg &s, const OptCoef &c, int
             *reinterpret_cast<float4 *>(s.v + i4) = v;
         }
         if (OP & kOptPolyak) *reinterpret_cast<float4 *>(s.t + i4) = t;
+        if (OP == kOptRmsprop) {
+            *reinterpret_cast<float4 *>(s.p + i4) = p;
+            *reinterpret_cast<float4 *>(s.v + i4) = v;
+        }
     } else if (s.vec) {                         // the segment's last, partial group of four
         for (int i = i4; i < s.n; i++) opt_one<OP>(s, c, i);
     } else {
@@ -131,6 +152,7 @@ __global__ __launch_bounds__(kOptThreads) void k_optim_step(const OptSeg *__rest
     c.eps = S.eps[b]; c.tau = S.tau; c.omt = S.one_minus_tau;
     if (s.op == kOptAdam) opt_chunk<kOptAdam>(s, c, job.first);
     else if (s.op == kOptPolyak) opt_chunk<kOptPolyak>(s, c, job.first);
+    else if (s.op == kOptRmsprop) opt_chunk<kOptRmsprop>(s, c, job.first);
     else opt_chunk<kOptAdamPolyak>(s, c, job.first);
 }
 

@@ -5,7 +5,13 @@ meshenv_optim_*, csrc/meshenv_optim.h: k_optim_step): the statements that follow
     self.actor.optimizer.step();  self.ent_coef_optimizer.step()
     polyak_update(self.critic.parameters(), self.critic_target.parameters(), self.tau)      # TD3: the actor's too
 
-as two launches: ``critic_step()`` and ``actor_step(polyak=True)``.  The kernel applies torch's Adam (the order of operations
+as two launches: ``critic_step()`` and ``actor_step(polyak=True)``; and the one statement of ``PPO.train`` / ``A2C.train``,
+
+    self.policy.optimizer.step()
+
+as one: ``policy_step()``, for PPO's Adam and for A2C's default ``torch.optim.RMSprop(alpha=0.99, eps=1e-5)`` (momentum = 0,
+not centered: ``torch.optim.rmsprop._single_tensor_rmsprop``; its ``square_avg`` is updated in place like Adam's moments).
+The kernel applies torch's Adam (the order of operations
 of ``torch.optim.adam._single_tensor_adam``, non-capturable) IN PLACE to the live parameters and to the optimiser's OWN state
 tensors (``exp_avg``, ``exp_avg_sq``; ``step`` is incremented on the host), so ``optimizer.state_dict()``,
 ``load_state_dict()`` and a stock ``optimizer.step()`` in between keep working, and applies ``t = t (1 - tau) + tau p`` to the
@@ -27,11 +33,14 @@ from .sb3_nets import check_device
 
 CHUNK = _capi.OPTIM_CHUNK            # elements per workgroup
 THREADS = 256
-ADAM, POLYAK, ADAM_POLYAK = _capi.OPTIM_ADAM, _capi.OPTIM_POLYAK, _capi.OPTIM_ADAM_POLYAK
-PROGRAMS = ("critic", "actor_polyak", "actor", "polyak")      # meshenv_optim_bind's program index
+ADAM, POLYAK, ADAM_POLYAK, RMSPROP = _capi.OPTIM_ADAM, _capi.OPTIM_POLYAK, _capi.OPTIM_ADAM_POLYAK, _capi.OPTIM_RMSPROP
+PROGRAMS = ("critic", "actor_polyak", "actor", "polyak", "policy")      # meshenv_optim_bind's program index
 SUPPORTED = ("torch.optim.Adam with one param group, float32 contiguous parameters, and none of amsgrad, maximize, "
              "weight_decay, capturable, differentiable, decoupled_weight_decay, fused")
 _FLAGS = ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay", "fused")
+SUPPORTED_RMSPROP = ("torch.optim.RMSprop with one param group, float32 contiguous parameters, momentum = 0, and none of centered, "
+                     "weight_decay, maximize, capturable, differentiable")
+_FLAGS_RMSPROP = ("centered", "maximize", "capturable", "differentiable")
 
 
 def adam_scalars(step: float, lr: float, beta1: float, beta2: float) -> Tuple[float, float]:
@@ -42,6 +51,11 @@ def adam_scalars(step: float, lr: float, beta1: float, beta2: float) -> Tuple[fl
     step_size = lr / bias_correction1
     bias_correction2_sqrt = bias_correction2 ** 0.5
     return step_size, bias_correction2_sqrt
+
+
+def _is_rmsprop(opt) -> bool:
+    import torch
+    return type(opt) is torch.optim.RMSprop
 
 
 @dataclass
@@ -60,7 +74,8 @@ class Segment:
 
 @dataclass
 class Row:
-    """A segment with the tensors of this call: (param, grad, exp_avg, exp_avg_sq, target), None where the op takes none."""
+    """A segment with the tensors of this call: (param, grad, exp_avg, exp_avg_sq, target), None where the op takes none
+    (RMSprop: its square_avg travels as exp_avg_sq and there is no exp_avg)."""
     seg: Segment
     tensors: tuple
 
@@ -86,10 +101,13 @@ class Plan:
 
 class OptimStepSpec:
     """critic: the optimiser ``critic_step`` runs (or None); actor: the optimisers ``actor_step`` runs, in order (SAC: the
-    actor's and the entropy coefficient's); polyak: [(source parameters, target parameters)]; tau in [0, 1]."""
+    actor's and the entropy coefficient's); polyak: [(source parameters, target parameters)]; tau in [0, 1]; policy: the
+    optimiser ``policy_step`` runs (PPO / A2C: ``model.policy.optimizer``).  Every slot takes a torch.optim.Adam or a
+    torch.optim.RMSprop."""
 
-    def __init__(self, critic=None, actor: Sequence = (), polyak: Sequence = (), tau: float = 0.005):
+    def __init__(self, critic=None, actor: Sequence = (), polyak: Sequence = (), tau: float = 0.005, policy=None):
         self.critic = critic
+        self.policy = policy
         self.actor = list(actor)
         if len(self.actor) > _capi.OPTIM_BLOCKS:
             raise ValueError(f"{len(self.actor)} optimisers in one launch; at most {_capi.OPTIM_BLOCKS}")
@@ -132,11 +150,13 @@ class OptimStepSpec:
 
     # ---------------------------------------------------------------- refusals
     def optimizers(self):
-        return ([self.critic] if self.critic is not None else []) + self.actor
+        return ([self.critic] if self.critic is not None else []) + self.actor + ([self.policy] if self.policy is not None else [])
 
     def _opt_name(self, opt) -> str:
         if opt is self.critic:
             return "the critic optimiser"
+        if opt is self.policy:
+            return "the policy optimiser"
         return f"actor-step optimiser {[id(o) for o in self.actor].index(id(opt))}"
 
     @staticmethod
@@ -153,6 +173,18 @@ class OptimStepSpec:
     def _group(cls, opt, name):
         """param_groups[0] after the checks that a later ``add_param_group`` or an edited flag would break."""
         groups = opt.param_groups
+        if _is_rmsprop(opt):
+            if len(groups) != 1:
+                raise ValueError(f"{name} has {len(groups)} param groups; supported: {SUPPORTED_RMSPROP}")
+            g = groups[0]
+            if g.get("momentum", 0) != 0:
+                raise ValueError(f"{name} has momentum={g['momentum']!r}; supported: {SUPPORTED_RMSPROP}")
+            for flag in _FLAGS_RMSPROP:
+                if g.get(flag):
+                    raise ValueError(f"{name} has {flag}={g[flag]!r}; supported: {SUPPORTED_RMSPROP}")
+            if g.get("weight_decay", 0) != 0:
+                raise ValueError(f"{name} has weight_decay={g['weight_decay']!r}; supported: {SUPPORTED_RMSPROP}")
+            return g
         if len(groups) != 1:
             raise ValueError(f"{name} has {len(groups)} param groups; supported: {SUPPORTED}")
         g = groups[0]
@@ -166,8 +198,9 @@ class OptimStepSpec:
     @classmethod
     def _check_optimizer(cls, opt, name) -> None:
         import torch
-        if type(opt) is not torch.optim.Adam:
-            raise ValueError(f"{name} is {type(opt).__module__}.{type(opt).__name__}, not torch.optim.Adam; supported: {SUPPORTED}")
+        if type(opt) is not torch.optim.Adam and not _is_rmsprop(opt):
+            raise ValueError(f"{name} is {type(opt).__module__}.{type(opt).__name__}, not torch.optim.Adam or torch.optim.RMSprop; "
+                             f"supported: {SUPPORTED}; or {SUPPORTED_RMSPROP}")
         g = cls._group(opt, name)
         for i, p in enumerate(g["params"]):
             cls._check_tensor(p, f"{name}: parameter {i}")
@@ -177,6 +210,8 @@ class OptimStepSpec:
         target_of = {id(p): t for p, t in self.pairs}
         if program == "critic":
             opts, polyak = ([self.critic] if self.critic is not None else []), False
+        elif program == "policy":
+            opts, polyak = ([self.policy] if self.policy is not None else []), False
         elif program == "polyak":
             opts, polyak = [], True
         else:
@@ -186,8 +221,12 @@ class OptimStepSpec:
             for i, p in enumerate(opt.param_groups[0]["params"]):
                 t = target_of.get(id(p)) if polyak else None
                 if t is not None:
+                    if _is_rmsprop(opt):             # a target must see the stepped value; no such op is built
+                        raise ValueError(f"{self._opt_name(opt)}: parameter {i} is stepped by RMSprop and is a Polyak source; there is "
+                                         "no RMSprop + Polyak launch")
                     fused.add(id(p))
-                segs.append(Segment(ADAM if t is None else ADAM_POLYAK, b, p, t, f"optimiser {b} parameter {i}"))
+                op = RMSPROP if _is_rmsprop(opt) else ADAM if t is None else ADAM_POLYAK
+                segs.append(Segment(op, b, p, t, f"optimiser {b} parameter {i}"))
         if polyak:
             # a source stepped by this launch is updated by the thread that stepped it; every other pair is a segment of its
             # own and reads what earlier launches left (critic -> critic_target after critic_step)
@@ -214,22 +253,30 @@ class OptimStepSpec:
     def _optimizers_of(self, program):
         if program == "critic":
             return [self.critic] if self.critic is not None else []
+        if program == "policy":
+            return [self.policy] if self.policy is not None else []
         return [] if program == "polyak" else self.actor
 
     def prepare(self, program: str) -> Plan:
         """The tensors of this call: validates the optimisers, the gradients and the state, creating the state of a parameter
-        that has none the way ``Adam._init_group`` does.  Nothing is stepped yet (``commit``)."""
+        that has none the way ``Adam._init_group`` / ``RMSprop._init_group`` does.  Nothing is stepped yet (``commit``)."""
         import torch
         segs = self._segments[program]
         if not segs:
             raise ValueError(f"nothing bound for {program!r}: " +
-                             ("no critic optimiser" if program == "critic" else "no Polyak pairs" if program == "polyak" else "no actor optimisers"))
+                             ("no critic optimiser" if program == "critic" else "no Polyak pairs" if program == "polyak" else
+                              "no policy optimiser" if program == "policy" else "no actor optimisers"))
         groups, tensors = [], {}
         for b, opt in enumerate(self._optimizers_of(program)):
             name = self._opt_name(opt)
             g = self._group(opt, name)
-            if torch.is_tensor(g["lr"]) or any(torch.is_tensor(x) for x in g["betas"]):
+            rms = _is_rmsprop(opt)
+            if rms:
+                if any(torch.is_tensor(g[k]) for k in ("lr", "alpha", "eps")):
+                    raise ValueError(f"{name}: lr, alpha and eps must be Python floats, not tensors")
+            elif torch.is_tensor(g["lr"]) or any(torch.is_tensor(x) for x in g["betas"]):
                 raise ValueError(f"{name}: lr and betas must be Python floats, not tensors")
+            moments = ("square_avg",) if rms else ("exp_avg", "exp_avg_sq")
             steps = []
             for i, p in enumerate(g["params"]):
                 what = f"{name}: parameter {i} of shape {tuple(p.shape)}"
@@ -243,19 +290,25 @@ class OptimStepSpec:
                 if grad.device != p.device:
                     raise ValueError(f"{what}: .grad is on {grad.device}, the parameter on {p.device}")
                 st = opt.state[p]
-                if len(st) == 0:                      # Adam._init_group, capturable and fused off
+                if len(st) == 0 and rms:              # RMSprop._init_group, capturable off, momentum = 0, not centered
+                    st["step"] = torch.zeros((), dtype=torch.float32)
+                    st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                elif len(st) == 0:                    # Adam._init_group, capturable and fused off
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 step = st["step"]
                 if not torch.is_tensor(step) or step.device.type != "cpu":
                     raise ValueError(f"{what}: state['step'] is not a CPU tensor (capturable or fused state?)")
-                for k in ("exp_avg", "exp_avg_sq"):
+                if rms and set(st) != {"step", "square_avg"}:
+                    raise ValueError(f"{what}: its RMSprop state holds {sorted(st)}, not 'step' and 'square_avg' alone "
+                                     "(the state of momentum or centered?)")
+                for k in moments:
                     s = st[k]
                     if s.dtype != torch.float32 or not s.is_contiguous() or s.shape != p.shape or s.device != p.device:
                         raise ValueError(f"{what}: state[{k!r}] is not a float32 contiguous tensor like the parameter")
                 steps.append(step)
-                tensors[id(p)] = (grad, st["exp_avg"], st["exp_avg_sq"])
+                tensors[id(p)] = (grad, None, st["square_avg"]) if rms else (grad, st["exp_avg"], st["exp_avg_sq"])
             if not steps:
                 raise ValueError(f"{name} has no parameters")
             values = [float(s) for s in steps]
@@ -264,7 +317,7 @@ class OptimStepSpec:
             groups.append((g, steps))
         rows = []
         for s in segs:
-            g_, m_, v_ = tensors[id(s.param)] if s.op & ADAM else (None, None, None)
+            g_, m_, v_ = tensors[id(s.param)] if s.op & ADAM or s.op == RMSPROP else (None, None, None)
             rows.append(Row(s, (s.param, g_, m_, v_, s.target)))
         return Plan(program, rows, groups)
 
@@ -274,6 +327,10 @@ class OptimStepSpec:
         for b, (g, steps) in enumerate(plan.groups):
             for s in steps:
                 s += 1
+            if "betas" not in g:                     # an RMSprop group: alpha in beta2, 1 - alpha in w2, lr in step_size; the others unread
+                S.step_size[b], S.bc2_sqrt[b], S.w1[b] = g["lr"], 1.0, 0.0
+                S.beta2[b], S.w2[b], S.eps[b] = g["alpha"], 1 - g["alpha"], g["eps"]
+                continue
             beta1, beta2 = g["betas"]
             S.step_size[b], S.bc2_sqrt[b] = adam_scalars(steps[0].item(), g["lr"], beta1, beta2)
             S.w1[b], S.beta2[b], S.w2[b], S.eps[b] = 1 - beta1, beta2, 1 - beta2, g["eps"]
@@ -293,10 +350,19 @@ class OptimStepSpec:
         return cls(critic_optimizer, [actor_optimizer], [(critic_params, critic_target_params), (actor_params, actor_target_params)], tau)
 
     @classmethod
+    def on_policy(cls, optimizer) -> "OptimStepSpec":
+        return cls(policy=optimizer)
+
+    @classmethod
     def from_sb3(cls, model) -> "OptimStepSpec":
-        """Duck-typed on SB3 2.x's SAC (``critic.optimizer``, ``actor.optimizer``, ``ent_coef_optimizer`` when
+        """A PPO / A2C model or its ActorCriticPolicy (``.policy``, or the object itself, has ``mlp_extractor`` and a non-None
+        ``optimizer``): that optimiser is bound to ``policy``.  Otherwise duck-typed on SB3 2.x's SAC
+        (``critic.optimizer``, ``actor.optimizer``, ``ent_coef_optimizer`` when
         ``log_ent_coef`` is learned, ``critic`` -> ``critic_target``) and TD3 / DDPG (``critic.optimizer``,
         ``actor.optimizer``, ``critic`` -> ``critic_target``, ``actor`` -> ``actor_target``), with ``model.tau``."""
+        for pol in (getattr(model, "policy", None), model):
+            if pol is not None and hasattr(pol, "mlp_extractor") and getattr(pol, "optimizer", None) is not None:
+                return cls.on_policy(pol.optimizer)
         name = type(model).__name__
         actor, critic, critic_target = (getattr(model, k, None) for k in ("actor", "critic", "critic_target"))
         if actor is None or critic is None or critic_target is None:
@@ -344,8 +410,8 @@ def _no_batch_norm(model, name) -> None:
 
 
 class FusedOptimStep(Handle):
-    """An OptimStepSpec bound on one GPU: critic_step(), actor_step(polyak=True), polyak(); one launch each on the current
-    stream, no synchronisation while the tensors' pointers stay what they were."""
+    """An OptimStepSpec bound on one GPU: critic_step(), actor_step(polyak=True), polyak(), policy_step(); one launch each on
+    the current stream, no synchronisation while the tensors' pointers stay what they were."""
     PREFIX = "meshenv_optim"
 
     def __init__(self, spec: OptimStepSpec, device: int = 0):
@@ -364,6 +430,11 @@ class FusedOptimStep(Handle):
             actor_target_params=(), tau: float = 0.005, device: int = 0):
         return cls(OptimStepSpec.td3(critic_optimizer, actor_optimizer, critic_params, critic_target_params, actor_params,
                                      actor_target_params, tau), device)
+
+    @classmethod
+    def on_policy(cls, optimizer, device: int = 0):
+        """PPO's / A2C's one optimiser (``model.policy.optimizer``), for ``policy_step()``."""
+        return cls(OptimStepSpec.on_policy(optimizer), device)
 
     @classmethod
     def from_sb3(cls, model, device: int = 0):
@@ -406,3 +477,7 @@ class FusedOptimStep(Handle):
     def polyak(self) -> None:
         """``polyak_update`` of every pair alone.  One launch."""
         self._run("polyak")
+
+    def policy_step(self) -> None:
+        """Adam or RMSprop on the policy optimiser: ``model.policy.optimizer.step()`` of PPO / A2C.  One launch."""
+        self._run("policy")

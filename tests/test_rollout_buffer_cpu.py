@@ -1,0 +1,221 @@
+"""Host only: the numpy restatement of the rollout gather (tests/rollout_buffer_ref.py) against a transcription of SB3 2.x's
+``RolloutBuffer.get``; the index convention; the short last minibatch; ``batch_size=None``; the NaN rule of an index that is no
+row; every refusal of ``DeviceRolloutBuffer.load`` / ``get`` that needs no device; packaging."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import rollout_buffer_ref as RB
+
+
+# ----------------------------------------------------------------------------------------------------------- SB3, transcribed
+class _Sb3RolloutBuffer:
+    """stable_baselines3.common.buffers.RolloutBuffer: the arrays ``add`` fills ([buffer_size, n_envs, ...]) and ``get`` /
+    ``_get_samples`` / ``swap_and_flatten`` as SB3 2.x writes them (``to_torch`` left out: the samples stay numpy)."""
+
+    def __init__(self, out):
+        self.buffer_size, self.n_envs = out["obs"].shape[:2]
+        self.observations, self.actions = out["obs"].copy(), out["buffer_actions"].copy()
+        self.values, self.log_probs = out["value"].copy(), out["log_prob"].copy()
+        self.advantages, self.returns = out["advantages"].copy(), out["returns"].copy()
+        self.generator_ready = False
+        self.full = True
+
+    @staticmethod
+    def swap_and_flatten(arr):
+        shape = arr.shape
+        if len(shape) < 3:
+            shape = (*shape, 1)
+        return arr.swapaxes(0, 1).reshape(shape[0] * shape[1], *shape[2:])
+
+    def get(self, batch_size=None):
+        assert self.full, ""
+        indices = np.random.permutation(self.buffer_size * self.n_envs)
+        # Prepare the data
+        if not self.generator_ready:
+            _tensor_names = ["observations", "actions", "values", "log_probs", "advantages", "returns"]
+            for tensor in _tensor_names:
+                self.__dict__[tensor] = self.swap_and_flatten(self.__dict__[tensor])
+            self.generator_ready = True
+        # Return everything, don't create minibatches
+        if batch_size is None:
+            batch_size = self.buffer_size * self.n_envs
+        start_idx = 0
+        while start_idx < self.buffer_size * self.n_envs:
+            yield self._get_samples(indices[start_idx: start_idx + batch_size])
+            start_idx += batch_size
+
+    def _get_samples(self, batch_inds):
+        data = (self.observations[batch_inds], self.actions[batch_inds], self.values[batch_inds].flatten(),
+                self.log_probs[batch_inds].flatten(), self.advantages[batch_inds].flatten(), self.returns[batch_inds].flatten())
+        return dict(zip(RB.FIELDS, data))
+
+
+@pytest.mark.parametrize("T,n", RB.SHAPES)
+@pytest.mark.parametrize("batch_size", RB.BATCH_SIZES)
+def test_restatement_is_sb3s_get_with_numpys_own_permutation(T, n, batch_size):
+    out = RB.rollout(T, n)
+    rows = T * n
+    np.random.seed(7 + rows)
+    theirs = list(_Sb3RolloutBuffer(out).get(batch_size))
+    np.random.seed(7 + rows)
+    perm = np.random.permutation(rows)                       # the draw SB3 made
+    mine = RB.get(out, perm, batch_size)
+    assert len(mine) == len(theirs) == (1 if batch_size is None else -(-rows // batch_size))
+    for a, b in zip(mine, theirs):
+        assert list(a) == list(b) == list(RB.FIELDS)
+        for f in RB.FIELDS:
+            assert a[f].shape == b[f].shape and a[f].dtype == b[f].dtype == np.float32 and np.array_equal(a[f], b[f]), f
+    assert sum(len(a["returns"]) for a in mine) == rows
+    for k, inp in RB.rollout(T, n).items():                  # nothing was written
+        assert np.array_equal(out[k], inp)
+
+
+def test_index_convention_is_env_major():
+    T, n = 3, 5
+    out = RB.rollout(T, n)
+    g = RB.gather(out, np.arange(T * n))
+    for env in range(n):
+        for t in range(T):
+            i = env * T + t
+            assert np.array_equal(g["observations"][i], out["obs"][t, env]) and np.array_equal(g["actions"][i], out["buffer_actions"][t, env])
+            for f, k in zip(RB.FIELDS[2:], RB.KEYS[2:]):
+                assert g[f][i] == out[k][t, env]
+    assert not np.array_equal(g["returns"], out["returns"].reshape(-1))      # and NOT the [T][n] order (t * n + env)
+    assert [x.shape for x in g.values()] == [(15, 18), (15, 3), (15,), (15,), (15,), (15,)]
+
+
+def test_short_last_minibatch_and_none():
+    from reinforcementlearning4meshgeneration_amd import rollout_buffer as M
+    assert RB.bounds(259, 100) == M.minibatch_bounds(259, 100) == [(0, 100), (100, 200), (200, 259)]
+    assert RB.bounds(259, None) == M.minibatch_bounds(259, None) == [(0, 259)]
+    assert M.minibatch_bounds(1, 4) == [(0, 1)] and M.minibatch_bounds(8, 4) == [(0, 4), (4, 8)]
+    for rows in (1, 15, 259, 1056):
+        for b in RB.BATCH_SIZES:
+            assert RB.bounds(rows, b) == M.minibatch_bounds(rows, b)
+    mb = RB.get(RB.rollout(7, 37), np.arange(259)[::-1], 100)
+    assert [len(x["advantages"]) for x in mb] == [100, 100, 59] and mb[2]["observations"].shape == (59, 18)
+
+
+def test_an_index_that_is_no_row_gives_a_nan_row_and_reads_nothing():
+    T, n = 3, 5
+    out = RB.rollout(T, n)
+    perm = np.arange(15)
+    good = RB.gather(out, perm)
+    for bad in (15, -1, 2 ** 31 - 1, -2 ** 63, 2 ** 40):
+        p = perm.astype(np.int64)
+        p[4] = bad
+        g = RB.gather(out, p)
+        for f in RB.FIELDS:
+            assert np.isnan(g[f][4]).all() and np.array_equal(np.delete(g[f], 4, axis=0), np.delete(good[f], 4, axis=0)), (bad, f)
+    assert all(np.isfinite(x).all() for x in good.values())
+
+
+# ----------------------------------------------------------------------------------------------------------- the host half
+def _torch_out(T=3, n=5):
+    return {k: torch.from_numpy(v) for k, v in RB.rollout(T, n).items()}
+
+
+def _refused(fn, *words):
+    with pytest.raises(ValueError) as e:
+        fn()
+    for w in words:
+        assert w in str(e.value), (w, str(e.value))
+
+
+def test_check_rollout_accepts_the_six_fields_without_copying():
+    from reinforcementlearning4meshgeneration_amd import rollout_buffer as M
+    out = _torch_out()
+    out["reward"] = torch.zeros(3, 5, dtype=torch.float64)         # what else collect_rollout returns is ignored
+    T, n, tensors = M.check_rollout(out)
+    assert (T, n) == (3, 5) and all(x is out[k] for x, k in zip(tensors, RB.KEYS))
+    assert [k for k, _, _ in M.FIELDS] == list(RB.KEYS) and [f for _, _, f in M.FIELDS] == list(RB.FIELDS)
+    assert M.RolloutBufferSamples._fields == RB.FIELDS and M.RolloutBufferSamples.__name__ == "RolloutBufferSamples"
+    sliced = torch.zeros(4, 5, 18)[:3]                              # collect_rollout's obs is such a slice: contiguous
+    M.check_rollout(dict(out, obs=sliced))
+
+
+def test_load_refusals_name_what_was_found():
+    from reinforcementlearning4meshgeneration_amd import rollout_buffer as M
+    C = M.check_rollout
+    _refused(lambda: C([1, 2]), "dict", "list")
+    for k in RB.KEYS:
+        out = _torch_out()
+        del out[k]
+        _refused(lambda: C(out), repr(k))
+    out = _torch_out()
+    del out["advantages"], out["returns"]
+    _refused(lambda: C(out), "'advantages', 'returns'", "gamma")
+    _refused(lambda: C(dict(_torch_out(), obs=torch.zeros(3, 5, 17))), "'obs'", "(3, 5, 17)")
+    _refused(lambda: C(dict(_torch_out(), obs=torch.zeros(15, 18))), "'obs'", "(15, 18)")
+    _refused(lambda: C(dict(_torch_out(), obs=np.zeros((3, 5, 18), np.float32))), "'obs'", "ndarray")
+    _refused(lambda: C(dict(_torch_out(), obs=torch.zeros(0, 5, 18))), "'obs'", "(0, 5, 18)")
+    _refused(lambda: C(dict(_torch_out(), value=torch.zeros(3, 5, dtype=torch.float64))), "'value'", "float64")
+    _refused(lambda: C(dict(_torch_out(), obs=torch.zeros(3, 5, 18, dtype=torch.float16))), "'obs'", "float16")
+    _refused(lambda: C(dict(_torch_out(), log_prob=torch.zeros(5, 3))), "'log_prob'", "(5, 3)", "(3, 5)")
+    _refused(lambda: C(dict(_torch_out(), buffer_actions=torch.zeros(3, 5, 4))), "'buffer_actions'", "(3, 5, 4)", "(3, 5, 3)")
+    _refused(lambda: C(dict(_torch_out(), returns=torch.zeros(5, 3).t())), "'returns'", "not contiguous")
+    _refused(lambda: C(dict(_torch_out(), advantages=np.zeros((3, 5), np.float32))), "'advantages'", "ndarray")
+    _refused(lambda: C(dict(_torch_out(), advantages=torch.zeros(3, 5, device="meta"))), "'advantages'", "is on meta", "cpu")
+    _refused(lambda: C(_torch_out(), torch.device("cuda", 0)), "'obs'", "is on cpu", "cuda:0")
+    big = torch.zeros(1, device="meta").expand(2 ** 12, 2 ** 12, 18)
+    _refused(lambda: C(dict(_torch_out(), obs=big)), "16777216 rows", "2^24 - 16")
+
+
+def test_get_refusals_name_what_was_found():
+    from reinforcementlearning4meshgeneration_amd import rollout_buffer as M
+    for b in (0, -4, 2.0, "64", True):
+        _refused(lambda: M.minibatch_bounds(15, b), "batch_size", repr(b))
+    P = M.check_perm
+    ok = torch.arange(15)
+    assert P(ok, 15) is ok and P(ok.int(), 15).dtype == torch.int32          # taken as they are: no conversion
+    _refused(lambda: P(list(range(15)), 15), "tensor", "list")
+    _refused(lambda: P(np.arange(15), 15), "tensor", "ndarray")
+    _refused(lambda: P(ok.float(), 15), "float32", "int32 or int64")
+    _refused(lambda: P(ok.to(torch.int16), 15), "int16")
+    _refused(lambda: P(ok[:14], 15), "(14,)", "(15,)")
+    _refused(lambda: P(ok.reshape(3, 5), 15), "(3, 5)")
+    _refused(lambda: P(torch.arange(30)[::2], 15), "not contiguous")
+    for dtype in (torch.int64, torch.int32):
+        for j, bad in ((14, 15), (0, -1), (7, 2 ** 31 - 1)):
+            p = ok.to(dtype).clone()
+            p[j] = bad
+            P(p, 15)                                                            # unchecked by default: no read of the tensor
+            _refused(lambda: P(p, 15, check=True), f"perm[{j}] = {bad}", "0 <= index < 15")
+    P(ok.flip(0), 15, check=True)
+
+
+def test_get_before_load_and_no_cpu_fallback():
+    from reinforcementlearning4meshgeneration_amd import _capi
+    from reinforcementlearning4meshgeneration_amd import rollout_buffer as M
+    stub = types.SimpleNamespace(_in=None, _torch=torch)
+    _refused(lambda: M.DeviceRolloutBuffer.get(stub, 4), "before load()")
+    if not torch.cuda.is_available():
+        with pytest.raises(_capi.MeshEnvError):
+            M.DeviceRolloutBuffer()
+
+
+# ----------------------------------------------------------------------------------------------------------- packaging
+def test_exported_lazily_declared_and_built():
+    import os
+    import re
+
+    import reinforcementlearning4meshgeneration_amd as pkg
+    from reinforcementlearning4meshgeneration_amd import _capi, build
+    assert pkg.DeviceRolloutBuffer.__name__ == "DeviceRolloutBuffer" and pkg.RolloutBufferSamples._fields == RB.FIELDS
+    assert "DeviceRolloutBuffer" in pkg.__all__ and "RolloutBufferSamples" in pkg.__all__
+    names = _capi.EXPORTS_ROLLOUT
+    assert sorted(names) == sorted("meshenv_rollout_" + s for s in ("create", "destroy", "set_stream", "last_error", "gather"))
+    assert not set(names) & (set(_capi.EXPORTS) | set(_capi.EXPORTS_OPTIM) | set(_capi.EXPORTS_TD3_ACTOR_GRAD) | set(_capi.EXPORTS_PPO_GRAD))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "meshenv_rollout.h")).read()
+    assert sorted(set(re.findall(r"\b(meshenv_rollout_[a-z_]+)\s*\(", header))) == sorted(names)
+    assert f"#define MESHENV_ROLLOUT_MAX_ROWS {_capi.ROLLOUT_MAX_ROWS}" in header and _capi.ROLLOUT_MAX_ROWS == 2 ** 24 - 16
+    assert f"#define MESHENV_ROLLOUT_CHUNK {_capi.ROLLOUT_CHUNK}" in header and f"#define MESHENV_ROLLOUT_FIELDS {_capi.ROLLOUT_FIELDS}" in header
+    L = _capi.load()
+    for name in names:
+        assert hasattr(L, name), name
+    assert "meshenv_rollout.h" in build.PUBLIC_HEADERS
+    assert pkg.DeviceRolloutBuffer.PREFIX == "meshenv_rollout"
