@@ -22,9 +22,14 @@ PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h", "meshenv_td3_actor_grad.h", "m
 # -mllvm -amdgpu-atomic-optimizer-strategy=None: the LDS atomics of the observation scan (find_next_state) have one to
 # three active lanes; the optimiser's wave reduction in front of them is the very DPP sequence they replace
 # (headline 14.58 -> 14.42 us, 65 536 envs +1 %, rollout +2 %; tools/ab_all.sh).
+# -mllvm -amdgpu-kernarg-preload-count=16: leading plain kernel arguments (up to 14 dwords on gfx950) are in scalar registers
+# when a wave starts.  The CU-group step kernels take what their entry needs that way (EntryArgs, csrc/meshenv_kernels.h) and
+# request an environment's ring and record without a scalar round trip in front; the flag holds for the whole translation
+# unit, so every other kernel with leading pointer or integer arguments is preloaded as well.
 HIPCC_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
                "-fno-fast-math", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
-               "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
+               "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None",
+               "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
 def hipcc_path() -> str:

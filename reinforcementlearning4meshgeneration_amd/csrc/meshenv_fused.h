@@ -17,7 +17,7 @@
 namespace meshenv {
 
 struct GroupActorArgs {
-    GroupArgs g;             // FIRST: late_outs() reads the step's output pointers at GroupArgs' offsets of the kernarg segment
+    GroupArgs g;             // FIRST: late_outs() / late_state() read the step's pointers at GroupArgs' offsets of the argument block
     ActorWeights W;
     float *actions_next;     // [n][3]: the policy's actions for the next step (must not alias g.actions)
     float *eps_out;          // [n][3] exploration noise drawn, nullable
@@ -26,6 +26,8 @@ struct GroupActorArgs {
     int pad;
 };
 
+static_assert(alignof(GroupActorArgs) == 8, "follows the leading arguments (EntryArgs) without a gap, as GroupArgs does");
+
 __host__ __device__ __forceinline__ size_t group_actor_lds_bytes(int cap)
 {
     return group_lds_bytes(cap, 16) + sizeof(float) * kActorLdsFloats;
@@ -33,12 +35,14 @@ __host__ __device__ __forceinline__ size_t group_actor_lds_bytes(int cap)
 
 template <bool kDefaultParams, bool kSmall = false>
 __global__ void __launch_bounds__(64 * 16)
-k_step_group_actor(GroupActorArgs A)
+k_step_group_actor(MESHENV_ENTRY_PARAMS GroupActorArgs A)
 {
+    EntryArgs E;
+    MESHENV_ENTRY_PACK(E);
     extern __shared__ double2 smem[];
     float *lds = (float *)((char *)smem + group_lds_bytes(A.g.cap, 16));
     // every wave writes the observation its step ends with into the actor's input row as well (finish_and_store)
-    step_group_body<16, kDefaultParams, false, kSmall>(A.g, lds);   // (returns for every wave: nothing exits before the barrier)
+    step_group_body<16, kDefaultParams, false, kSmall>(E, A.g, lds);   // (returns for every wave: nothing exits before the barrier)
     ActorHead hd;
     actor_request_weights(hd, A.W, threadIdx.x, true);   // all three layers: in flight while the workgroup's slowest wave finishes
     __syncthreads();

@@ -496,7 +496,8 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
         if (!force && (G < 8 || n_envs > n_cu * G)) G = 1;  // LDS forced a smaller group: more than one workgroup per CU
         // Ragged packing: sixteen rings of the LONGEST stride do not fit, sixteen rings of their own lengths may (mixed
         // d1 / d2 / d3: 120 / 196 / 272 vertices -> 135 KB instead of 197 KB).  One workgroup per CU as in the uniform case.
-        if (G == 1 && want == 16 && n_envs <= n_cu * 16 && group_lds_bytes(cap, 16) > 150 * 1024) {
+        // (MESHENV_GROUP=16 asks for sixteen: the packing is tried before the batch settles for eight rings of the longest stride)
+        if ((G == 1 || (force && G < 16)) && want == 16 && n_envs <= n_cu * 16 && group_lds_bytes(cap, 16) > 150 * 1024) {
             std::vector<int2> pack((size_t)n_envs);
             size_t worst = 0;
             for (int w0 = 0; w0 < n_envs; w0 += 16) {
@@ -1312,11 +1313,11 @@ static int launch_step(MeshEnv *h, int n_steps, const float *actions_dev, float 
         A.env_lds = h->env_lds;
         A.ho_off = h->ho_off;
         A.pad = 0;
-        if (h->env_lds) hipLaunchKernelGGL((k_step_group<16, true, true>), grid, block, h->group_lds, h->stream, A);   // ragged: G == 16 only
-        else if (h->cap <= 64 && G == 16) hipLaunchKernelGGL((k_step_group<16, true, false, true>), grid, block, h->group_lds, h->stream, A);
-        else if (h->cap <= 64) hipLaunchKernelGGL((k_step_group<8, true, false, true>), grid, block, h->group_lds, h->stream, A);
-        else if (G == 16) hipLaunchKernelGGL((k_step_group<16, true>), grid, block, h->group_lds, h->stream, A);
-        else hipLaunchKernelGGL((k_step_group<8, true>), grid, block, h->group_lds, h->stream, A);
+        if (h->env_lds) hipLaunchKernelGGL((k_step_group<16, true, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);   // ragged: G == 16 only
+        else if (h->cap <= 64 && G == 16) hipLaunchKernelGGL((k_step_group<16, true, false, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
+        else if (h->cap <= 64) hipLaunchKernelGGL((k_step_group<8, true, false, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
+        else if (G == 16) hipLaunchKernelGGL((k_step_group<16, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
+        else hipLaunchKernelGGL((k_step_group<8, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
     } else {
         const dim3 grid(h->n_envs), block(64);
 #define MESHENV_LAUNCH_STEP(MULTI, DEF)                                                                                      \
@@ -1888,8 +1889,8 @@ int meshenv_step_actor(MeshEnv *h, MeshActor *a, const float *actions_dev, float
     GA.eps_out = eps_out_dev;
     GA.seed = seed; GA.counter = counter;
     GA.sample = sample ? 1 : 0; GA.pad = 0;
-    if (h->cap <= 64) hipLaunchKernelGGL((k_step_group_actor<true, true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, GA);
-    else hipLaunchKernelGGL((k_step_group_actor<true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, GA);
+    if (h->cap <= 64) hipLaunchKernelGGL((k_step_group_actor<true, true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, MESHENV_ENTRY_LAUNCH(GA.g) GA);
+    else hipLaunchKernelGGL((k_step_group_actor<true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, MESHENV_ENTRY_LAUNCH(GA.g) GA);
     HIP_TRY(h, hipGetLastError());
     h->steps_done += 1;
     return MESHENV_OK;

@@ -67,6 +67,7 @@ struct Ctx {
     double bl, area, ct, st;
     bool ring_dirty;
     bool tie = false;  // angles on a 1e-4 rounding boundary take glibc's atan2 (move() / smoothing kernels; geom.h, atan2_x_nc)
+    bool cold_global = false;  // the cold pointers are read as global ones (load_cold; the CU-group step kernels set it)
     // lane-private
     float obs;  // lanes 0..17: current observation
 };
@@ -89,6 +90,9 @@ __device__ __forceinline__ void wave_sync()
 
 // bounded spin on an LDS word another wavefront of the workgroup sets (all waves of a workgroup are co-resident, so the
 // setter always runs; the bound only keeps a logic error from hanging the GPU)
+// (The word is read and written through a generic volatile pointer: flat, system-scope accesses.  As LDS words at
+// workgroup scope -- ds_read_b32 / ds_write_b32 behind an lgkmcnt wait, the setter no longer draining vmcnt -- the
+// headline measured 0.04 us slower, at poll intervals of 1, 4 and 8 alike: DESIGN.md section 5.)
 __device__ __forceinline__ int spin_until_nonzero(volatile int *w)
 {
     int v = *w;
@@ -183,8 +187,9 @@ __device__ __forceinline__ EnvLoad load_env_issue(const DevState &S, int env, co
 
 // (lds_cap > 0: the ring slots this env's LDS region holds, when it is smaller than the HBM stride S.cap -- the CU-group
 // kernel packs the rings of mixed domains by their own lengths, see step_group_body; 0 = S.cap)
+// (small: the ring stride is at most 64 slots, so the ring is too -- no loop over slots >= 128)
 __device__ __forceinline__ void load_env_commit(Ctx &c, const DevState &S, int env, const EnvLoad &L, const bool with_keys = true,
-                                                const int lds_cap = 0)
+                                                const int lds_cap = 0, const bool small = false)
 {
     const int lane = lane_id();
     c.lane = lane;
@@ -205,6 +210,7 @@ __device__ __forceinline__ void load_env_commit(Ctx &c, const DevState &S, int e
     c.status = uniform_i32(s.status); c.dom = uniform_i32(s.dom);
     c.bl = uniform_f64(s.bl); c.area = uniform_f64(s.area); c.ct = uniform_f64(s.ct); c.st = uniform_f64(s.st);
     c.ring_dirty = false;
+    if (small) __builtin_assume(c.n <= 64 && c.n >= 0);
     if (lane < first) {
         c.xy[lane] = L.v_xy;
         c.id[lane] = L.v_id;
@@ -232,10 +238,11 @@ __device__ __forceinline__ void load_env_commit(Ctx &c, const DevState &S, int e
     wave_sync();
 }
 
-__device__ __forceinline__ void load_env(Ctx &c, const DevState &S, int env, const bool with_keys = true, const int lds_cap = 0)
+__device__ __forceinline__ void load_env(Ctx &c, const DevState &S, int env, const bool with_keys = true, const int lds_cap = 0,
+                                         const bool small = false)
 {
     const EnvLoad L = load_env_issue(S, env, with_keys);
-    load_env_commit(c, S, env, L, with_keys, lds_cap);
+    load_env_commit(c, S, env, L, with_keys, lds_cap, small);
 }
 
 // the candidate keys and stamps of a ring staged without them (load_env(.., false)), before an extraction
@@ -1030,14 +1037,14 @@ __device__ __forceinline__ void reset_from_domain(Ctx &c, const DevState &S)
             le.n_elem = c.n_elem;
             le.n_new = c.n_new;
             le.flags = (c.n <= 5 ? 1 : 0) | (c.status & kStLogOverflow);
-            LastEpisode *last_ep = load_cold(S).last_ep;
+            LastEpisode *last_ep = load_cold(S, c.cold_global).last_ep;
             le.episodes = last_ep[c.env].episodes + 1;
             last_ep[c.env] = le;
         }
         half ^= kStLogHalf;
     }
     const DomConst dc = S.dom[c.dom];
-    const DevCold cold = load_cold(S);
+    const DevCold cold = load_cold(S, c.cold_global);
     const int doff = uniform_i32(dc.off), n0 = uniform_i32(dc.n0);
     wave_sync();
     for (int i = c.lane; i < n0; i += 64) {
@@ -1064,7 +1071,7 @@ __device__ __forceinline__ void log_quad(Ctx &c, const DevState &S, int g0, int 
     const int cap = S.prm.log_cap;
     if (c.n_elem < cap) {
         if (c.lane == 0) {
-            int32_t *dst = load_cold(S).log_quads + (((size_t)c.env * 2 + ((c.status >> 4) & 1)) * cap + c.n_elem) * 4;
+            int32_t *dst = load_cold(S, c.cold_global).log_quads + (((size_t)c.env * 2 + ((c.status >> 4) & 1)) * cap + c.n_elem) * 4;
             dst[0] = g0; dst[1] = g1; dst[2] = g2; dst[3] = g3;
         }
     } else if (cap > 0) {
@@ -1400,7 +1407,7 @@ __device__ __forceinline__ void env_apply(Ctx &c, const DevState &S, Decision &d
             c.id[index] = kNewBit | c.n_new;
             c.stamp[index] = kNotCand;
             const int cap = prm.log_cap;
-            if (c.n_new < cap) load_cold(S).log_vxy[((size_t)c.env * 2 + ((c.status >> 4) & 1)) * cap + c.n_new] = make_double2(d.new_point.x, d.new_point.y);
+            if (c.n_new < cap) load_cold(S, c.cold_global).log_vxy[((size_t)c.env * 2 + ((c.status >> 4) & 1)) * cap + c.n_new] = make_double2(d.new_point.x, d.new_point.y);
         }
         if (prm.log_cap > 0 && c.n_new >= prm.log_cap) c.status |= kStLogOverflow;
         c.n_new += 1;
@@ -2072,7 +2079,8 @@ struct StepOuts {
     float *term_obs;
 };
 
-// the single by-value argument of k_step_group: its layout IS the kernel-argument segment
+// the by-value argument block of k_step_group, behind the preloaded leading arguments (EntryArgs below): its layout IS the
+// kernel-argument segment from byte kEntryBytes on
 struct GroupArgs {
     DevState S;
     StepOuts outs;
@@ -2088,38 +2096,87 @@ struct GroupArgs {
     int pad;
 };
 
+// What the entry of a CU-group step needs before it can request an environment's state, as LEADING PLAIN ARGUMENTS of the
+// kernel, in front of its argument block: fourteen dwords, the most the hardware preloads into scalar registers before
+// the first instruction (-mllvm -amdgpu-kernarg-preload-count=16 in the build flags; a by-value struct is not preloaded).
+// With them the ring and the record are requested with no scalar round trip in front.  They repeat GroupArgs::S and
+// GroupArgs::actions; the block behind them keeps its layout, shifted by kEntryBytes in the kernel-argument segment
+// (late_outs, late_state, late_step0).
+struct EntryArgs {
+    double2 *ring_xy;
+    int32_t *ring_id;
+    double *ring_key;
+    int32_t *ring_stamp;
+    EnvScalars *scal;
+    const float *actions;
+    int n_envs, cap;   // cap: the ring stride of the state arrays (DevState::cap)
+};
+constexpr unsigned kEntryBytes = sizeof(EntryArgs);
+static_assert(sizeof(EntryArgs) == 14 * 4, "fourteen dwords: the preload limit");
+#define MESHENV_ENTRY_PARAMS double2 *e_ring_xy, int32_t *e_ring_id, double *e_ring_key, int32_t *e_ring_stamp, EnvScalars *e_scal, \
+                             const float *e_actions, int e_n_envs, int e_cap,
+#define MESHENV_ENTRY_PACK(E)                                                                                            \
+    E.ring_xy = e_ring_xy; E.ring_id = e_ring_id; E.ring_key = e_ring_key; E.ring_stamp = e_ring_stamp; E.scal = e_scal; \
+    E.actions = e_actions; E.n_envs = e_n_envs; E.cap = e_cap
+// host side: the leading arguments of a launch, from the GroupArgs that follows them
+#define MESHENV_ENTRY_LAUNCH(A) (A).S.ring_xy, (A).S.ring_id, (A).S.ring_key, (A).S.ring_stamp, (A).S.scal, (A).actions, (A).S.n_envs, (A).S.cap,
+
+// (the pointers come back as global ones -- as_global, csrc/meshenv_state.h: the opaque copy of the segment pointer hides
+// that they are kernel arguments, and the results would be written with flat_store)
 __device__ __forceinline__ StepOuts late_outs()
 {
     typedef const __attribute__((address_space(4))) char *kptr;
     kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));  // not before this point
     typedef const __attribute__((address_space(4))) unsigned long long *qptr;
-    qptr q = (qptr)(ka + offsetof(GroupArgs, outs));
+    qptr q = (qptr)(ka + kEntryBytes + offsetof(GroupArgs, outs));
     static_assert(sizeof(StepOuts) == 5 * sizeof(unsigned long long), "StepOuts is five pointers");
     StepOuts o;
-    o.obs_out = (float *)q[0];
-    o.reward = (double *)q[1];
-    o.done = (uint8_t *)q[2];
-    o.complete = (uint8_t *)q[3];
-    o.term_obs = (float *)q[4];
+    o.obs_out = as_global((float *)q[0]);
+    o.reward = as_global((double *)q[1]);
+    o.done = as_global((uint8_t *)q[2]);
+    o.complete = as_global((uint8_t *)q[3]);
+    o.term_obs = as_global((float *)q[4]);   // (nullable: null stays null)
     return o;
+}
+
+// GroupArgs::step0, read where the work counters are updated and nowhere else: as an ordinary argument it is fetched at
+// the kernel's entry and occupies two scalar registers from the first to the last instruction.
+__device__ __forceinline__ unsigned long long late_step0()
+{
+    typedef const __attribute__((address_space(4))) char *kptr;
+    kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));  // not before this point
+    return *(const __attribute__((address_space(4))) unsigned long long *)(ka + kEntryBytes + offsetof(GroupArgs, step0));
 }
 
 // The DevState at the head of the kernel-argument segment (GroupArgs and every argument block built on it), read again behind
 // an opaque copy of the segment pointer: the write-back of a step needs the ring arrays, the record and counter arrays and
 // the domain table, none of which the checks or the update in between touch -- re-reading them costs two scalar loads,
 // holding them costs scalar registers (or VGPR lanes) on every path.  prm comes from the caller's copy (literals).
+// Every pointer is handed back as a global one (as_global): the write-back -- finish_and_store, store_env, store_ring,
+// reset_from_domain -- issues global_store / global_load, not flat_*.
 __device__ __forceinline__ DevState late_state(const DevState &S)
 {
     typedef const __attribute__((address_space(4))) unsigned long long *qptr;
     qptr q = (qptr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(q));   // not before this point
+    static_assert(kEntryBytes % 8 == 0 && alignof(GroupArgs) == 8, "the argument block follows the leading arguments without a gap");
+    q += kEntryBytes / 8;
     constexpr unsigned kWords = offsetof(DevState, prm) / 8;
     static_assert(offsetof(DevState, prm) % 8 == 0, "whole quadwords before prm");
     union { DevState s; unsigned long long w[sizeof(DevState) / 8]; } u;
     u.s = S;
 #pragma unroll
     for (unsigned i = 0; i < kWords; i++) u.w[i] = q[i];
+    u.s.dom = as_global(u.s.dom); u.s.cold = as_global(u.s.cold);
+    u.s.ring_xy = as_global(u.s.ring_xy); u.s.ring_id = as_global(u.s.ring_id);
+    u.s.ring_key = as_global(u.s.ring_key); u.s.ring_stamp = as_global(u.s.ring_stamp);
+    u.s.scal = as_global(u.s.scal); u.s.cnt = as_global(u.s.cnt);
+    u.s.obs_cache = as_global(u.s.obs_cache); u.s.msg = as_global(u.s.msg);   // (msg is nullable: null stays null)
+#ifdef MESHENV_STAMPS
+    u.s.dbg = as_global(u.s.dbg);
+#endif
     return u.s;
 }
 
@@ -2127,7 +2184,7 @@ __device__ __forceinline__ DevState late_state(const DevState &S)
 // (helper_done != nullptr: the reward of this valid step is written by a helper wavefront, which also reads the ring:
 // an auto-reset waits for it before it overwrites the ring)
 __device__ __forceinline__ void finish_and_store(Ctx &c, const DevState &S_in, const Decision &d, const EnvCounters &cnt0,
-                                                 int n_before, int auto_reset, unsigned long long step0,
+                                                 int n_before, int auto_reset,
                                                  volatile int *helper_done = nullptr, float *actor_row = nullptr,
                                                  const bool cnt_late = false)
 {
@@ -2169,6 +2226,7 @@ __device__ __forceinline__ void finish_and_store(Ctx &c, const DevState &S_in, c
         // (cnt_late: a rejected step of the CU-group kernel -- its counters only move when the episode is truncated, so
         // they are read here instead of being held, unused, through the checks of every wave)
         EnvCounters k = cnt_late ? S.cnt[env] : cnt0;
+        const unsigned long long step0 = late_step0();
         k.sum_n += (unsigned long long)n_before * (step0 + 1ULL - k.last_change);
         k.last_change = step0 + 1ULL;
         if (r.valid) { k.valid += 1ULL; k.sum_n_valid += (unsigned long long)n_before; }
@@ -2192,14 +2250,18 @@ __device__ __forceinline__ void finish_and_store(Ctx &c, const DevState &S_in, c
 // (kSmall: the batch's ring stride is at most 64 slots, so every ring fits one 64-lane pass: the compiler is told n <= 64 and
 // drops the chunk loops of every ring pass and the multi-chunk forms behind them -- 8864 -> 7621 static instructions)
 template <int G, bool kDefaultParams, bool kRagged = false, bool kSmall = false>
-__device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor_in = nullptr)
+__device__ __forceinline__ void step_group_body(const EntryArgs &E, const GroupArgs &A, float *actor_in = nullptr)
 {
     const int tid = (int)threadIdx.x;
     extern __shared__ double2 smem[];
     DevState S = A.S;
-    const int cap = A.cap, auto_reset = A.auto_reset;
+    // the preloaded copies: what the entry computes its first addresses from is in scalar registers when the wave starts
+    S.ring_xy = E.ring_xy; S.ring_id = E.ring_id; S.ring_key = E.ring_key; S.ring_stamp = E.ring_stamp; S.scal = E.scal;
+    S.n_envs = E.n_envs; S.cap = E.cap;
+    const float *__restrict__ actions = E.actions;
+    const int cap = E.cap;   // (GroupArgs::cap is the same number: the LDS regions are carved by the stride of the state arrays)
+    const int auto_reset = A.auto_reset;
     if (kSmall) __builtin_assume(cap <= 64 && S.cap <= 64 && cap > 0 && S.cap > 0);   // no second chunk in the loads either
-    const float *__restrict__ actions = A.actions;
     if (kDefaultParams) apply_default_params(S.prm);
     const int wave = uniform_i32(tid >> 6);  // wave-uniform by construction: keeps env and every address derived from it in SGPRs
     const size_t env_bytes = lds_bytes_for(cap);
@@ -2214,6 +2276,7 @@ __device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor
 #endif
     if (active) {
         Ctx c;
+        c.cold_global = true;
         int my_off = (int)((size_t)wave * env_bytes), my_cap = cap;
         if (kRagged) {   // wave-uniform: one scalar load, requested with the state
             const int2 e = A.env_lds[env];
@@ -2226,12 +2289,20 @@ __device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor
         EnvCounters cnt0;
         cnt0.last_change = 0; cnt0.valid = 0; cnt0.sum_n = 0; cnt0.sum_n_valid = 0;
         constexpr bool kCntLate = true;
-        load_env(c, S, env, true, kRagged ? my_cap : 0);
+        EnvLoad L = load_env_issue(S, env, true);
+        // All three action floats travel with the record: the ring length that everything below starts from comes out of
+        // an asm that reads them, so they are requested in the burst of the record and the ring.  (The third one was
+        // requested behind the wait for the ring and waited for at once; actions are 12 bytes per env, so for one wave in
+        // five it lies on another 64-byte line than the first two -- a scalar-cache miss, fully exposed.)  The asm is not
+        // volatile and touches no memory: a volatile one in front of the record's use counts as a possible store, and the
+        // wave-uniform record is then fetched with vector loads (docs/DESIGN_rounds_1-3.md, section 5).
+        asm("" : "+s"(L.s.n) : "s"(a0), "s"(a1), "s"(a2));
+        load_env_commit(c, S, env, L, true, kRagged ? my_cap : 0, kSmall);
         if (kSmall) __builtin_assume(c.n <= 64 && c.n >= 0);
         const int n_before = c.n;
         Decision d = env_check(c, S, a0, a1, a2, false, false, 0.0, 0.0, 0.5, true);
         if (!d.ok) {
-            finish_and_store(c, S, d, cnt0, n_before, auto_reset, A.step0, nullptr, actor_in ? actor_in + wave * 132 : nullptr, kCntLate);
+            finish_and_store(c, S, d, cnt0, n_before, auto_reset, nullptr, actor_in ? actor_in + wave * 132 : nullptr, kCntLate);
         } else {
             pending = 1;
             if (c.lane == 0) {
@@ -2329,6 +2400,7 @@ __device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor
     if (hsrc >= 0) {
         // ---- phase 2, helper: the reward of env ho[hsrc]
         Ctx c;
+        c.cold_global = true;
         Handoff &h = ho[hsrc];
         if (kRagged) carve_lds(c, (char *)smem + uniform_i32(h.lds_off), uniform_i32(h.lds_cap));
         else carve_lds(c, (char *)smem + (size_t)hsrc * env_bytes, cap);
@@ -2339,22 +2411,24 @@ __device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor
         const int henv = uniform_i32(h.env);
         const double rew = reward_on_helper(c, S, d, uniform_i32(h.n), uniform_i32(h.dom), &h.upd_done);
         wave_sync();
+        const DevState SL = late_state(S);   // (msg too: read at the entry it is one more kernel-argument load every wave waits for)
         if (c.n > 5) {  // not the end of the episode: the ring is final, write it back here (off the update wave's path)
             c.env = henv;
             c.base = (size_t)henv * S.cap;
-            store_ring(c, late_state(S));
+            store_ring(c, SL);
         }
         if (c.lane == 0) {
             *(volatile int *)&h.helper_done = 1;
             const StepOuts o = late_outs();
             o.reward[henv] = rew;
-            if (S.msg) S.msg[(size_t)henv * 21 + 18] = (float)rew;
+            if (SL.msg) SL.msg[(size_t)henv * 21 + 18] = (float)rew;
         }
         return;
     }
 
     // ---- phase 2: the update of env ho[src], in place in its LDS region
     Ctx c;
+    c.cold_global = true;
     Handoff &h = ho[src];
     if (kRagged) carve_lds(c, (char *)smem + uniform_i32(h.lds_off), uniform_i32(h.lds_cap));
     else carve_lds(c, (char *)smem + (size_t)src * env_bytes, cap);
@@ -2379,7 +2453,7 @@ __device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor
 #ifdef MESHENV_STAMPS
     const unsigned long long dbg_t8 = __builtin_amdgcn_s_memrealtime();
 #endif
-    finish_and_store(c, S, d, cnt0, n_before, auto_reset, A.step0, helpers ? &h.helper_done : nullptr,
+    finish_and_store(c, S, d, cnt0, n_before, auto_reset, helpers ? &h.helper_done : nullptr,
                      actor_in ? actor_in + src * 132 : nullptr);
 #ifdef MESHENV_STAMPS
     if (c.lane == 0) {
@@ -2399,9 +2473,11 @@ __device__ __forceinline__ void step_group_body(const GroupArgs &A, float *actor
 
 template <int G, bool kDefaultParams, bool kRagged = false, bool kSmall = false>
 __global__ void __launch_bounds__(64 * G)
-k_step_group(GroupArgs A)
+k_step_group(MESHENV_ENTRY_PARAMS GroupArgs A)
 {
-    step_group_body<G, kDefaultParams, kRagged, kSmall>(A);
+    EntryArgs E;
+    MESHENV_ENTRY_PACK(E);
+    step_group_body<G, kDefaultParams, kRagged, kSmall>(E, A);
 }
 
 }  // namespace meshenv

@@ -120,13 +120,32 @@ struct DevState {
     Params prm;
 };
 
+// A pointer the compiler has lost the address space of (it went through an opaque register copy, or was loaded from
+// memory) as what it is: device memory.  Rebuilt from its integer value as a global pointer, it is accessed with
+// global_load / global_store; a generic one costs flat_* instructions, which also occupy the LDS path and tick both
+// wait counters.  (A plain generic -> global -> generic cast is folded away; the integer in between is not.)
+template <class T>
+__device__ __forceinline__ T *as_global(T *p)
+{
+    return (T *)(__attribute__((address_space(1))) T *)(unsigned long long)p;
+}
+
 // The cold pointers, loaded at the point of use (the empty asm keeps the compiler from hoisting the loads into the
 // kernel prologue, where they would occupy scalar registers on every path).
-__device__ __forceinline__ DevCold load_cold(const DevState &S)
+// (global: the block and everything it points to are device allocations, said so again behind the asm -- as_global; a
+// compile-time constant per call.  The CU-group step kernels pass it: their reset path then reads the domain with
+// global_load, not flat_load.  The one-wave k_step does not: with it, 65 536 x boundary() measured 58.5 against 57.7 us
+// per step -- the wave-uniform block then arrives through the scalar cache)
+__device__ __forceinline__ DevCold load_cold(const DevState &S, const bool global = false)
 {
     const DevCold *p = S.cold;
     asm volatile("" : "+s"(p));
-    return *p;
+    if (!global) return *p;
+    DevCold c = *as_global(p);
+    c.dom_xy = as_global(c.dom_xy); c.dom_key = as_global(c.dom_key); c.dom_stamp = as_global(c.dom_stamp);
+    c.dom_obs = as_global(c.dom_obs); c.log_quads = as_global(c.log_quads); c.log_vxy = as_global(c.log_vxy);
+    c.last_ep = as_global(c.last_ep);
+    return c;
 }
 
 }  // namespace meshenv
