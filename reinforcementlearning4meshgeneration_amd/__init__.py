@@ -9,7 +9,8 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "random_domain", "MeshEnvError", "FusedActor", "FusedPolicy", "EvalResult", "evaluate_policy",
            "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
            "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
-           "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples"]
+           "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
+           "TrainLogs"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -58,4 +59,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("DeviceRolloutBuffer", "RolloutBufferSamples"):
         from . import rollout_buffer
         return getattr(rollout_buffer, name)
+    if name in ("FusedOnPolicyTrain", "OnPolicyTrainSpec", "TrainLogs"):
+        from . import onpolicy_train
+        return getattr(onpolicy_train, name)
     raise AttributeError(name)

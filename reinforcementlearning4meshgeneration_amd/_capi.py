@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -98,6 +98,13 @@ EXPORTS_ROLLOUT = [
     "meshenv_rollout_gather",
 ]
 ROLLOUT_FIELDS, ROLLOUT_CHUNK, ROLLOUT_MAX_ROWS = 6, 1024, 2 ** 24 - 16
+
+# every symbol include/meshenv_onpolicy_train.h declares: PPO.train / A2C.train as one call
+EXPORTS_ONPOLICY_TRAIN = [
+    "meshenv_onpolicy_train_create", "meshenv_onpolicy_train_destroy", "meshenv_onpolicy_train_set_stream",
+    "meshenv_onpolicy_train_last_error", "meshenv_onpolicy_train_run",
+]
+TRAIN_OUTPUTS, TRAIN_MAX_MINIBATCHES = 12, 65536
 
 
 class MeshOptimScalars(C.Structure):
@@ -203,7 +210,8 @@ def load():
                                           ("meshenv_target", [C.c_int, f32, f32, f32, f32], True),
                                           ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
                                           ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True),
-                                          ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True)):
+                                          ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True),
+                                          ("meshenv_onpolicy_train", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -248,12 +256,15 @@ def load():
     L.meshenv_optim_bind.argtypes = [vp, C.c_int, C.c_int] + [C.POINTER(vp)] * 5 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 3
     L.meshenv_optim_step.argtypes = [vp, C.c_int, C.POINTER(MeshOptimScalars)]
     L.meshenv_rollout_gather.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int]
+    L.meshenv_onpolicy_train_run.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_double, f32, f32, C.c_int, C.c_int, f32, C.c_double,
+                                             C.POINTER(MeshOptimScalars), C.c_int, vp]
     for name in ("meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
                  "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",
                  "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample", "meshenv_td3_actor_grad_bind",
                  "meshenv_td3_actor_grad_backward", "meshenv_ppo_grad_bind", "meshenv_ppo_grad_backward", "meshenv_policy_bind",
-                 "meshenv_policy_refresh", "meshenv_rollout_gather"):
+                 "meshenv_policy_refresh", "meshenv_rollout_gather", "meshenv_onpolicy_train_run"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_reset_static", "meshenv_move", "meshenv_get_not_valid", "meshenv_set_stream", "meshenv_num_envs", "meshenv_max_ring", "meshenv_reset", "meshenv_step",
                  "meshenv_rollout", "meshenv_get_status", "meshenv_get_state", "meshenv_get_elements",

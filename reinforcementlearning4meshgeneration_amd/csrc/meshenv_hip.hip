@@ -8,6 +8,7 @@
 #include "../../include/meshenv_td3_actor_grad.h"
 #include "../../include/meshenv_ppo_grad.h"
 #include "../../include/meshenv_rollout.h"
+#include "../../include/meshenv_onpolicy_train.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -38,6 +39,7 @@
 #include "meshenv_ppo_grad.h"
 #include "meshenv_optim.h"
 #include "meshenv_rollout.h"
+#include "meshenv_onpolicy_train.h"
 
 using namespace meshenv;
 
@@ -3187,6 +3189,39 @@ struct MeshOptim : HandleBase {
     OptProgram prog[MESHENV_OPTIM_PROGRAMS];
 };
 
+namespace {
+
+// The launch of a bound program: k_optim_step, or with a gate (meshenv_onpolicy_train_run) k_optim_step_gated over the same
+// tables.
+int optim_step_launch(MeshOptim *o, int program, const MeshOptimScalars *scalars, const TrainGate *gate, const char *fn)
+{
+    if (!o) return MESHENV_E_ARG;
+    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || !scalars)
+        return fail(o, MESHENV_E_ARG, std::string(fn) + ": program out of range or no scalars");
+    OptProgram &P = o->prog[program];
+    if (!P.bound) return fail(o, MESHENV_E_STATE, std::string(fn) + ": program " + std::to_string(program) + " is not bound (meshenv_optim_bind)");
+    DeviceGuard guard(o->device);
+    if (guard.err != hipSuccess) return fail(o, MESHENV_E_HIP, std::string(fn) + ": hipSetDevice failed");
+    if (P.ordered != o->stream) {           // the tables were uploaded on another stream: order this one after the upload
+        if (hipStreamWaitEvent(o->stream, P.copied, 0) != hipSuccess)
+            return fail(o, MESHENV_E_HIP, std::string(fn) + ": hipStreamWaitEvent failed");
+        P.ordered = o->stream;
+    }
+    o->last_stream = o->stream;
+    OptScalars S;
+    std::memcpy(&S, scalars, sizeof(S));
+    return launch(o, guard, fn, [&] {
+        if (gate)
+            hipLaunchKernelGGL(k_optim_step_gated, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
+                               (const OptJob *)(P.dev + P.jobs_at), S, *gate);
+        else
+            hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
+                               (const OptJob *)(P.dev + P.jobs_at), S);
+    });
+}
+
+}  // namespace
+
 extern "C" {
 
 int meshenv_optim_create(int device, void *stream, MeshOptim **out)
@@ -3285,25 +3320,7 @@ int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param
 
 int meshenv_optim_step(MeshOptim *o, int program, const MeshOptimScalars *scalars)
 {
-    if (!o) return MESHENV_E_ARG;
-    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || !scalars)
-        return fail(o, MESHENV_E_ARG, "meshenv_optim_step: program out of range or no scalars");
-    OptProgram &P = o->prog[program];
-    if (!P.bound) return fail(o, MESHENV_E_STATE, "meshenv_optim_step: program " + std::to_string(program) + " is not bound (meshenv_optim_bind)");
-    DeviceGuard guard(o->device);
-    if (guard.err != hipSuccess) return fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipSetDevice failed");
-    if (P.ordered != o->stream) {           // the tables were uploaded on another stream: order this one after the upload
-        if (hipStreamWaitEvent(o->stream, P.copied, 0) != hipSuccess)
-            return fail(o, MESHENV_E_HIP, "meshenv_optim_step: hipStreamWaitEvent failed");
-        P.ordered = o->stream;
-    }
-    o->last_stream = o->stream;
-    OptScalars S;
-    std::memcpy(&S, scalars, sizeof(S));
-    return launch(o, guard, "meshenv_optim_step", [&] {
-        hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
-                           (const OptJob *)(P.dev + P.jobs_at), S);
-    });
+    return optim_step_launch(o, program, scalars, nullptr, "meshenv_optim_step");
 }
 
 }  // extern "C"
@@ -3373,6 +3390,113 @@ int meshenv_rollout_gather(MeshRolloutBuffer *r, int T, int n_envs, const void *
         if (variant == 1) hipLaunchKernelGGL(k_rollout_gather<true>, dim3(grid), dim3(kRgThreads), 0, r->stream, A);
         else hipLaunchKernelGGL(k_rollout_gather<false>, dim3(grid), dim3(kRgThreads), 0, r->stream, A);
     });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ PPO.train / A2C.train in one call
+static_assert(MESHENV_TRAIN_OUTPUTS == kTrOut, "include/meshenv_onpolicy_train.h and csrc/meshenv_onpolicy_train.h disagree");
+
+struct MeshOnPolicyTrain : HandleBase {
+    float *buf = nullptr;       // the tally (kTlWords doubles, padded to 16), stop[K_max + 1] (padded), the kPgOut outputs of K_max minibatches
+};
+
+namespace {
+
+constexpr size_t kTrTallyFloats = 32, kTrStopFloats = MESHENV_TRAIN_MAX_MINIBATCHES + 16;
+static_assert(kTlWords * 2 <= kTrTallyFloats, "the tally fits its block");
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_onpolicy_train_create(int device, void *stream, MeshOnPolicyTrain **out)
+{
+    const int rc = create_handle("meshenv_onpolicy_train_create", device, stream, out);
+    if (rc != MESHENV_OK) return rc;
+    MeshOnPolicyTrain *t = *out;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess ||
+        !zeroed_once(t, &t->buf, kTrTallyFloats + kTrStopFloats + (size_t)MESHENV_TRAIN_MAX_MINIBATCHES * kPgOut)) {
+        g_create_error = "meshenv_onpolicy_train_create: allocation failed";
+        if (t->buf) (void)hipFree(t->buf);
+        delete t;
+        *out = nullptr;
+        return MESHENV_E_HIP;
+    }
+    return MESHENV_OK;
+}
+
+void meshenv_onpolicy_train_destroy(MeshOnPolicyTrain *t) { destroy_handle(t, t ? t->buf : nullptr); }
+
+const char *meshenv_onpolicy_train_last_error(const MeshOnPolicyTrain *t) { return last_error(t); }
+
+int meshenv_onpolicy_train_set_stream(MeshOnPolicyTrain *t, void *stream) { return set_stream(t, stream); }
+
+int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *o, int program, MeshRolloutBuffer *r,
+                               MeshPolicy *policy, int T, int n_envs, const float *const *in_dev, float *const *gather_dev,
+                               const void *perm_dev, int perm_bytes, int n_epochs, int batch_size, int a2c, double clip_range,
+                               float ent_coef, float vf_coef, int normalize_advantage, int clip_grad, float max_grad_norm,
+                               double target_kl, const MeshOptimScalars *scalars, int n_scalars, double *out_dev)
+{
+    if (!t) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_onpolicy_train_run";
+    if (!g || !o || !r) return fail(t, MESHENV_E_ARG, fn + ": the gradient, optimiser and rollout-buffer handles are required");
+    if (g->device != t->device || o->device != t->device || r->device != t->device || (policy && policy->device != t->device))
+        return fail(t, MESHENV_E_ARG, fn + ": the handles are on different devices");
+    if (!g->bound) return fail(t, MESHENV_E_STATE, fn + ": the gradient handle has no tensors bound (meshenv_ppo_grad_bind)");
+    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS) return fail(t, MESHENV_E_ARG, fn + ": program out of range");
+    if (!o->prog[program].bound) return fail(t, MESHENV_E_STATE, fn + ": the optimiser's program is not bound (meshenv_optim_bind)");
+    if (policy && (!policy->loaded || !policy->live))
+        return fail(t, MESHENV_E_STATE, fn + ": the policy has no tensors bound (meshenv_policy_bind)");
+    if (g->stream != t->stream || o->stream != t->stream || r->stream != t->stream || (policy && policy->stream != t->stream))
+        return fail(t, MESHENV_E_STATE, fn + ": the handles are on different streams (set_stream them to one)");
+    if (n_epochs < 1 || batch_size < 1) return fail(t, MESHENV_E_ARG, fn + ": n_epochs >= 1 and batch_size >= 1 are required");
+    if (!(target_kl >= 0.0)) return fail(t, MESHENV_E_ARG, fn + ": target_kl must be >= 0 (+inf: none), not negative or NaN");
+    if (T < 1 || n_envs < 1 || (long long)T * n_envs > MESHENV_ROLLOUT_MAX_ROWS)
+        return fail(t, MESHENV_E_ARG, fn + ": T >= 1, n_envs >= 1 and T * n_envs <= 2^24 - 16 are required");
+    if (!in_dev || !gather_dev || !perm_dev || !scalars || !out_dev || ((uintptr_t)out_dev & 7))
+        return fail(t, MESHENV_E_ARG, fn + ": in_dev, gather_dev, perm_dev, scalars and an 8-byte aligned out_dev are required");
+    if (perm_bytes != 4 && perm_bytes != 8) return fail(t, MESHENV_E_ARG, fn + ": perm_bytes is 4 (int32) or 8 (int64)");
+    const int rows = T * n_envs;
+    const int per_epoch = (rows + batch_size - 1) / batch_size;
+    const long long K = (long long)n_epochs * per_epoch;
+    if (K > MESHENV_TRAIN_MAX_MINIBATCHES)
+        return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(K) + " minibatches; at most " + std::to_string(MESHENV_TRAIN_MAX_MINIBATCHES));
+    if (n_scalars != K) return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(n_scalars) + " scalar sets for " + std::to_string(K) + " minibatches");
+    for (int f = 0; f < MESHENV_ROLLOUT_FIELDS; f++)
+        if (!in_dev[f] || !gather_dev[f]) return fail(t, MESHENV_E_ARG, fn + ": null pointer for field " + std::to_string(f));
+    double *tally = reinterpret_cast<double *>(t->buf);
+    int32_t *stop = reinterpret_cast<int32_t *>(t->buf + kTrTallyFloats);
+    float *pg_out = t->buf + kTrTallyFloats + kTrStopFloats;
+    const float *obs = gather_dev[0], *act = gather_dev[1], *old = gather_dev[3], *adv = gather_dev[4], *ret = gather_dev[5];
+    int m = 0;
+    for (int e = 0; e < n_epochs; e++) {
+        const char *perm = (const char *)perm_dev + (size_t)e * rows * perm_bytes;
+        int rc = meshenv_rollout_gather(r, T, n_envs, perm, perm_bytes, in_dev, gather_dev, 0);
+        if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + r->err);
+        for (int k = 0; k < per_epoch; k++, m++) {
+            const int a = k * batch_size, n = rows - a < batch_size ? rows - a : batch_size;
+            float *out_m = pg_out + (size_t)m * kPgOut;
+            rc = meshenv_ppo_grad_backward(g, n, obs + (size_t)a * kRgObs, act + (size_t)a * kRgAct, a2c ? nullptr : old + a, adv + a, ret + a,
+                                           a2c, clip_range, ent_coef, vf_coef, normalize_advantage, clip_grad, max_grad_norm, out_m,
+                                           nullptr, nullptr);
+            if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + g->err);
+            TrainGate G{};
+            G.stop = stop + m; G.pg_out = out_m; G.tally = tally; G.kl_limit = 1.5 * target_kl;
+            G.first_of_epoch = k == 0; G.first_of_train = m == 0;
+            rc = optim_step_launch(o, program, scalars + m, &G, "meshenv_onpolicy_train_run");
+            if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + o->err);
+        }
+    }
+    DeviceGuard guard(t->device);
+    int rc = launch(t, guard, "meshenv_onpolicy_train_run", [&] {
+        hipLaunchKernelGGL(k_train_finish, dim3(1), dim3(kTrFinishThreads), 0, t->stream, in_dev[2], in_dev[5], rows, g->log_std,
+                           (const double *)tally, out_dev);
+    }, "finish launch");
+    if (rc != MESHENV_OK || !policy) return rc;
+    rc = meshenv_policy_refresh(policy);
+    return rc == MESHENV_OK ? rc : fail(t, rc, fn + ": " + policy->err);
 }
 
 }  // extern "C"

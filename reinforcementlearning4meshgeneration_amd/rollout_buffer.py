@@ -146,11 +146,16 @@ class DeviceRolloutBuffer(Handle):
             perm = check_perm(perm, rows, check)
             if perm.device != self.device:
                 perm = perm.to(self.device)
+        o = self._outputs()
+        self._gather(perm, 0)
+        return (RolloutBufferSamples(*[x[a:b] for x in o]) for a, b in bounds)
+
+    def _outputs(self) -> list:
+        """The six output buffers for the loaded rollout: allocated at the first use for a given number of rows."""
+        t, rows = self._torch, self.rows
         if self._out is None or self._out[0].shape[0] != rows:
             self._out = [t.empty((rows,) + tail, dtype=t.float32, device=self.device) for _, tail, _ in FIELDS]
-        self._gather(perm, 0)
-        o = self._out
-        return (RolloutBufferSamples(*[x[a:b] for x in o]) for a, b in bounds)
+        return self._out
 
     def _gather(self, perm, variant: int) -> None:
         self._bind_stream()
