@@ -10,7 +10,7 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
            "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
            "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
-           "TrainLogs"]
+           "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -62,4 +62,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedOnPolicyTrain", "OnPolicyTrainSpec", "TrainLogs"):
         from . import onpolicy_train
         return getattr(onpolicy_train, name)
+    if name in ("FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs"):
+        from . import offpolicy_train
+        return getattr(offpolicy_train, name)
     raise AttributeError(name)

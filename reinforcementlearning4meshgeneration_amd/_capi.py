@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_offpolicy_train.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -106,6 +106,14 @@ EXPORTS_ONPOLICY_TRAIN = [
 ]
 TRAIN_OUTPUTS, TRAIN_MAX_MINIBATCHES = 12, 65536
 
+# every symbol include/meshenv_offpolicy_train.h declares: SAC.train / TD3.train as one call, and the draw of all its minibatches
+EXPORTS_OFFPOLICY_TRAIN = [
+    "meshenv_offpolicy_train_create", "meshenv_offpolicy_train_destroy", "meshenv_offpolicy_train_set_stream",
+    "meshenv_offpolicy_train_last_error", "meshenv_offpolicy_train_run", "meshenv_replay_sample_batches",
+]
+OFFTRAIN_OUTPUTS, OFFTRAIN_MAX_STEPS = 8, 65536
+OFFTRAIN_SAMPLE_FLOATS, REPLAY_BATCHES_MAX_SAMPLES = 41, 2 ** 24
+
 
 class MeshOptimScalars(C.Structure):
     """include/meshenv_optim.h MeshOptimScalars: the host-computed scalars of one step, a kernel argument."""
@@ -211,7 +219,7 @@ def load():
                                           ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
                                           ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True),
                                           ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True),
-                                          ("meshenv_onpolicy_train", [], True)):
+                                          ("meshenv_onpolicy_train", [], True), ("meshenv_offpolicy_train", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -259,7 +267,11 @@ def load():
     L.meshenv_onpolicy_train_run.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_double, f32, f32, C.c_int, C.c_int, f32, C.c_double,
                                              C.POINTER(MeshOptimScalars), C.c_int, vp]
-    for name in ("meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
+    L.meshenv_replay_sample_batches.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 7
+    L.meshenv_offpolicy_train_run.argtypes = [vp] * 7 + [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
+                                              C.POINTER(vp), C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(MeshOptimScalars),
+                                              C.POINTER(MeshOptimScalars), C.c_int, vp]
+    for name in ("meshenv_replay_sample_batches", "meshenv_offpolicy_train_run", "meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
                  "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",
                  "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample", "meshenv_td3_actor_grad_bind",

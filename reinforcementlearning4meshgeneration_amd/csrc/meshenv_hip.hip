@@ -9,6 +9,7 @@
 #include "../../include/meshenv_ppo_grad.h"
 #include "../../include/meshenv_rollout.h"
 #include "../../include/meshenv_onpolicy_train.h"
+#include "../../include/meshenv_offpolicy_train.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -40,6 +41,7 @@
 #include "meshenv_optim.h"
 #include "meshenv_rollout.h"
 #include "meshenv_onpolicy_train.h"
+#include "meshenv_offpolicy_train.h"
 
 using namespace meshenv;
 
@@ -2269,21 +2271,25 @@ int meshenv_replay_add(MeshEnv *h, int T, const float *obs0_dev, const float *ob
     return MESHENV_OK;
 }
 
-int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size, int batch, uint64_t seed, uint64_t counter,
-                          const int32_t *rows_in_dev, const int32_t *envs_in_dev, float *obs_out_dev, float *actions_out_dev,
-                          float *next_obs_out_dev, float *dones_out_dev, float *rewards_out_dev, int32_t *rows_out_dev,
-                          int32_t *envs_out_dev)
+}  // extern "C"
+
+namespace {
+
+// meshenv_replay_sample (n_batches = 0: one batch, caller indices allowed) and meshenv_replay_sample_batches (n_batches >= 1)
+int replay_sample_launch(MeshEnv *h, const std::string &fn, const float *store_dev, int rows, int size, int batch, int n_batches,
+                         uint64_t seed, uint64_t counter, const int32_t *rows_in_dev, const int32_t *envs_in_dev, float *obs_out_dev,
+                         float *actions_out_dev, float *next_obs_out_dev, float *dones_out_dev, float *rewards_out_dev,
+                         int32_t *rows_out_dev, int32_t *envs_out_dev)
 {
-    if (!h) return MESHENV_E_ARG;
-    if (batch < 1) return fail_arg(h, "meshenv_replay_sample: batch >= 1 is required");
-    if (rows < 1) return fail_arg(h, "meshenv_replay_sample: rows >= 1 is required");
-    if (size < 1 || size > rows) return fail_arg(h, "meshenv_replay_sample: size must be in [1, rows] (an empty buffer has no samples)");
+    auto refuse = [&](const char *msg) { return fail_arg(h, (fn + ": " + msg).c_str()); };
+    if (batch < 1) return refuse("batch >= 1 is required");
+    if (rows < 1) return refuse("rows >= 1 is required");
+    if (size < 1 || size > rows) return refuse("size must be in [1, rows] (an empty buffer has no samples)");
     if (!store_dev || !obs_out_dev || !actions_out_dev || !next_obs_out_dev || !dones_out_dev || !rewards_out_dev)
-        return fail_arg(h, "meshenv_replay_sample: store and the five outputs are required");
-    if ((rows_in_dev != nullptr) != (envs_in_dev != nullptr))
-        return fail_arg(h, "meshenv_replay_sample: rows_in and envs_in are given together or not at all");
-    if ((uintptr_t)store_dev % 16 != 0) return fail_arg(h, "meshenv_replay_sample: the store must be 16-byte aligned");
-    const size_t n = (size_t)h->n_envs, B = (size_t)batch;
+        return refuse("store and the five outputs are required");
+    if ((rows_in_dev != nullptr) != (envs_in_dev != nullptr)) return refuse("rows_in and envs_in are given together or not at all");
+    if ((uintptr_t)store_dev % 16 != 0) return refuse("the store must be 16-byte aligned");
+    const size_t n = (size_t)h->n_envs, B = (size_t)batch * (size_t)(n_batches > 0 ? n_batches : 1);
     struct Range { const void *p; size_t bytes; };
     const Range in[] = {{store_dev, (size_t)rows * n * kReplayR * sizeof(float)}, {rows_in_dev, B * 4}, {envs_in_dev, B * 4}};
     const Range out[] = {{obs_out_dev, B * kObsDim * 4}, {actions_out_dev, B * 3 * 4}, {next_obs_out_dev, B * kObsDim * 4},
@@ -2293,23 +2299,53 @@ int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size
         return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
     };
     for (int i = 0; i < 7; i++) {
-        if (overlap(out[i], in[0])) return fail_arg(h, "meshenv_replay_sample: an output overlaps the store");
-        if (overlap(out[i], in[1]) || overlap(out[i], in[2]))
-            return fail_arg(h, "meshenv_replay_sample: an output overlaps rows_in / envs_in");
+        if (n_batches > 0 && ((uintptr_t)out[i].p & 3) != 0) return refuse("an output is not 4-byte aligned");
+        if (overlap(out[i], in[0])) return refuse("an output overlaps the store");
+        if (overlap(out[i], in[1]) || overlap(out[i], in[2])) return refuse("an output overlaps rows_in / envs_in");
         for (int j = 0; j < i; j++)
-            if (overlap(out[i], out[j])) return fail_arg(h, "meshenv_replay_sample: two outputs overlap");
+            if (overlap(out[i], out[j])) return refuse("two outputs overlap");
     }
     MESHENV_ON_DEVICE(h);
     ReplaySampleArgs A{};
-    A.n = h->n_envs; A.rows = rows; A.size = size; A.B = batch;
+    A.n = h->n_envs; A.rows = rows; A.size = size; A.B = (int)B;
     A.seed = seed; A.counter = counter;
     A.store = store_dev; A.rows_in = rows_in_dev; A.envs_in = envs_in_dev;
     A.obs = obs_out_dev; A.act = actions_out_dev; A.next = next_obs_out_dev; A.dones = dones_out_dev; A.rew = rewards_out_dev;
     A.rows_out = rows_out_dev; A.envs_out = envs_out_dev;
-    hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)((B + kReplaySamples - 1) / kReplaySamples)), dim3(kReplayThreads), 0,
-                       h->stream, A);
+    const dim3 grid((unsigned)((B + kReplaySamples - 1) / kReplaySamples));
+    if (n_batches > 0) hipLaunchKernelGGL(k_replay_sample_batches, grid, dim3(kReplayThreads), 0, h->stream, A, batch);
+    else hipLaunchKernelGGL(k_replay_sample, grid, dim3(kReplayThreads), 0, h->stream, A);
     HIP_TRY(h, hipGetLastError());
     return MESHENV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size, int batch, uint64_t seed, uint64_t counter,
+                          const int32_t *rows_in_dev, const int32_t *envs_in_dev, float *obs_out_dev, float *actions_out_dev,
+                          float *next_obs_out_dev, float *dones_out_dev, float *rewards_out_dev, int32_t *rows_out_dev,
+                          int32_t *envs_out_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    return replay_sample_launch(h, "meshenv_replay_sample", store_dev, rows, size, batch, 0, seed, counter, rows_in_dev, envs_in_dev,
+                                obs_out_dev, actions_out_dev, next_obs_out_dev, dones_out_dev, rewards_out_dev, rows_out_dev, envs_out_dev);
+}
+
+static_assert(MESHENV_REPLAY_BATCHES_MAX_SAMPLES <= INT32_MAX / kReplayR, "k_replay_sample_batches indexes its samples in int32");
+
+int meshenv_replay_sample_batches(MeshEnv *h, const float *store_dev, int rows, int size, int batch, int n_batches, uint64_t seed,
+                                  uint64_t counter, float *obs_out_dev, float *actions_out_dev, float *next_obs_out_dev,
+                                  float *dones_out_dev, float *rewards_out_dev, int32_t *rows_out_dev, int32_t *envs_out_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (n_batches < 1) return fail_arg(h, "meshenv_replay_sample_batches: n_batches >= 1 is required");
+    if (batch >= 1 && (long long)n_batches * batch > MESHENV_REPLAY_BATCHES_MAX_SAMPLES)
+        return fail_arg(h, "meshenv_replay_sample_batches: n_batches * batch exceeds MESHENV_REPLAY_BATCHES_MAX_SAMPLES (2^24)");
+    return replay_sample_launch(h, "meshenv_replay_sample_batches", store_dev, rows, size, batch, n_batches, seed, counter, nullptr,
+                                nullptr, obs_out_dev, actions_out_dev, next_obs_out_dev, dones_out_dev, rewards_out_dev, rows_out_dev,
+                                envs_out_dev);
 }
 
 }  // extern "C"
@@ -3178,6 +3214,7 @@ struct OptProgram {
     size_t cap = 0;
     size_t jobs_at = 0;         // byte offset of the job table
     int n_jobs = 0;
+    int n_seg = 0;
     hipEvent_t copied = nullptr;   // the last upload from `host`
     hipStream_t ordered = nullptr; // the stream that is known to be ordered after that upload
     bool bound = false;
@@ -3191,9 +3228,11 @@ struct MeshOptim : HandleBase {
 
 namespace {
 
-// The launch of a bound program: k_optim_step, or with a gate (meshenv_onpolicy_train_run) k_optim_step_gated over the same
-// tables.
-int optim_step_launch(MeshOptim *o, int program, const MeshOptimScalars *scalars, const TrainGate *gate, const char *fn)
+// The launch of a bound program: k_optim_step, or with a gate (meshenv_onpolicy_train_run) k_optim_step_gated, or with a note
+// (meshenv_offpolicy_train_run) k_optim_step_noted, over the same tables.  A noted program must not step what the note reads:
+// the caller has looked (optim_program_writes).
+int optim_step_launch(MeshOptim *o, int program, const MeshOptimScalars *scalars, const TrainGate *gate, const char *fn,
+                      const OptNote *note = nullptr)
 {
     if (!o) return MESHENV_E_ARG;
     if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || !scalars)
@@ -3211,13 +3250,26 @@ int optim_step_launch(MeshOptim *o, int program, const MeshOptimScalars *scalars
     OptScalars S;
     std::memcpy(&S, scalars, sizeof(S));
     return launch(o, guard, fn, [&] {
-        if (gate)
+        if (note)
+            hipLaunchKernelGGL(k_optim_step_noted, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
+                               (const OptJob *)(P.dev + P.jobs_at), S, *note);
+        else if (gate)
             hipLaunchKernelGGL(k_optim_step_gated, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
                                (const OptJob *)(P.dev + P.jobs_at), S, *gate);
         else
             hipLaunchKernelGGL(k_optim_step, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
                                (const OptJob *)(P.dev + P.jobs_at), S);
     });
+}
+
+// The segment of a bound program that writes `ptr` (as a parameter or as a Polyak target), or -1: the host copy of its table.
+int optim_program_writes(const MeshOptim *o, int program, const float *ptr)
+{
+    const OptProgram &P = o->prog[program];
+    const OptSeg *segs = reinterpret_cast<const OptSeg *>(P.host);
+    for (int i = 0; i < P.n_seg; i++)
+        if (segs[i].p == ptr || segs[i].t == ptr) return i;
+    return -1;
 }
 
 }  // namespace
@@ -3314,6 +3366,7 @@ int meshenv_optim_bind(MeshOptim *o, int program, int n_seg, float *const *param
     o->used = true;
     P.jobs_at = jobs_at;
     P.n_jobs = (int)n_jobs;
+    P.n_seg = n_seg;
     P.bound = true;
     return MESHENV_OK;
 }
@@ -3497,6 +3550,165 @@ int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *
     if (rc != MESHENV_OK || !policy) return rc;
     rc = meshenv_policy_refresh(policy);
     return rc == MESHENV_OK ? rc : fail(t, rc, fn + ": " + policy->err);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC.train / TD3.train in one call
+static_assert(MESHENV_OFFTRAIN_OUTPUTS == kOffOut, "include/meshenv_offpolicy_train.h and csrc/meshenv_offpolicy_train.h disagree");
+static_assert(MESHENV_OFFTRAIN_SAMPLE_FLOATS == 2 * kObsDim + 3 + 2, "the sample workspace holds the five fields");
+
+struct MeshOffPolicyTrain : HandleBase {
+    float *slots = nullptr;     // [MESHENV_OFFTRAIN_MAX_STEPS][kOffSlot]: critic_loss actor_loss ent_coef_loss ent_coef per step
+};
+
+extern "C" {
+
+int meshenv_offpolicy_train_create(int device, void *stream, MeshOffPolicyTrain **out)
+{
+    const int rc = create_handle("meshenv_offpolicy_train_create", device, stream, out);
+    if (rc != MESHENV_OK) return rc;
+    MeshOffPolicyTrain *t = *out;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess || !zeroed_once(t, &t->slots, (size_t)MESHENV_OFFTRAIN_MAX_STEPS * kOffSlot)) {
+        g_create_error = "meshenv_offpolicy_train_create: allocation failed";
+        if (t->slots) (void)hipFree(t->slots);
+        delete t;
+        *out = nullptr;
+        return MESHENV_E_HIP;
+    }
+    return MESHENV_OK;
+}
+
+void meshenv_offpolicy_train_destroy(MeshOffPolicyTrain *t) { destroy_handle(t, t ? t->slots : nullptr); }
+
+const char *meshenv_offpolicy_train_last_error(const MeshOffPolicyTrain *t) { return last_error(t); }
+
+int meshenv_offpolicy_train_set_stream(MeshOffPolicyTrain *t, void *stream) { return set_stream(t, stream); }
+
+int meshenv_offpolicy_train_run(MeshOffPolicyTrain *t, MeshEnv *env, MeshTarget *target, MeshCriticGrad *cg, MeshActorGrad *sac_ag,
+                                MeshTd3ActorGrad *td3_ag, MeshOptim *o, int critic_program, const float *store_dev, int rows, int size,
+                                int batch, int K, uint64_t seed, uint64_t counter0, float *const *sample_dev, int chunk,
+                                float *target_dev, const int32_t *actor_program, const MeshOptimScalars *critic_scalars,
+                                const MeshOptimScalars *actor_scalars, int n_actor_scalars, double *out_dev)
+{
+    if (!t) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_offpolicy_train_run";
+    if (!env || !target || !cg || !o) return fail(t, MESHENV_E_ARG, fn + ": the env, target, critic-gradient and optimiser handles are required");
+    if ((sac_ag != nullptr) == (td3_ag != nullptr))
+        return fail(t, MESHENV_E_ARG, fn + ": exactly one of the SAC and the TD3 actor-gradient handle is required");
+    const bool sac = sac_ag != nullptr;
+    const int ag_device = sac ? sac_ag->device : td3_ag->device;
+    const hipStream_t ag_stream = sac ? sac_ag->stream : td3_ag->stream;
+    if (env->device != t->device || target->device != t->device || cg->device != t->device || o->device != t->device || ag_device != t->device)
+        return fail(t, MESHENV_E_ARG, fn + ": the handles are on different devices");
+    const int kind = sac ? kTargetSAC : kTargetTD3;
+    if (target->kind != kind || cg->kind != kind)
+        return fail(t, MESHENV_E_ARG, fn + ": the target and critic-gradient handles are not of the actor-gradient handle's kind");
+    if (!target->bound) return fail(t, MESHENV_E_STATE, fn + ": the target handle has no tensors bound (meshenv_target_bind)");
+    if (!target->packed) return fail(t, MESHENV_E_STATE, fn + ": the target handle was never refreshed (meshenv_target_refresh)");
+    if (!cg->bound) return fail(t, MESHENV_E_STATE, fn + ": the critic-gradient handle has no tensors bound (meshenv_critic_grad_bind)");
+    if (!(sac ? sac_ag->bound : td3_ag->bound))
+        return fail(t, MESHENV_E_STATE, fn + ": the actor-gradient handle has no tensors bound");
+    if (K < 1 || K > MESHENV_OFFTRAIN_MAX_STEPS)
+        return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(K) + " gradient steps; 1 to " + std::to_string(MESHENV_OFFTRAIN_MAX_STEPS) + " per call");
+    if (batch < 1 || chunk < 1) return fail(t, MESHENV_E_ARG, fn + ": batch >= 1 and chunk >= 1 are required");
+    if (!store_dev || !sample_dev || !target_dev || !actor_program || !critic_scalars || !out_dev || ((uintptr_t)out_dev & 7) ||
+        ((uintptr_t)target_dev & 3))
+        return fail(t, MESHENV_E_ARG, fn + ": store_dev, sample_dev, a 4-byte aligned target_dev, actor_program, critic_scalars and an "
+                                           "8-byte aligned out_dev are required");
+    for (int f = 0; f < 5; f++)
+        if (!sample_dev[f]) return fail(t, MESHENV_E_ARG, fn + ": null sample buffer " + std::to_string(f));
+    auto program_bound = [&](int p) { return p >= 0 && p < MESHENV_OPTIM_PROGRAMS && o->prog[p].bound; };
+    if (critic_program < 0 || critic_program >= MESHENV_OPTIM_PROGRAMS) return fail(t, MESHENV_E_ARG, fn + ": critic program out of range");
+    if (!program_bound(critic_program)) return fail(t, MESHENV_E_STATE, fn + ": the critic program is not bound (meshenv_optim_bind)");
+    // the actor steps: k = phase, phase + period, ... and nothing else
+    int n_actor = 0, polyak_updates = 0, phase = K, period = 1, last = -1;
+    for (int k = 0; k < K; k++) {
+        const int p = actor_program[k];
+        if (p < 0) continue;
+        if (p >= MESHENV_OPTIM_PROGRAMS) return fail(t, MESHENV_E_ARG, fn + ": actor program out of range at step " + std::to_string(k));
+        if (!o->prog[p].bound)
+            return fail(t, MESHENV_E_STATE, fn + ": program " + std::to_string(p) + " of step " + std::to_string(k) + " is not bound (meshenv_optim_bind)");
+        if (n_actor == 0) phase = k;
+        else if (n_actor == 1) period = k - last;
+        else if (k - last != period) return fail(t, MESHENV_E_ARG, fn + ": the actor steps do not recur with one period");
+        last = k;
+        n_actor++;
+        const OptSeg *segs = reinterpret_cast<const OptSeg *>(o->prog[p].host);
+        bool polyak = false;
+        for (int i = 0; i < o->prog[p].n_seg; i++) polyak = polyak || (segs[i].op & kOptPolyak) != 0;
+        polyak_updates += polyak ? 1 : 0;
+    }
+    if (n_actor == 1) period = K;        // one actor step: any period that reaches past the call
+    if (n_actor >= 2 && last + period < K) return fail(t, MESHENV_E_ARG, fn + ": the actor steps do not recur with one period");
+    if (n_actor != n_actor_scalars || (n_actor > 0 && !actor_scalars))
+        return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(n_actor_scalars) + " actor scalar sets for " + std::to_string(n_actor) + " actor steps");
+    if (env->stream != t->stream || target->stream != t->stream || cg->stream != t->stream || o->stream != t->stream || ag_stream != t->stream)
+        return fail(t, MESHENV_E_STATE, fn + ": the handles are on different streams (set_stream them to one)");
+    if (chunk > K) chunk = K;
+    if ((long long)chunk * batch > MESHENV_REPLAY_BATCHES_MAX_SAMPLES)
+        return fail(t, MESHENV_E_ARG, fn + ": chunk * batch exceeds MESHENV_REPLAY_BATCHES_MAX_SAMPLES (2^24)");
+    {   // the target buffer is written while the step's samples are still read
+        const size_t width[5] = {kObsDim, 3, kObsDim, 1, 1};
+        const uintptr_t y0 = (uintptr_t)target_dev, y1 = y0 + (size_t)batch * sizeof(float);
+        for (int f = 0; f < 5; f++) {
+            const uintptr_t s0 = (uintptr_t)sample_dev[f], s1 = s0 + (size_t)chunk * batch * width[f] * sizeof(float);
+            if (y0 < s1 && s0 < y1) return fail(t, MESHENV_E_ARG, fn + ": target_dev overlaps sample buffer " + std::to_string(f));
+        }
+    }
+    const bool learned = sac && sac_ag->log_ent_coef != nullptr;
+    if (learned && optim_program_writes(o, critic_program, sac_ag->log_ent_coef) >= 0)
+        return fail(t, MESHENV_E_ARG, fn + ": segment " + std::to_string(optim_program_writes(o, critic_program, sac_ag->log_ent_coef)) +
+                                           " of the critic program writes log_ent_coef, which the noted critic step reads");
+    float *obs = sample_dev[0], *act = sample_dev[1], *next = sample_dev[2], *dones = sample_dev[3], *rew = sample_dev[4];
+    int a = 0;
+    for (int k = 0; k < K; k++) {
+        const int j = k % chunk;
+        if (j == 0) {
+            const int nb = K - k < chunk ? K - k : chunk;
+            const int rc = meshenv_replay_sample_batches(env, store_dev, rows, size, batch, nb, seed, counter0 + (uint64_t)k, obs, act, next,
+                                                         dones, rew, nullptr, nullptr);
+            if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + env->err);
+        }
+        const size_t at = (size_t)j * batch;
+        float *slot = t->slots + (size_t)k * kOffSlot;
+        int rc = meshenv_target_forward(target, batch, next + at * kObsDim, rew + at, dones + at, nullptr, 1, seed, counter0 + (uint64_t)k,
+                                        target_dev, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + target->err);
+        rc = meshenv_critic_grad_backward(cg, batch, obs + at * kObsDim, act + at * 3, target_dev, slot, nullptr, nullptr, nullptr, nullptr);
+        if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + cg->err);
+        OptNote note{learned ? sac_ag->log_ent_coef : nullptr, slot + 3};
+        rc = optim_step_launch(o, critic_program, critic_scalars + k, nullptr, "meshenv_offpolicy_train_run", learned ? &note : nullptr);
+        if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + o->err);
+        const int p = actor_program[k];
+        if (p >= 0) {
+            if (sac) {
+                rc = meshenv_actor_grad_backward(sac_ag, batch, obs + at * kObsDim, nullptr, 1, seed, counter0 + (uint64_t)k, slot + 1, nullptr,
+                                                 nullptr, nullptr);
+                if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + sac_ag->err);
+            } else {
+                rc = meshenv_td3_actor_grad_backward(td3_ag, batch, obs + at * kObsDim, slot + 1, nullptr, nullptr);
+                if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + td3_ag->err);
+            }
+            rc = optim_step_launch(o, p, actor_scalars + a, nullptr, "meshenv_offpolicy_train_run");
+            if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + o->err);
+            a++;
+        }
+        if (sac || p >= 0) {       // a tensor the target handle has bound changed: SAC's actor every step, TD3's targets on actor steps
+            rc = meshenv_target_refresh(target);
+            if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + target->err);
+        }
+    }
+    OffFinishArgs A{};
+    A.slots = t->slots; A.out = out_dev; A.K = K; A.phase = phase; A.period = period;
+    A.actor_steps = n_actor; A.polyak_updates = polyak_updates;
+    A.mode = !sac ? kOffTd3 : learned ? kOffSacLearned : kOffSacFixed;
+    A.ent_coef = sac ? sac_ag->ent_coef : 0.0f;
+    DeviceGuard guard(t->device);
+    return launch(t, guard, "meshenv_offpolicy_train_run", [&] {
+        hipLaunchKernelGGL(k_offpolicy_finish, dim3(1), dim3(kTrFinishThreads), 0, t->stream, A);
+    }, "finish launch");
 }
 
 }  // extern "C"

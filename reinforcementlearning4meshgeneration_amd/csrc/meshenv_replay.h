@@ -126,7 +126,13 @@ static_assert(kReplayThreads >= kReplaySamples, "one thread per sample draws its
 // any; the records go to an LDS tile, from which the five outputs are written as runs of consecutive floats (sample-major,
 // as the outputs are laid out), so every wave's stores are contiguous.  A caller-supplied index outside [0, rows) x
 // [0, n_envs) reads nothing: that sample's outputs are NaN and its echoed row is -1.
-__global__ __launch_bounds__(kReplayThreads) void k_replay_sample(ReplaySampleArgs a)
+//
+// BATCHES (k_replay_sample_batches): a.B = n_batches * batch is the flat sample count and the outputs are [n_batches][batch][.],
+// i.e. flat over j = g * batch + i.  Sample i of batch g draws with the Philox words (i, lo(counter + g), hi(counter + g),
+// kReplayDrawTag), the 64-bit sum wrapping modulo 2^64: the bits of k_replay_sample at counter + g.  A workgroup's
+// kReplaySamples samples may lie in two or more batches.  No caller indices.
+template <bool BATCHES>
+__device__ __forceinline__ void replay_sample_body(const ReplaySampleArgs &a, int batch)
 {
     __shared__ __align__(16) float tile[kReplaySamples][kReplayStride];
     __shared__ int srow[kReplaySamples], senv[kReplaySamples];
@@ -136,13 +142,15 @@ __global__ __launch_bounds__(kReplayThreads) void k_replay_sample(ReplaySampleAr
     if (tid < ns) {
         const int s = s0 + tid;
         int row, env;
-        if (a.rows_in) {
+        if (!BATCHES && a.rows_in) {
             row = a.rows_in[s];
             env = a.envs_in[s];
             if ((unsigned)row >= (unsigned)a.rows || (unsigned)env >= (unsigned)a.n) row = -1, env = 0;
         } else {
+            const int g = BATCHES ? s / batch : 0;
+            const uint64_t counter = a.counter + (uint64_t)g;
             uint32_t w[4];
-            philox4x32((uint32_t)s, (uint32_t)a.counter, (uint32_t)(a.counter >> 32), kReplayDrawTag, (uint32_t)a.seed,
+            philox4x32((uint32_t)(s - g * batch), (uint32_t)counter, (uint32_t)(counter >> 32), kReplayDrawTag, (uint32_t)a.seed,
                        (uint32_t)(a.seed >> 32), w);
             row = (int)__umulhi(w[0], (uint32_t)a.size);
             env = (int)__umulhi(w[1], (uint32_t)a.n);
@@ -180,6 +188,14 @@ __global__ __launch_bounds__(kReplayThreads) void k_replay_sample(ReplaySampleAr
         a.dones[base + tid] = tile[tid][kRepDone] * (1.0f - tile[tid][kRepTimeout]);
         a.rew[base + tid] = tile[tid][kRepReward];
     }
+}
+
+__global__ __launch_bounds__(kReplayThreads) void k_replay_sample(ReplaySampleArgs a) { replay_sample_body<false>(a, 1); }
+
+// n_batches minibatches of `batch` samples in one launch (meshenv_replay_sample_batches)
+__global__ __launch_bounds__(kReplayThreads) void k_replay_sample_batches(ReplaySampleArgs a, int batch)
+{
+    replay_sample_body<true>(a, batch);
 }
 
 }  // namespace meshenv

@@ -213,6 +213,41 @@ class DeviceReplayBuffer:
         out, rows, envs = self._sample(batch, int(seed), int(counter), None, None, bool(return_indices))
         return (out, rows, envs) if return_indices else out
 
+    def _stacked(self, n_batches: int, batch: int):
+        """The five stacked tensors of ``n_batches`` batches: [n_batches, batch, 18], [.., 3], [.., 18], [.., 1], [.., 1]."""
+        t = self._torch
+        f32 = dict(dtype=t.float32, device=self.device)
+        return tuple(t.empty((n_batches, batch, w), **f32) for w in (OBS_DIM, ACT_DIM, OBS_DIM, 1, 1))
+
+    def sample_batches(self, batch_size: int, n_batches: int, seed: int = 0, counter: int = 0, return_indices: bool = False):
+        """``n_batches`` x ``sample(batch_size)`` in ONE launch (k_replay_sample_batches): a list of ReplayBufferSamples whose
+        fields are contiguous views into five stacked tensors [n_batches, batch_size, .].  Batch g has exactly the bits of
+        ``sample(batch_size, seed=seed, counter=counter + g)`` (the counter wraps modulo 2^64).  return_indices: also the int32
+        CUDA tensors (batch_inds, env_inds), [n_batches, batch_size] each."""
+        batch, G = int(batch_size), int(n_batches)
+        if batch < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if G < 1:
+            raise ValueError(f"n_batches must be positive, got {n_batches}")
+        if G * batch > _capi.REPLAY_BATCHES_MAX_SAMPLES:
+            raise ValueError(f"{G} batches of {batch} are {G * batch} samples; at most {_capi.REPLAY_BATCHES_MAX_SAMPLES} per launch")
+        if self.size() < 1:
+            raise ValueError("cannot sample from an empty replay buffer")
+        t = self._torch
+        stacked = self._stacked(G, batch)
+        rows_out = envs_out = None
+        if return_indices:
+            rows_out = t.empty((G, batch), dtype=t.int32, device=self.device)
+            envs_out = t.empty((G, batch), dtype=t.int32, device=self.device)
+        self._venv._bind_stream()
+        rc = self._L.meshenv_replay_sample_batches(
+            self._venv._handle, self.store.data_ptr(), self.rows, self.size(), batch, G, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+            C.c_uint64(int(counter) & (2 ** 64 - 1)), *[x.data_ptr() for x in stacked],
+            rows_out.data_ptr() if return_indices else None, envs_out.data_ptr() if return_indices else None)
+        _capi.check(self._venv._handle, rc, "meshenv_replay_sample_batches")
+        out = [ReplayBufferSamples(*[x[g] for x in stacked]) for g in range(G)]
+        return (out, rows_out, envs_out) if return_indices else out
+
     def gather(self, batch_inds, env_inds, check: bool = True):
         """SB3's ReplayBuffer._get_samples(batch_inds) with explicit env indices: int32 CUDA tensors [B] of rows in
         [0, buffer_size) and envs in [0, n_envs).  check=True validates their range first (one host synchronisation);

@@ -1,0 +1,312 @@
+"""GPU: ``FusedOffPolicyTrain.train`` (include/meshenv_offpolicy_train.h) against the composition the project ships, driven by
+the transcription of SB3's two loops on a deep-copied twin (tests/offpolicy_train_ref.py).  Every case runs two successive
+``train()`` calls; afterwards every parameter, every Adam moment, every optimiser ``step``, ``_n_updates`` and the TD target of
+one fixed batch are equal bit for bit, and the logged means lie within the bound of a float64 sum of the composition's
+float32 values.
+
+train/ent_coef (learned).  The device writes ``expf(log_ent_coef)`` per step; the reference is the float64 ``exp`` of the
+twin's float32 ``log_ent_coef`` before that step, rounded to float32.  The margin is 1.5 ulp of the reference: 1 ulp for the
+device's ``expf`` (the figure of ROCm's HIP math accuracy table for expf) plus half an ulp for the reference's own rounding.
+Single steps are read through calls of one gradient step, whose mean is that step's value; the first is exp(0) = 1 exactly."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import offpolicy_train_ref as TR
+
+pytestmark = pytest.mark.gpu
+
+SEED = 4
+
+
+@pytest.fixture(scope="module")
+def buf():
+    from reinforcementlearning4meshgeneration_amd import DeviceReplayBuffer
+    from reinforcementlearning4meshgeneration_amd.domains import boundary
+    from reinforcementlearning4meshgeneration_amd.vec_env import MeshVecEnv
+    env = MeshVecEnv([boundary(0)], n_envs=TR.N_ENVS)
+    b = TR.fill(DeviceReplayBuffer(env, buffer_size=8 * TR.N_ENVS), steps=6)
+    assert b.size() == 6
+    yield b
+    env.close()
+
+
+@pytest.fixture(scope="module")
+def fixed_batch(buf):
+    import torch
+    s = buf.sample(33, seed=99, counter=7)
+    noise = torch.from_numpy(np.random.default_rng(3).standard_normal((33, 3)).astype(np.float32)).cuda()
+    return s, noise
+
+
+def _pair(kind, buf, **attrs):
+    from reinforcementlearning4meshgeneration_amd import FusedOffPolicyTrain
+    m = TR.model(kind, **attrs)
+    tw = TR.twin(m)
+    return m, tw, FusedOffPolicyTrain.from_sb3(m, buf), TR.Composition(tw, buf)
+
+
+def _ulp32(x):
+    return float(np.spacing(np.float32(abs(x))))
+
+
+def _check_logs(logs, recs, m, kind, learned):
+    """One train()'s logs against the composition's records of the same steps."""
+    got, recs = logs.read(), TR.host(recs)
+    K = len(recs)
+    actor = [r["actor_loss"] for r in recs if "actor_loss" in r]
+    assert got["train/n_updates"] == m._n_updates and got["gradient_steps"] == K and got["actor_steps"] == len(actor)
+    want = {"train/critic_loss": [r["critic_loss"] for r in recs]}
+    if actor:
+        want["train/actor_loss"] = actor
+    else:
+        assert "train/actor_loss" not in got and math.isnan(logs.values()["actor_loss"])
+    if learned:
+        want["train/ent_coef_loss"] = [r["ent_coef_loss"] for r in recs]
+    else:
+        assert "train/ent_coef_loss" not in got and math.isnan(logs.values()["ent_coef_loss"])
+    for key, vals in want.items():
+        mean, bound = TR.mean_and_bound(vals)
+        print(f"{key}: |device - fsum| = {abs(got[key] - mean):.3e}, bound {bound:.3e} over {len(vals)} steps")
+        assert abs(got[key] - mean) <= bound, (key, got[key], mean, bound)
+    assert got["last_critic_loss"] == recs[-1]["critic_loss"]
+    if kind == "td3":
+        assert "train/ent_coef" not in got and math.isnan(logs.values()["ent_coef"])
+    elif learned:
+        refs = [float(np.float32(math.exp(r["log_ent_coef"]))) for r in recs]
+        mean, bound = TR.mean_and_bound(refs)
+        margin = sum(1.5 * _ulp32(r) for r in refs) / K + bound
+        print(f"train/ent_coef: |device - reference mean| = {abs(got['train/ent_coef'] - mean):.3e}, margin {margin:.3e}")
+        assert abs(got["train/ent_coef"] - mean) <= margin
+    return got
+
+
+def _run(kind, buf, fixed_batch, K, B, learned=True, chunks=(None, None), **attrs):
+    import torch
+    m, tw, tr, comp = _pair(kind, buf, learned=learned, **attrs)
+    out = []
+    try:
+        for call in range(2):
+            c0 = tr.counter
+            assert c0 == call * K
+            logs = tr.train(K, batch_size=B, seed=SEED, sample_chunk=chunks[call])
+            recs = comp.train(K, batch_size=B, seed=SEED, counter=c0)
+            out.append(_check_logs(logs, recs, m, kind, learned and kind == "sac"))
+            assert TR.differing(m, tw) == [], f"after call {call}"
+        assert tr.calls == 2 and m._n_updates == tw._n_updates
+        s, noise = fixed_batch                       # the target handle's snapshot is current
+        y, yt = tr.td.target(s, noise=noise), comp.td.target(s, noise=noise)
+        assert torch.equal(y.view(torch.int32), yt.view(torch.int32)) and bool(torch.isfinite(y).all())
+    finally:
+        tr.close()
+        comp.close()
+    return out, m
+
+
+# ----------------------------------------------------------------------------------------------------------- SAC
+@pytest.mark.parametrize("K,B,interval", [(1, 100, 1), (5, 65, 2), (3, 1, 1)])
+def test_sac_learned_coefficient(buf, fixed_batch, K, B, interval):
+    out, m = _run("sac", buf, fixed_batch, K, B, target_update_interval=interval)
+    assert m._n_updates == 2 * K
+    assert out[0]["polyak_updates"] == len(range(0, K, interval)) and out[0]["actor_steps"] == K
+    assert float(m.critic.optimizer.state[TR.critic_params(m)[0]]["step"]) == 2 * K
+    assert float(m.ent_coef_optimizer.state[m.log_ent_coef]["step"]) == 2 * K
+    if K == 1:
+        assert out[0]["train/ent_coef"] == 1.0               # exp(0), before the first step
+
+
+def test_sac_fixed_coefficient(buf, fixed_batch):
+    out, m = _run("sac", buf, fixed_batch, 3, 100, learned=False)
+    for got in out:
+        assert got["train/ent_coef"] == float(m.ent_coef_tensor) == float(np.float32(0.1))
+        assert "train/ent_coef_loss" not in got and set(got) >= {"train/actor_loss", "train/critic_loss", "train/n_updates"}
+
+
+def test_sac_ent_coef_of_single_steps(buf):
+    """Each step's logged coefficient against the float64 exp of the twin's log_ent_coef before it, within 1.5 ulp."""
+    m, tw, tr, comp = _pair("sac", buf)
+    worst = 0.0
+    try:
+        for step in range(5):
+            got = tr.train(1, seed=SEED).read()["train/ent_coef"]
+            rec = TR.host(comp.train(1, seed=SEED, counter=step))[0]
+            ref = float(np.float32(math.exp(rec["log_ent_coef"])))
+            worst = max(worst, abs(got - ref) / _ulp32(ref))
+            assert abs(got - ref) <= 1.5 * _ulp32(ref), (step, got, ref)
+            if step == 0:
+                assert rec["log_ent_coef"] == 0.0 and got == 1.0
+            else:
+                assert rec["log_ent_coef"] != 0.0
+        assert TR.differing(m, tw) == []
+        print(f"train/ent_coef over 5 single steps: max |device - float32(exp64)| = {worst:.3f} ulp")
+    finally:
+        tr.close()
+        comp.close()
+
+
+# ----------------------------------------------------------------------------------------------------------- TD3
+def test_td3_delay_2_steps_the_actor_at_updates_2_4_6(buf, fixed_batch):
+    out, m = _run("td3", buf, fixed_batch, 3, 100, policy_delay=2)
+    assert [g["actor_steps"] for g in out] == [1, 2] and [g["polyak_updates"] for g in out] == [1, 2]
+    assert m._n_updates == 6
+    assert float(m.actor.optimizer.state[TR.actor_params(m)[0]]["step"]) == 3
+    assert float(m.critic.optimizer.state[TR.critic_params(m)[0]]["step"]) == 6
+
+
+def test_td3_delay_1(buf, fixed_batch):
+    out, m = _run("td3", buf, fixed_batch, 3, 65, policy_delay=1)
+    assert [g["actor_steps"] for g in out] == [3, 3]
+
+
+def test_td3_one_step_from_an_even_n_updates_leaves_the_actor_alone(buf):
+    import torch
+    m, tw, tr, comp = _pair("td3", buf, policy_delay=2)
+    try:
+        tr.train(2, seed=SEED)                               # updates 1, 2: the actor's state exists, _n_updates is even
+        comp.train(2, seed=SEED, counter=0)
+        assert m._n_updates == 2 and TR.differing(m, tw) == []
+        keep = {k: v.detach().clone() for k, v in TR.state(m).items() if k.startswith(("actor", "critic_target"))}
+        assert any(k.startswith("actor.optimizer") for k in keep) and any(k.startswith("actor_target") for k in keep)
+        logs = tr.train(1, seed=SEED)
+        recs = comp.train(1, seed=SEED, counter=2)
+        got = _check_logs(logs, recs, m, "td3", False)
+        assert got["actor_steps"] == 0 and got["polyak_updates"] == 0 and "train/actor_loss" not in got and m._n_updates == 3
+        now = TR.state(m)
+        assert all(torch.equal(now[k].detach().contiguous().view(torch.int32), v.contiguous().view(torch.int32)) for k, v in keep.items())
+        assert TR.differing(m, tw) == []
+    finally:
+        tr.close()
+        comp.close()
+
+
+# ----------------------------------------------------------------------------------------------------------- the queue
+def test_chunk_boundaries_leave_the_same_bits(buf, fixed_batch):
+    _, a = _run("sac", buf, fixed_batch, 5, 65, chunks=(2, 1), target_update_interval=2)
+    _, b = _run("sac", buf, fixed_batch, 5, 65, chunks=(5, 5), target_update_interval=2)
+    assert TR.differing(a, b) == []                          # and two fresh runs leave equal bits
+    _, c = _run("td3", buf, fixed_batch, 5, 100, chunks=(2, 3))
+    _, d = _run("td3", buf, fixed_batch, 5, 100)
+    assert TR.differing(c, d) == []
+
+
+def test_lr_schedule_steps_with_the_scheduled_lr(buf):
+    m, tw, tr, comp = _pair("sac", buf, lr_schedule=lambda progress: 1e-3 * progress, _current_progress_remaining=0.5)
+    try:
+        comp.set_lr(5e-4)                                    # the loop's lr, set by hand
+        tr.train(3, seed=SEED)
+        comp.train(3, seed=SEED, counter=0)
+        assert all(opt.param_groups[0]["lr"] == 5e-4 for _, opt in TR.optimizers(m))
+        assert TR.differing(m, tw) == []
+        m._current_progress_remaining = tw._current_progress_remaining = 0.25
+        comp.set_lr(2.5e-4)
+        tr.train(2, seed=SEED)
+        comp.train(2, seed=SEED, counter=3)
+        assert TR.differing(m, tw) == []
+        fresh = TR.model("sac")                              # a run at the default lr differs
+        assert TR.differing(m, fresh) != []
+    finally:
+        tr.close()
+        comp.close()
+
+
+@pytest.mark.parametrize("kind", ["sac", "td3"])
+def test_the_handles_stay_usable_between_two_trains(buf, kind):
+    """cg.backward + fo.critic_step(), a stock optimizer.step() and a load_state_dict in between: the next train() matches."""
+    m, tw, tr, comp = _pair(kind, buf)
+    try:
+        tr.train(2, seed=SEED)
+        comp.train(2, seed=SEED, counter=0)
+        binds = tr.fo.binds
+        tr.train(2, seed=SEED)
+        comp.train(2, seed=SEED, counter=2)
+        assert tr.fo.binds == binds                          # the steady state: no upload, the kept plans
+        for model, h in ((m, tr), (tw, comp)):
+            s = buf.sample(40, seed=8, counter=1)
+            y = h.td.target(s, seed=8, counter=1)
+            h.cg.backward(s, y)
+            h.fo.critic_step()
+            model.actor.optimizer.step()                     # stock torch on the gradients the last actor backward left
+            opt = model.critic.optimizer
+            opt.load_state_dict(opt.state_dict())            # replaces the state tensors
+            h.td.refresh()
+        assert TR.differing(m, tw) == []
+        c0 = tr.counter
+        logs = tr.train(3, seed=SEED)
+        recs = comp.train(3, seed=SEED, counter=c0)
+        _check_logs(logs, recs, m, kind, kind == "sac")
+        assert c0 == 4 and TR.differing(m, tw) == []
+    finally:
+        tr.close()
+        comp.close()
+
+
+def test_refusals_on_the_device(buf):
+    import torch
+    from reinforcementlearning4meshgeneration_amd import DeviceReplayBuffer, FusedOffPolicyTrain, MeshEnvError
+    m, tw, tr, comp = _pair("sac", buf)
+    try:
+        with pytest.raises(ValueError, match="gradient_steps"):
+            tr.train(0)
+        with pytest.raises(ValueError, match="gradient_steps"):
+            tr.train(-1)
+        with pytest.raises(ValueError, match="sample_chunk"):
+            tr.train(2, sample_chunk=0)
+        empty = DeviceReplayBuffer(buf._venv, buffer_size=8 * TR.N_ENVS)
+        other = FusedOffPolicyTrain.from_sb3(m, empty, td=tr.td, cg=tr.cg, ag=tr.ag, fo=tr.fo)
+        with pytest.raises(ValueError, match="empty replay buffer"):
+            other.train(1)
+        other.close()                                        # closes nothing it was given
+        with pytest.raises(ValueError, match="not a DeviceReplayBuffer"):
+            FusedOffPolicyTrain.from_sb3(m, object())
+        # handles set to different streams
+        side = torch.cuda.Stream()
+        tr._L.meshenv_critic_grad_set_stream(tr.cg._h, C.c_void_p(side.cuda_stream))
+        with pytest.raises(MeshEnvError, match=r"the handles are on different streams \(set_stream them to one\)"):
+            tr.train(1, seed=SEED)
+        tr._L.meshenv_critic_grad_set_stream(tr.cg._h, C.c_void_p(tr.cg._stream))
+        assert tr.calls == 0 and tr.counter == 0 and m._n_updates == 0      # nothing was enqueued, nothing was stepped
+        assert all(float(st["step"]) == 0.0 for _, opt in TR.optimizers(m) for st in opt.state.values())
+        tr.train(2, seed=SEED)
+        comp.train(2, seed=SEED, counter=0)
+        assert TR.differing(m, tw) == []
+        _c_refusals(tr, buf)
+        torch.cuda.synchronize()
+        assert TR.differing(m, tw) == []                     # a refused call enqueues nothing
+    finally:
+        tr.close()
+        comp.close()
+
+
+def _c_refusals(tr, buf):
+    """meshenv_offpolicy_train_run's own refusals, on the handles of a SAC train() that has run (programs 0, 1 bound)."""
+    import torch
+    from reinforcementlearning4meshgeneration_amd import _capi
+    L, S = tr._L, _capi.MeshOptimScalars
+    _, _, stacked, target = tr._work
+    out = torch.empty(8, dtype=torch.float64, device="cuda")
+
+    def call(**kw):
+        K = kw.get("K", 2)
+        n = max(K, 1) if K <= 8 else 1
+        a = dict(t=tr._h, env=buf._venv._handle, td=tr.td._h, cg=tr.cg._h, sac=tr.ag._h, td3=None, fo=tr.fo._h, cp=0,
+                 store=buf.store.data_ptr(), rows=buf.rows, size=buf.size(), batch=100, K=K, seed=1, c0=0, samples=tr._ptrs(stacked),
+                 chunk=2, target=target.data_ptr(), progs=(C.c_int32 * n)(*[1] * n), cs=(S * n)(), acs=(S * n)(), na=n,
+                 out=out.data_ptr())
+        a.update(kw)
+        rc = L.meshenv_offpolicy_train_run(*a.values())
+        return rc, L.meshenv_offpolicy_train_last_error(tr._h).decode()
+
+    cases = [(dict(K=0), _capi.E_ARG, "gradient steps"), (dict(K=65537), _capi.E_ARG, "gradient steps"),
+             (dict(batch=0), _capi.E_ARG, "batch >= 1"), (dict(chunk=0), _capi.E_ARG, "chunk >= 1"),
+             (dict(td3=tr.ag._h), _capi.E_ARG, "exactly one"), (dict(sac=None), _capi.E_ARG, "exactly one"),
+             (dict(na=1), _capi.E_ARG, "actor scalar sets"), (dict(out=out.data_ptr() + 4), _capi.E_ARG, "8-byte aligned"),
+             (dict(out=None), _capi.E_ARG, "are required"), (dict(target=stacked[0].data_ptr()), _capi.E_ARG, "overlaps sample buffer"),
+             (dict(K=4, progs=(C.c_int32 * 4)(1, 1, -1, 1), na=3), _capi.E_ARG, "one period"),
+             (dict(progs=(C.c_int32 * 2)(3, 3)), _capi.E_STATE, "is not bound"), (dict(cp=4), _capi.E_STATE, "critic program is not bound"),
+             (dict(cp=99), _capi.E_ARG, "out of range"), (dict(size=0), _capi.E_ARG, "size must be"),
+             (dict(cp=1), _capi.E_ARG, "writes log_ent_coef")]
+    for kw, code, msg in cases:
+        rc, err = call(**kw)
+        assert rc == code and msg in err, (kw, rc, err)
