@@ -8,7 +8,8 @@ twin model made by ``copy.deepcopy`` before anything runs, with the same seeds a
           ag.backward(s) -> fo.actor_step(polyak=True) -> td.refresh()
 
 and the models and the buffer the tests share.  ``sac_steps`` / ``td3_steps`` are the two schedules as SB3 states them, with
-no device."""
+no device; ``finish_order_means`` is k_offpolicy_finish's own order of the logged sums in numpy float64, with no device
+either."""
 import copy
 import math
 
@@ -35,6 +36,59 @@ def td3_steps(gradient_steps, policy_delay, n_updates):
         n_updates += 1
         out.append((n_updates, n_updates % policy_delay == 0))
     return out, n_updates
+
+
+# ---------------------------------------------------------------------------------------- k_offpolicy_finish, restated
+FINISH_THREADS = 1024                                    # kTrFinishThreads
+SAC_LEARNED, SAC_FIXED, TD3 = 0, 1, 2                    # kOffSacLearned, kOffSacFixed, kOffTd3
+
+
+def phase_period(actor):
+    """(phase, period) as meshenv_offpolicy_train_run derives them from the per-step flags "this step updates the actor": the
+    first such step and the distance to the second; one actor step: period K; none: phase K, period 1."""
+    at = [k for k, u in enumerate(actor) if u]
+    K = len(actor)
+    if not at:
+        return K, 1
+    return at[0], (K if len(at) == 1 else at[1] - at[0])
+
+
+def finish_order_means(slots, K, phase, period, mode, ent_coef=None, threads=FINISH_THREADS, trips=None):
+    """What k_offpolicy_finish (csrc/meshenv_offpolicy_train.h) writes, restated in numpy float64: thread t adds the float32
+    slots of its steps k = t, t + 1024, ... one after another to four partial sums that start at 0.0 (critic_loss of every
+    step; ent_coef of every step with a learned coefficient; actor_loss, and ent_coef_loss when learned, of the steps with
+    k >= phase and (k - phase) % period == 0), train_block_sum's tree halves the 1024 partial sums of each, and the sums are
+    divided by K or by the number of actor steps (NaN without one).  slots: [>= K][4] float32.
+
+    Returns dict(critic_loss, actor_loss, ent_coef_loss, ent_coef, last_critic_loss, steps: the selected k).  ``trips``: how
+    many trips of the strided loop are taken, None for all; ``trips=1`` is the kernel that reads steps 0 .. 1023 only."""
+    slots = np.asarray(slots, np.float32)[:K].astype(np.float64)
+    k = np.arange(K)
+    selected = (k >= phase) & ((k - phase) % period == 0)
+    learned = mode == SAC_LEARNED
+    n_trips = -(-K // threads) if trips is None else min(trips, -(-K // threads))
+
+    def block_sum(x, take):
+        s = np.zeros(threads, np.float64)
+        for trip in range(n_trips):
+            seg, use = x[trip * threads:(trip + 1) * threads], take[trip * threads:(trip + 1) * threads]
+            s[:len(seg)] = np.where(use, s[:len(seg)] + seg, s[:len(seg)])
+        w = threads // 2
+        while w > 0:
+            s[:w] = s[:w] + s[w:2 * w]
+            w >>= 1
+        return float(s[0])
+    every, none = np.ones(K, bool), np.zeros(K, bool)
+    critic = block_sum(slots[:, 0], every)
+    actor = block_sum(slots[:, 1], selected)
+    ent_loss = block_sum(slots[:, 2], selected if learned else none)
+    ent = block_sum(slots[:, 3], every if learned else none)
+    n_actor = int(selected.sum())
+    nan = float("nan")
+    return dict(critic_loss=critic / float(K), actor_loss=actor / float(n_actor) if n_actor else nan,
+                ent_coef_loss=ent_loss / float(n_actor) if learned and n_actor else nan,
+                ent_coef=ent / float(K) if learned else float(np.float32(ent_coef)) if mode == SAC_FIXED else nan,
+                last_critic_loss=float(slots[K - 1, 0]), steps=[int(i) for i in k[selected]])
 
 
 # ---------------------------------------------------------------------------------------- models

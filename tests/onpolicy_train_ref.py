@@ -5,6 +5,7 @@
                       tests feed it hand-made records, ``compose`` feeds it the kernels the project already ships
     explained_variance_ref / explained_variance_f64
                       stable_baselines3.common.utils.explained_variance as numpy states it, and its fp64 restatement
+    finish_order_f64  k_train_finish's own order of the same sums in numpy float64: 1024 strided partial sums and a halving tree
     compose           rb.get -> pg.backward -> host KL test -> fo.policy_step -> refresh on a model: the oracle of the GPU tests
     histories, perms  the synthetic [T][n] rollout and the fixed permutations both sides of a GPU test take
     eager_kls         the same loop on CPU torch (ppo_grad_ref.eager + torch's Adam): how the seed of the second-epoch stop was checked
@@ -82,6 +83,39 @@ def explained_variance_f64(y_pred, y_true):
     return (float("nan") if var_r == 0 else 1.0 - var_d / var_r), var_d, var_r
 
 
+FINISH_THREADS = 1024      # kTrFinishThreads: k_train_finish's one workgroup
+
+
+def finish_order_f64(values, returns, threads=FINISH_THREADS, trips=None):
+    """(the value, var(returns - values), var(returns)) in k_train_finish's order (csrc/meshenv_onpolicy_train.h), restated in
+    numpy float64 with no device code: d = r - v formed in float32; thread t adds its rows t, t + 1024, ... one after another
+    to a partial sum that starts at 0.0; train_block_sum's tree halves the 1024 partial sums (red[t] += red[t + w], w = 512,
+    256, ..., 1); two passes, the means first, then the centred squares (cr * cr rounded, then added: the library is built
+    with -ffp-contract=off); every sum is divided by ``rows``.
+
+    ``trips``: how many trips of the strided loop are taken; None is all of them.  ``trips=1`` is the kernel that reads only
+    rows 0 .. 1023 and still divides by ``rows``: the counter-example the sizes above 1024 are there to catch."""
+    r32, v32 = np.asarray(returns, np.float32), np.asarray(values, np.float32)
+    rows = len(r32)
+    r, d = r32.astype(np.float64), (r32 - v32).astype(np.float64)
+    n_trips = -(-rows // threads) if trips is None else min(trips, -(-rows // threads))
+
+    def block_sum(x):
+        s = np.zeros(threads, np.float64)
+        for k in range(n_trips):
+            seg = x[k * threads:(k + 1) * threads]
+            s[:len(seg)] = s[:len(seg)] + seg
+        w = threads // 2
+        while w > 0:
+            s[:w] = s[:w] + s[w:2 * w]
+            w >>= 1
+        return float(s[0])
+    mean_r, mean_d = block_sum(r) / float(rows), block_sum(d) / float(rows)
+    cr, cd = r - mean_r, d - mean_d
+    var_r, var_d = block_sum(cr * cr) / float(rows), block_sum(cd * cd) / float(rows)
+    return (float("nan") if var_r == 0.0 else 1.0 - var_d / var_r), var_d, var_r
+
+
 def std_ref(log_std):
     """exp(log_std).mean() in float32 over the three elements: each exp correctly rounded, ((e0 + e1) + e2) / 3."""
     e = [np.float32(math.exp(float(x))) for x in np.asarray(log_std, np.float32)]
@@ -89,16 +123,26 @@ def std_ref(log_std):
 
 
 # ----------------------------------------------------------------------------------------------------------- inputs
-def host_histories(kind, T, n, constant_returns=False):
+def host_histories(kind, T, n, constant_returns=False, offset=0.0, scale=1.0):
     """A [T][n] rollout (numpy float32) of tests/ppo_grad_ref.py's batch rows for the recipe's policy: returns N(0, 1), values =
-    returns / 2 (so var(returns - values) / var(returns) = 1 / 4)."""
+    returns / 2 (so var(returns - values) / var(returns) = 1 / 4).
+
+    ``offset``, ``scale``: returns = offset + scale z with z the same N(0, 1) draw, in float32.  With ``offset == 0`` the values
+    stay returns / 2; then d = returns - values is returns / 2 EXACTLY, so var_d / var_r is 1 / 4 over ANY subset of the rows
+    and explained_variance cannot tell a kernel that drops rows.  With an offset, values = returns - scale / 2 z: d is still
+    about scale / 2 z, but the mean of the returns is far from 0 and every row counts.  The defaults give the arrays of the
+    two-argument call bit for bit."""
     import on_policy_stubs as S
     import policy_ref as R
     import ppo_grad_ref as P
     data = P.batch(P.modules(S.RECIPES[kind]), T * n, R.input_rows())
-    ret = np.full((T, n), 0.75, np.float32) if constant_returns else data["returns"].reshape(T, n)
+    z = data["returns"].reshape(T, n)
+    plain = offset == 0.0 and scale == 1.0
+    shifted = z if plain else np.float32(offset) + np.float32(scale) * z
+    value = shifted * np.float32(0.5) if offset == 0.0 else shifted - np.float32(0.5 * scale) * z
+    ret = np.full((T, n), 0.75, np.float32) if constant_returns else shifted
     host = {"obs": data["observations"].reshape(T, n, 18), "buffer_actions": data["actions"].reshape(T, n, 3),
-            "value": data["returns"].reshape(T, n) * np.float32(0.5), "log_prob": data["old_log_prob"].reshape(T, n),
+            "value": value, "log_prob": data["old_log_prob"].reshape(T, n),
             "advantages": data["advantages"].reshape(T, n), "returns": ret}
     return {k: np.ascontiguousarray(v) for k, v in host.items()}
 

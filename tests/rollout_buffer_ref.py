@@ -1,6 +1,8 @@
 """Host-only numpy restatement of k_rollout_gather (csrc/meshenv_rollout.h) and of DeviceRolloutBuffer.get: SB3 2.x's
 ``RolloutBuffer.swap_and_flatten`` + ``_get_samples`` over the histories ``collect_rollout`` leaves in [T][n] order, with the
-kernel's rule for an index that is no row (the row is NaN in every field; the branch no GPU test enters).  Shared by
+kernel's rule for an index that is no row (the row is NaN in every field and nothing is read for it; the index is compared as
+the 64-bit value it is, BEFORE it is narrowed: 2^32 + 3 is no row, not row 3.  tests/test_gpu_rollout_buffer.py enters the
+branch with int32 and int64 permutations, ``narrowed_first`` is the wrong kernel it would tell).  Shared by
 tests/test_rollout_buffer_cpu.py and tests/test_gpu_rollout_buffer.py; nothing here touches a device."""
 from __future__ import annotations
 
@@ -57,6 +59,16 @@ def gather(out, perm):
         y[~ok] = np.nan
         res[f] = y
     return res
+
+
+def narrowed_first(perm):
+    """The indices a kernel would see that cut an int64 index down to its low 32 bits (as a signed int32) before comparing it
+    with the number of rows: the counter-example of the GPU test's int64 cases."""
+    return np.asarray(perm).astype(np.int64).astype(np.uint64).astype(np.uint32).view(np.int32).astype(np.int64)
+
+
+NOT_ROWS_32 = (-1, None, 2 ** 31 - 1)                                   # None stands for ``rows`` itself
+NOT_ROWS_64 = NOT_ROWS_32 + (2 ** 32 + 3, -2 ** 32 + 5, 2 ** 63 - 1)  # the fourth and fifth alias rows 3 and 5 when narrowed first
 
 
 def bounds(rows, batch_size):

@@ -7,9 +7,16 @@ float32 values.
 train/ent_coef (learned).  The device writes ``expf(log_ent_coef)`` per step; the reference is the float64 ``exp`` of the
 twin's float32 ``log_ent_coef`` before that step, rounded to float32.  The margin is 1.5 ulp of the reference: 1 ulp for the
 device's ``expf`` (the figure of ROCm's HIP math accuracy table for expf) plus half an ulp for the reference's own rounding.
-Single steps are read through calls of one gradient step, whose mean is that step's value; the first is exp(0) = 1 exactly."""
+Single steps are read through calls of one gradient step, whose mean is that step's value; the first is exp(0) = 1 exactly.
+
+Past the toy sizes.  k_offpolicy_finish is one workgroup of 1024 threads over steps t, t + 1024, ...: the K = 1027 cases give
+threads 0, 1 and 2 a second trip, for TD3 with policy_delay 3 entered at _n_updates = 4 (the actor steps are k = 1, 4, ...: a
+phase that is neither 0 nor the parity of a delay of 2) and for SAC with a learned coefficient, once with all minibatches
+drawn at once and once with sample_chunk 1000, whose seam is not the 1024 seam.  Three calls of K = 4 with policy_delay 3 move
+the phase from call to call: 2, 1, 0."""
 import ctypes as C
 import math
+import time
 
 import numpy as np
 import pytest
@@ -179,6 +186,94 @@ def test_td3_one_step_from_an_even_n_updates_leaves_the_actor_alone(buf):
     finally:
         tr.close()
         comp.close()
+
+
+def test_td3_delay_3_moves_the_actor_phase_from_call_to_call(buf, fixed_batch):
+    """Three calls of K = 4 from _n_updates = 0: the actor steps fall at k = 2, then k = 1, then k = 0 and 3."""
+    import torch
+    m, tw, tr, comp = _pair("td3", buf, policy_delay=3)
+    out = []
+    try:
+        for call, want in enumerate(([2], [1], [0, 3])):
+            c0 = tr.counter
+            logs = tr.train(4, batch_size=65, seed=SEED)
+            recs = comp.train(4, batch_size=65, seed=SEED, counter=c0)
+            assert [k for k, r in enumerate(recs) if "actor_loss" in r] == want
+            out.append(_check_logs(logs, recs, m, "td3", False))
+            assert TR.differing(m, tw) == [], f"after call {call}"
+        assert [g["actor_steps"] for g in out] == [1, 1, 2] and [g["polyak_updates"] for g in out] == [1, 1, 2]
+        assert m._n_updates == 12 and tr.calls == 3
+        assert float(m.actor.optimizer.state[TR.actor_params(m)[0]]["step"]) == 4
+        assert float(m.critic.optimizer.state[TR.critic_params(m)[0]]["step"]) == 12
+        s, noise = fixed_batch
+        y, yt = tr.td.target(s, noise=noise), comp.td.target(s, noise=noise)
+        assert torch.equal(y.view(torch.int32), yt.view(torch.int32)) and bool(torch.isfinite(y).all())
+    finally:
+        tr.close()
+        comp.close()
+
+
+def _all_finite(torch, m):
+    return all(bool(torch.isfinite(x.detach()).all()) for x in TR.state(m).values())
+
+
+def test_td3_delay_3_1027_steps_from_phase_1(buf, fixed_batch):
+    """One call of K = 4 first (_n_updates = 4), then one of K = 1027: the actor steps are k = 1, 4, ..., 1024, 342 of them, and
+    steps 1024, 1025 and 1026 are the second trip of threads 0, 1 and 2 of k_offpolicy_finish."""
+    import torch
+    t0 = time.perf_counter()
+    m, tw, tr, comp = _pair("td3", buf, policy_delay=3)
+    try:
+        tr.train(4, batch_size=16, seed=SEED)
+        comp.train(4, batch_size=16, seed=SEED, counter=0)
+        assert TR.differing(m, tw) == [] and tr.counter == 4
+        logs = tr.train(1027, batch_size=16, seed=SEED)
+        recs = comp.train(1027, batch_size=16, seed=SEED, counter=4)
+        assert [k for k, r in enumerate(recs) if "actor_loss" in r] == list(range(1, 1027, 3))
+        got = _check_logs(logs, recs, m, "td3", False)
+        assert got["actor_steps"] == 342 and got["polyak_updates"] == 342 and m._n_updates == 1031
+        assert TR.differing(m, tw) == []
+        assert float(m.actor.optimizer.state[TR.actor_params(m)[0]]["step"]) == 343
+        assert float(m.critic.optimizer.state[TR.critic_params(m)[0]]["step"]) == 1031
+        s, noise = fixed_batch
+        y, yt = tr.td.target(s, noise=noise), comp.td.target(s, noise=noise)
+        assert torch.equal(y.view(torch.int32), yt.view(torch.int32)) and bool(torch.isfinite(y).all()) and _all_finite(torch, m)
+    finally:
+        tr.close()
+        comp.close()
+    print(f"wall time {time.perf_counter() - t0:.2f} s")
+
+
+def test_sac_1027_steps_with_the_chunk_seam_off_the_1024_seam(buf, fixed_batch):
+    """SAC with a learned coefficient, target_update_interval 2, K = 1027, B = 16: one call that draws all 1027 minibatches at
+    once and, on a fresh model, one with sample_chunk 1000; both against ONE run of the composition."""
+    import torch
+    t0 = time.perf_counter()
+    m, tw, tr, comp = _pair("sac", buf, target_update_interval=2)
+    m2 = TR.model("sac", target_update_interval=2)
+    from reinforcementlearning4meshgeneration_amd import FusedOffPolicyTrain
+    tr2 = FusedOffPolicyTrain.from_sb3(m2, buf)
+    try:
+        assert TR.differing(m, m2) == []                     # the same seed: the same model
+        logs = tr.train(1027, batch_size=16, seed=SEED)
+        logs2 = tr2.train(1027, batch_size=16, seed=SEED, sample_chunk=1000)
+        recs = comp.train(1027, batch_size=16, seed=SEED, counter=0)
+        assert tr._work[0] == 1027 and tr2._work[0] == 1000
+        for model, lg in ((m, logs), (m2, logs2)):
+            got = _check_logs(lg, recs, model, "sac", True)
+            assert got["actor_steps"] == 1027 and got["polyak_updates"] == 514 and model._n_updates == 1027
+            assert _all_finite(torch, model)
+        assert TR.differing(m, m2) == [] and TR.differing(m, tw) == [] and TR.differing(m2, tw) == []
+        assert torch.equal(logs.device.view(torch.int64), logs2.device.view(torch.int64))
+        assert float(m.ent_coef_optimizer.state[m.log_ent_coef]["step"]) == 1027
+        s, noise = fixed_batch
+        ys = [h.td.target(s, noise=noise).clone() for h in (tr, tr2, comp)]
+        assert all(torch.equal(ys[0].view(torch.int32), y.view(torch.int32)) for y in ys[1:]) and bool(torch.isfinite(ys[0]).all())
+    finally:
+        tr.close()
+        tr2.close()
+        comp.close()
+    print(f"wall time {time.perf_counter() - t0:.2f} s")
 
 
 # ----------------------------------------------------------------------------------------------------------- the queue

@@ -15,7 +15,16 @@ float32 at the three values the test reaches (they differ by an ulp of float64 a
 whose exponential lies within 2^-29 of a float32 rounding boundary).
 
 "The packed weights of the refreshed FusedPolicy" are compared through what they compute: actions, log_prob and value of
-``forward`` on every row of the rollout, against the twin's and against a FusedPolicy packed afresh from the stepped model."""
+``forward`` on every row of the rollout, against the twin's and against a FusedPolicy packed afresh from the stepped model.
+
+Past the toy sizes (sections 7 and 8 below).  k_train_finish is one workgroup of 1024 threads over rows t, t + 1024, ...: (32, 32)
+is exactly 1024 rows, A2C's (25, 41) is 1025 (one minibatch of 65 tiles on 64 workgroups), PPO's (31, 67) is 2077 (130
+minibatches per epoch, the last of 13 rows, K = 260 gates and tally entries per train()).  With values = returns / 2 the
+difference d = returns - values is returns / 2 exactly, so explained_variance is 0.75 over ANY subset of the rows and cannot
+tell a kernel that drops the rows past 1024; each of these sizes is therefore also run with returns = 1000 + N(0, 1)
+(tests/test_onpolicy_train_cpu.py states the counter-example).  The stop state between calls: a train() that stops at its
+first minibatch between two that do not, a stop at the second minibatch of the second epoch, a 4-row train() after a 35-row one
+on the same trainer."""
 import math
 
 import numpy as np
@@ -29,14 +38,14 @@ pytestmark = pytest.mark.gpu
 _CACHE = {}
 
 
-def _histories(kind, T, n, constant_returns=False):
+def _histories(kind, T, n, constant_returns=False, offset=0.0):
     """The rollout on the device, built once per shape; log_prob is the initial policy's own."""
     import torch
 
     from reinforcementlearning4meshgeneration_amd import FusedPPOGrad
-    key = (kind, T, n, constant_returns)
+    key = (kind, T, n, constant_returns, offset)
     if key not in _CACHE:
-        host = TR.host_histories(kind, T, n, constant_returns)
+        host = TR.host_histories(kind, T, n, constant_returns, offset=offset)
         out = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
         model, _ = S.model(kind, "cuda")
         pg = FusedPPOGrad.from_sb3(model)
@@ -105,9 +114,9 @@ def _assert_same_bits(torch, a, b, out, what):
     fresh.close()
 
 
-def _both(torch, kind, T, n, target_kl=None, trains=1, constant_returns=False):
+def _both(torch, kind, T, n, target_kl=None, trains=1, constant_returns=False, offset=0.0):
     """(the train() side, the composed side, the logs of the last train(), the composition's last result, the rollout)."""
-    out = _histories(kind, T, n, constant_returns)
+    out = _histories(kind, T, n, constant_returns, offset)
     perms = _perms(torch, kind, T * n)
     a, b = Side(kind, target_kl), Side(kind, target_kl)
     logs = ref = None
@@ -118,15 +127,18 @@ def _both(torch, kind, T, n, target_kl=None, trains=1, constant_returns=False):
     return a, b, logs, ref, out
 
 
-def _composition_kls(torch):
-    """approx_kl per minibatch of the composition without a target_kl on the (3, 11) PPO rollout: recorded once."""
-    if "kls" not in _CACHE:
+def _composition_kls(torch, T=3, n=11, with_params=False):
+    """approx_kl per minibatch of the composition without a target_kl on the (T, n) PPO rollout, and the parameters it leaves:
+    recorded once per shape."""
+    key = ("kls", T, n)
+    if key not in _CACHE:
         side = Side("ppo")
-        out = _histories("ppo", 3, 11)
-        ref = TR.compose(side.model, side.pg, side.fo, side.rb, side.fp, out, _perms(torch, "ppo", 33))
-        _CACHE["kls"] = [float(r["approx_kl"]) for r in ref["records"]]
+        out = _histories("ppo", T, n)
+        ref = TR.compose(side.model, side.pg, side.fo, side.rb, side.fp, out, _perms(torch, "ppo", T * n))
+        _CACHE[key] = ([float(r["approx_kl"]) for r in ref["records"]], [p.detach().clone() for p in side.params])
+        torch.cuda.synchronize()
         side.close()
-    return _CACHE["kls"]
+    return _CACHE[key] if with_params else _CACHE[key][0]
 
 
 # ----------------------------------------------------------------------------------------------------------- 1. bits
@@ -332,3 +344,208 @@ def test_refusals_before_any_launch():
         tr.train(out, _perms(torch, "ppo", 33))
     assert tr.calls == 0 and all(len(side.opt.state[p]) == 0 or float(side.opt.state[p]["step"]) == 0.0 for p in side.params)
     side.close()
+
+
+# ----------------------------------------------------------------------------------------------------------- 7. rows past 1024
+def _mean_bound(x):
+    n = len(x)
+    return math.fsum(x) / n, (n + 1) * 2.0 ** -53 * math.fsum(abs(y) for y in x) / n
+
+
+def _assert_means(v, recs, last_epoch):
+    """The five means against math.fsum of the composition's records (approx_kl: the last epoch's), loss and grad_norm the last
+    record's."""
+    for key, name, rows in (("policy_gradient_loss", "policy_loss", recs), ("value_loss", "value_loss", recs),
+                            ("entropy_loss", "entropy_loss", recs), ("clip_fraction", "clip_fraction", recs), ("approx_kl", "approx_kl", last_epoch)):
+        mean, bound = _mean_bound([float(r[name]) for r in rows])
+        print(f"{key}: device {v[key]!r}, fsum / n {mean!r} over {len(rows)}, bound {bound:.3e}")
+        assert abs(v[key] - mean) <= bound, key
+    assert v["loss"] == float(recs[-1]["loss"]) and v["grad_norm"] == float(recs[-1]["grad_norm"])
+
+
+def _assert_explained_variance(v, out, rows):
+    values, returns = out["value"].cpu().numpy().reshape(-1), out["returns"].cpu().numpy().reshape(-1)
+    assert len(values) == rows
+    f64, var_d, var_r = TR.explained_variance_f64(values, returns)
+    f32 = float(TR.explained_variance_ref(values, returns))
+    got = v["explained_variance"]
+    print(f"explained_variance at {rows} rows: device {got!r}, fp64 {f64!r}, numpy float32 {f32!r}, |device - fp64| {abs(got - f64):.3e}, "
+          f"var_d / var_r {var_d / var_r:.4f}")
+    assert 0.1 < var_d / var_r < 10.0
+    assert abs(got - f64) <= 1e-12 * max(1.0, var_d / var_r)
+    assert abs(got - f32) <= 8 * rows * 2.0 ** -24 * (1 + var_d / var_r)
+
+
+def _explained_variance_with_an_offset(torch, kind, T, n):
+    """One train() on the same shape with returns = 1000 + N(0, 1): the rollout on which a dropped row shows."""
+    out = _histories(kind, T, n, offset=1000.0)
+    side = Side(kind)
+    logs = side.trainer().train(out, _perms(torch, kind, T * n))
+    _assert_explained_variance(logs.values(), out, T * n)
+    assert all(bool(torch.isfinite(p).all()) for p in side.params)
+    side.close()
+
+
+def test_ppo_2077_rows_260_minibatches_two_trains():
+    """(31, 67): every thread of k_train_finish takes two or three trips, the tally and the stop chain run over 260 minibatches,
+    twice on the same handle."""
+    import time
+
+    import torch
+    t0 = time.perf_counter()
+    a, b, logs, ref, out = _both(torch, "ppo", 31, 67, trains=2)
+    v, recs = logs.values(), ref["records"]
+    assert len(recs) == 260 and ref["steps"] == 260 and ref["n_updates"] == 2 and len(ref["last_epoch_kl"]) == 130
+    assert (v["steps_applied"], v["epochs_run"], v["minibatches_evaluated"]) == (260, 2, 260)
+    assert all(float(a.opt.state[p]["step"]) == 520.0 for p in a.params) and a.model._n_updates == 4
+    print()
+    _assert_means(v, recs, recs[130:])
+    _assert_explained_variance(v, out, 2077)
+    assert v["std"] == TR.std_ref(a.params[-1].detach().cpu().numpy())
+    a.close(); b.close()
+    print(f"wall time {time.perf_counter() - t0:.2f} s")
+
+
+def test_ppo_2077_rows_with_returns_around_1000():
+    import torch
+    a, b, logs, ref, out = _both(torch, "ppo", 31, 67, offset=1000.0)
+    assert float(out["returns"].mean()) > 999.0 and logs.values()["steps_applied"] == 260
+    print()
+    _assert_explained_variance(logs.values(), out, 2077)
+    assert all(bool(torch.isfinite(p).all()) for p in a.params)
+    a.close(); b.close()
+
+
+def test_ppo_2077_rows_a_target_kl_that_never_triggers_leaves_the_bits_of_none():
+    """target_kl = twice the largest approx_kl the composition records without one: each of the 260 gates compares against a
+    finite limit and passes."""
+    import torch
+    kls, params = _composition_kls(torch, 31, 67, with_params=True)
+    assert len(kls) == 260 and max(kls) > 0.0 and all(math.isfinite(k) for k in kls)
+    target = 2.0 * max(kls)
+    a, b, logs, ref, out = _both(torch, "ppo", 31, 67, target_kl=target)
+    v = logs.values()
+    assert (v["steps_applied"], v["epochs_run"], v["minibatches_evaluated"]) == (260, 2, 260) and ref["steps"] == 260
+    assert all(torch.equal(p, q) for p, q in zip(a.params, params))               # the bits of the run without a target_kl
+    assert all(float(a.opt.state[p]["step"]) == 260.0 for p in a.params) and a.model._n_updates == 2
+    a.close(); b.close()
+
+
+def test_a2c_1025_rows_one_minibatch_of_65_tiles():
+    import torch
+    a, b, logs, ref, out = _both(torch, "a2c", 25, 41)
+    v, rec = logs.values(), ref["records"]
+    assert len(rec) == 1 and (v["steps_applied"], v["epochs_run"], v["minibatches_evaluated"]) == (1, 1, 1)
+    rec = rec[0]
+    for key, name in (("policy_gradient_loss", "policy_loss"), ("value_loss", "value_loss"), ("entropy_loss", "entropy_loss"),
+                      ("clip_fraction", "clip_fraction"), ("approx_kl", "approx_kl"), ("loss", "loss"), ("grad_norm", "grad_norm")):
+        assert v[key] == float(rec[name]), key                                     # a mean over one record is the record
+    r = logs.read()
+    assert r["train/policy_loss"] == float(rec["policy_loss"]) and r["train/n_updates"] == 1 and "train/clip_range" not in r
+    print()
+    _assert_explained_variance(v, out, 1025)
+    assert "square_avg" in a.opt.state[a.params[0]] and float(a.opt.state[a.params[0]]["step"]) == 1.0     # the RMSprop program
+    a.close(); b.close()
+    _explained_variance_with_an_offset(torch, "a2c", 25, 41)
+
+
+def test_ppo_exactly_1024_rows():
+    """(32, 32): every thread of k_train_finish has exactly one row, none a second."""
+    import torch
+    out = _histories("ppo", 32, 32)
+    side = Side("ppo")
+    logs = side.trainer().train(out, _perms(torch, "ppo", 1024))
+    assert logs.values()["minibatches_evaluated"] == 128
+    print()
+    _assert_explained_variance(logs.values(), out, 1024)
+    side.close()
+    _explained_variance_with_an_offset(torch, "ppo", 32, 32)
+
+
+# ----------------------------------------------------------------------------------------------------------- 8. the stop state across calls
+def _snapshot(torch, side, out):
+    obs = out["obs"].reshape(-1, 18)
+    eps = torch.linspace(-1.5, 1.5, obs.shape[0] * 3, device="cuda").reshape(-1, 3)
+    fwd = {k: x.clone() for k, x in side.fp.forward(obs, eps).items() if k in ("actions", "log_prob", "value")}
+    state = [{k: (float(x) if k == "step" else x.detach().clone()) for k, x in side.opt.state[p].items()} for p in side.params]
+    return [p.detach().clone() for p in side.params], state, fwd, side.model._n_updates
+
+
+def test_a_train_that_stops_at_its_first_minibatch_then_one_that_resumes():
+    """train() 1 without a target_kl (the optimiser state exists, the parameters have moved, so minibatch 0 of the next call has
+    approx_kl > 0); train() 2 with a target_kl 2^-10 under that kl / 1.5: it stops before any step; train() 3 without one: six
+    steps, from a stop chain whose every flag train() 2 left set."""
+    import torch
+    out, perms = _histories("ppo", 3, 11), _perms(torch, "ppo", 33)
+    a, b, c = Side("ppo"), Side("ppo"), Side("ppo")
+    a.trainer().train(out, perms)
+    for side in (b, c):
+        TR.compose(side.model, side.pg, side.fo, side.rb, side.fp, out, perms)
+    _assert_same_bits(torch, a, b, out, "train 1")
+    kl0 = float(TR.compose(c.model, c.pg, c.fo, c.rb, c.fp, out, perms)["records"][0]["approx_kl"])     # the scout: a third twin
+    c.close()
+    assert kl0 > 0.0
+    target = kl0 / 1.5 * (1 - 2.0 ** -10)
+    assert kl0 > 1.5 * target
+    params, state, fwd, n_updates = _snapshot(torch, a, out)
+    assert n_updates == 2 and all(st["step"] == 6.0 for st in state)
+    a.model.target_kl = b.model.target_kl = target
+    logs = a.trainer().train(out, perms)
+    ref = TR.compose(b.model, b.pg, b.fo, b.rb, b.fp, out, perms)
+    v, rec = logs.values(), ref["records"]
+    assert ref["steps"] == 0 and ref["n_updates"] == 1 and len(rec) == 1 and float(rec[0]["approx_kl"]) == kl0
+    assert (v["steps_applied"], v["epochs_run"], v["minibatches_evaluated"]) == (0, 1, 1)
+    now_params, now_state, now_fwd, now_updates = _snapshot(torch, a, out)
+    assert all(torch.equal(p, q) for p, q in zip(params, now_params))
+    for st, now in zip(state, now_state):
+        assert set(st) == set(now) and st["step"] == now["step"] == 6.0
+        assert all(torch.equal(st[k], now[k]) for k in st if k != "step")
+    assert now_updates == n_updates + 1 and logs.read()["train/n_updates"] == 3
+    assert all(torch.equal(fwd[k], now_fwd[k]) for k in fwd)
+    for key, name in (("policy_gradient_loss", "policy_loss"), ("value_loss", "value_loss"), ("entropy_loss", "entropy_loss"),
+                      ("clip_fraction", "clip_fraction"), ("approx_kl", "approx_kl"), ("loss", "loss"), ("grad_norm", "grad_norm")):
+        assert v[key] == float(rec[0][name]), key
+    _assert_same_bits(torch, a, b, out, "train 2, stopped at its first minibatch")
+    a.model.target_kl = b.model.target_kl = None
+    logs = a.trainer().train(out, perms)
+    ref = TR.compose(b.model, b.pg, b.fo, b.rb, b.fp, out, perms)
+    v = logs.values()
+    assert (v["steps_applied"], v["epochs_run"], v["minibatches_evaluated"]) == (6, 2, 6) and ref["steps"] == 6
+    print()
+    _assert_means(v, ref["records"], ref["records"][3:])
+    _assert_same_bits(torch, a, b, out, "train 3")
+    assert all(float(a.opt.state[p]["step"]) == 12.0 for p in a.params) and a.model._n_updates == 5
+    assert not any(torch.equal(p, q) for p, q in zip(a.params, params))
+    a.close(); b.close()
+
+
+def test_early_stop_at_the_second_minibatch_of_the_second_epoch():
+    """j = 4: the per-epoch KL sum, restarted at minibatch 3, holds two entries when the stop falls.  Permutation seed 7 serves:
+    minibatch 4's approx_kl is 15 % above minibatch 3's on CPU torch (tests/test_onpolicy_train_cpu.py), the largest before it."""
+    import torch
+    kls = _composition_kls(torch)
+    j = TR.first_exceeding(kls, 4)
+    print(f"\napprox_kl per minibatch {kls}; j = {j}")
+    assert j is not None and j >= 4, kls
+    _stop_case(torch, j, 3)
+
+
+def test_a_short_train_after_a_long_one_on_the_same_trainer():
+    """(5, 7): 35 rows, K = 6; then (2, 2): 4 rows, one minibatch per epoch, K = 2.  The second call's tally starts afresh at
+    its minibatch 0 and its stop chain is two flags long."""
+    import torch
+    a, b = Side("ppo"), Side("ppo")
+    long_out, short_out = _histories("ppo", 5, 7), _histories("ppo", 2, 2)
+    for out, rows, K in ((long_out, 35, 6), (short_out, 4, 2)):
+        perms = _perms(torch, "ppo", rows)
+        logs = a.trainer().train(out, perms)
+        ref = TR.compose(b.model, b.pg, b.fo, b.rb, b.fp, out, perms)
+        _assert_same_bits(torch, a, b, out, f"{rows} rows")
+        v, recs = logs.values(), ref["records"]
+        assert len(recs) == K and (v["steps_applied"], v["epochs_run"], v["minibatches_evaluated"]) == (K, 2, K)
+        print()
+        _assert_means(v, recs, recs[K // 2:])
+    assert v["approx_kl"] == float(recs[1]["approx_kl"])                         # the last epoch's one record
+    _assert_explained_variance(v, short_out, 4)
+    assert all(float(a.opt.state[p]["step"]) == 8.0 for p in a.params) and a.model._n_updates == 4 and a.tr.calls == 2
+    a.close(); b.close()

@@ -2,8 +2,13 @@
 tests/rollout_buffer_ref.py.  The outputs are copies, so every comparison is ``torch.equal``: no tolerance.
 
 Shapes (T, n) = (1, 1), (3, 5), (7, 37), (32, 33): rows 1, 15, 259 and 1056, below and across a 256-thread workgroup and a
-1024-float chunk of every field (the 1056 x 18 observations span 19 chunks).  No test feeds the kernel an index that is no
-row: that branch is covered by the host restatement alone (tests/test_rollout_buffer_cpu.py)."""
+1024-float chunk of every field (the 1056 x 18 observations span 19 chunks).
+
+An index that is no row.  ``FusedOnPolicyTrain.train(perms=...)`` checks the shape and dtype of a caller's permutations and
+``get`` checks values only on request, so k_rollout_gather's own guard (rg_source) is what stands between such an index and
+an out-of-bounds read: it compares the index as 64 bits before narrowing it and returns -1, for which nothing is read and NaN
+is written.  ``test_an_index_that_is_no_row_gives_a_nan_row`` enters that branch at (7, 37) with int32 and int64 permutations,
+through both variants of the observation copy."""
 import numpy as np
 import pytest
 
@@ -107,6 +112,46 @@ def test_repeat_reuse_own_permutation_and_a_side_stream(buffer):
     rb.load(small)
     mb = next(iter(rb.get(None, perm=torch.arange(15, device="cuda", dtype=torch.int32))))
     assert mb.actions.shape == (15, 3) and torch.equal(mb.advantages, _flat(torch, small)["advantages"])
+
+
+@pytest.mark.parametrize("dtype", ["int32", "int64"])
+def test_an_index_that_is_no_row_gives_a_nan_row(dtype, buffer):
+    """(7, 37), 259 rows, minibatches of 64, the value check off.  int32: -1, rows and 2^31 - 1; int64: the same and 2^32 + 3,
+    -2^32 + 5 (rows 3 and 5 to a kernel that narrowed first: wrong data where NaN belongs) and 2^63 - 1.  Those rows are NaN in
+    every field, every other row has the bits of the restatement."""
+    import torch
+    rb, (T, n) = buffer, (7, 37)
+    rows = T * n
+    host = RB.rollout(T, n, seed=5)
+    out = _dev(host)
+    rb.load(out)
+    bad = [rows if b is None else b for b in (RB.NOT_ROWS_32 if dtype == "int32" else RB.NOT_ROWS_64)]
+    at = [10, 100, 200, 63, 64, 258][:len(bad)]                      # three minibatches, both ends of one, the last row
+    perm = np.random.default_rng(rows).permutation(rows).astype(dtype)
+    perm[at] = bad
+    assert perm.tolist().count(3) == 1 and perm.tolist().count(5) == 1          # rows 3 and 5 are also gathered where they belong
+    want = RB.gather(host, perm)
+    dev_perm = torch.from_numpy(perm).cuda()
+    for variant in (0, 1):
+        if variant == 0:
+            got = list(rb.get(64, perm=dev_perm))                   # check=False: nothing looks at the values first
+            assert [len(mb.returns) for mb in got] == [64, 64, 64, 64, 3]
+            fields = [torch.cat([getattr(mb, f) for mb in got]) for f in RB.FIELDS]
+        else:
+            for x in rb._out:
+                x.fill_(-7.0)
+            rb._gather(dev_perm, 1)                                 # the observations in 8-byte pieces
+            fields = rb._out
+        for f, x in zip(RB.FIELDS, fields):
+            x = x.cpu().numpy()
+            assert np.isnan(x[at]).all(), (f, variant)
+            keep = np.delete(np.arange(rows), at)
+            assert np.array_equal(x[keep], want[f][keep]) and np.isfinite(x[keep]).all(), (f, variant)
+            assert np.array_equal(np.isnan(x), np.isnan(want[f])), (f, variant)
+    for k, v in host.items():                                       # the fields of out are not written
+        assert np.array_equal(out[k].cpu().numpy(), v), k
+    with pytest.raises(ValueError, match=r"perm\[10\] = -1 is not a row"):
+        rb.get(64, perm=dev_perm, check=True)
 
 
 def test_check_refuses_an_index_that_is_no_row_before_any_launch(buffer):

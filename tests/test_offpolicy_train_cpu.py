@@ -1,11 +1,14 @@
 """CPU: the host half of ``FusedOffPolicyTrain`` (reinforcementlearning4meshgeneration_amd/offpolicy_train.py): the two
-schedules against the transcription of SB3's loops (tests/offpolicy_train_ref.py), the scalar sets of the critic and the actor
+schedules against the transcription of SB3's loops (tests/offpolicy_train_ref.py), the restatement of ``k_offpolicy_finish``'s
+summation order and actor-step selector past 1024 steps, the scalar sets of the critic and the actor
 steps against successive ``OptimStepSpec.commit`` preparations, the scheduled learning rate, the hyper-parameters, every
 refusal, the draw counter, and the packaging."""
+import math
 import os
 import re
 import types
 
+import numpy as np
 import pytest
 
 import offpolicy_train_ref as TR
@@ -52,6 +55,83 @@ def test_td3_two_calls_of_three_step_the_actor_at_updates_2_4_6():
     first = T.td3_actor_schedule(3, 2, 0)
     second = T.td3_actor_schedule(3, 2, 3)
     assert first == [False, True, False] and second == [True, False, True]
+
+
+FINISH_K = (1, 5, 1024, 1025, 1027, 2050)
+
+
+def _slots(K, seed=0):
+    """[K][4] float32 of the sizes the four logged values have: critic_loss, actor_loss, ent_coef_loss, ent_coef."""
+    rng = np.random.default_rng(seed + K)
+    x = rng.standard_normal((K, 4)) * [0.3, 2.0, 0.5, 0.05] + [1.0, -3.0, 0.2, 0.9]
+    return x.astype(np.float32)
+
+
+@pytest.mark.parametrize("K", FINISH_K)
+def test_k_offpolicy_finishs_order_keeps_the_sum_bound_for_every_phase_and_the_first_1024_steps_alone_do_not(K):
+    """finish_order_means against math.fsum of the same float32 values within mean_and_bound, TD3 with policy_delay 1, 2, 3 and
+    every _n_updates that gives another phase, SAC with a learned and a fixed coefficient.  The selected steps are those of
+    SB3's schedules.  A kernel that read steps 0 .. 1023 only misses the bound at every K above 1024."""
+    T = _T()
+    slots = _slots(K)
+    critic = [float(v) for v in slots[:, 0]]
+    for delay in (1, 2, 3):
+        phases = set()
+        for n_updates in range(delay):
+            steps, _ = TR.td3_steps(K, delay, n_updates)
+            flags = [u for _, u in steps]
+            assert flags == T.td3_actor_schedule(K, delay, n_updates)
+            want = [k for k, u in enumerate(flags) if u]
+            phase, period = TR.phase_period(flags)
+            assert phase == ((delay - 1 - n_updates) % delay if want else K)
+            phases.add(phase)
+            for ph, per in {(phase, period), (phase, delay) if want else (phase, period)}:
+                got = TR.finish_order_means(slots, K, ph, per, TR.TD3)
+                assert got["steps"] == want, (K, delay, n_updates)
+                mean, bound = TR.mean_and_bound(critic)
+                assert abs(got["critic_loss"] - mean) <= bound
+                if want:
+                    mean, bound = TR.mean_and_bound([float(slots[k, 1]) for k in want])
+                    assert abs(got["actor_loss"] - mean) <= bound
+                else:
+                    assert math.isnan(got["actor_loss"])
+                assert math.isnan(got["ent_coef_loss"]) and math.isnan(got["ent_coef"]) and got["last_critic_loss"] == critic[-1]
+        assert phases == (set(range(delay)) if K >= delay else set(range(K)) | {K})          # every phase below the period
+    for interval in (1, 2):
+        flags = [True for _ in TR.sac_steps(K, interval)]                             # SAC steps the actor at every step
+        phase, period = TR.phase_period(flags)
+        assert phase == 0 and period == (1 if K > 1 else K)
+        got = TR.finish_order_means(slots, K, phase, period, TR.SAC_LEARNED)
+        assert got["steps"] == [k for k, _ in TR.sac_steps(K, interval)]
+        for key, col in (("critic_loss", 0), ("actor_loss", 1), ("ent_coef_loss", 2), ("ent_coef", 3)):
+            mean, bound = TR.mean_and_bound([float(v) for v in slots[:, col]])
+            assert abs(got[key] - mean) <= bound, key
+    fixed = TR.finish_order_means(slots, K, 0, 1, TR.SAC_FIXED, ent_coef=0.1)
+    assert fixed["ent_coef"] == float(np.float32(0.1)) and math.isnan(fixed["ent_coef_loss"])
+    # the counter-example
+    first = TR.finish_order_means(slots, K, 1 % K, 3, TR.TD3, trips=1)
+    whole = TR.finish_order_means(slots, K, 1 % K, 3, TR.TD3)
+    if K <= TR.FINISH_THREADS:
+        assert all(first[key] == whole[key] or (math.isnan(first[key]) and math.isnan(whole[key])) for key in whole)
+    else:
+        for key, vals in (("critic_loss", critic), ("actor_loss", [float(slots[k, 1]) for k in whole["steps"]])):
+            mean, bound = TR.mean_and_bound(vals)
+            assert abs(first[key] - mean) > 1e-4 > bound, (key, first[key], mean)
+
+
+def test_a_phase_at_or_past_k_selects_nothing():
+    slots = _slots(5)
+    for phase, period in ((5, 1), (5, 3), (7, 2)):
+        got = TR.finish_order_means(slots, 5, phase, period, TR.TD3)
+        assert got["steps"] == [] and math.isnan(got["actor_loss"]) and not math.isnan(got["critic_loss"])
+        got = TR.finish_order_means(slots, 5, phase, period, TR.SAC_LEARNED)
+        assert math.isnan(got["actor_loss"]) and math.isnan(got["ent_coef_loss"]) and not math.isnan(got["ent_coef"])
+    assert TR.phase_period([False] * 5) == (5, 1) and TR.phase_period([False, False, True, False]) == (2, 4)
+    # delay 3 over three calls of four: phases 2, 1, 0
+    T = _T()
+    assert [TR.phase_period(T.td3_actor_schedule(4, 3, n)) for n in (0, 4, 8)] == [(2, 4), (1, 4), (0, 3)]
+    assert TR.phase_period(T.td3_actor_schedule(1027, 3, 4)) == (1, 3) and sum(T.td3_actor_schedule(1027, 3, 4)) == 342
+    assert sum(T.sac_polyak_schedule(1027, 2)) == 514
 
 
 # ----------------------------------------------------------------------------------------------------------- 2. scalar sets
@@ -104,7 +184,6 @@ def test_scalar_sets_equal_successive_commits_bit_for_bit(kind, loaded):
 
 @pytest.mark.parametrize("kind", ["sac", "td3"])
 def test_the_scheduled_lr_is_in_every_set_of_every_optimiser(kind):
-    import numpy as np
     T = _T()
     from reinforcementlearning4meshgeneration_amd.optim_step import OptimStepSpec, adam_scalars
     m = _ready(kind, lr_schedule=lambda progress: 1e-3 * progress, _current_progress_remaining=0.25)

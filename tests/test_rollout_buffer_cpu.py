@@ -113,6 +113,27 @@ def test_an_index_that_is_no_row_gives_a_nan_row_and_reads_nothing():
     assert all(np.isfinite(x).all() for x in good.values())
 
 
+def test_the_gpu_tests_int64_cases_tell_a_kernel_that_narrows_before_it_compares():
+    """2^32 + 3 and -2^32 + 5 are no rows; cut to 32 bits first they are rows 3 and 5, and 2^63 - 1 becomes -1."""
+    T, n = 7, 37
+    rows = T * n
+    out = RB.rollout(T, n)
+    perm = np.random.default_rng(rows).permutation(rows).astype(np.int64)
+    at = [10, 100, 200, 63, 64, 258]
+    bad = [rows if b is None else b for b in RB.NOT_ROWS_64]
+    perm[at] = bad
+    assert RB.narrowed_first(bad).tolist() == [-1, rows, 2 ** 31 - 1, 3, 5, -1]
+    good, wrong = RB.gather(out, perm), RB.gather(out, RB.narrowed_first(perm))
+    fl = RB.flat(out)
+    for f in RB.FIELDS:
+        assert np.isnan(good[f][at]).all() and np.isfinite(np.delete(good[f], at, axis=0)).all()
+        assert np.array_equal(wrong[f][63], fl[f][3]) and np.array_equal(wrong[f][64], fl[f][5])       # wrong data, not NaN
+        assert np.isnan(wrong[f][[10, 100, 200, 258]]).all()
+    p32 = perm.copy()
+    p32[[63, 64, 258]] = [1, 2, 3]
+    assert np.array_equal(RB.narrowed_first(p32), p32)                        # what fits 32 bits is unchanged
+
+
 # ----------------------------------------------------------------------------------------------------------- the host half
 def _torch_out(T=3, n=5):
     return {k: torch.from_numpy(v) for k, v in RB.rollout(T, n).items()}
