@@ -5,6 +5,7 @@ streams and writes tests/golden/<name>.npz.  The fixtures are data only: domain 
 actions, and the reference's outputs/state after every step.
 
 usage: python oracle/gen_golden.py            (rewrites every fixture)
+       python oracle/gen_golden.py --smooth-only [smooth_xf_boundary0_dx1e6_s1 ...]    (the named smoothing fixtures)
 """
 from __future__ import annotations
 
@@ -216,9 +217,28 @@ SMOOTH_TRACES = [
 ]
 
 
-def main_smooth():
-    for name, dom, seed, T, every, iteration in SMOOTH_TRACES:
-        tr = H.record_smooth_trace(H.domain_points(dom), H.biased_actions(seed, T), every, iteration=iteration, max_v=4096)
+# The smoothers on scaled / shifted domains (x -> scale x + shift applied before the reference env is built; the
+# transforms of XF_TRACES): (fixture name, domain, seed, T, every, iteration cap, scale, (dx, dy)).  The 0.001 stop rule
+# is an absolute threshold on sum(x + y): scaled up the sweeps run longer, scaled down they collapse, and under a shift
+# of 1e8 the sum's ulp is of the threshold's order.  boundary16 shifted by (1e8, -1e8) is not here: its shoelace area
+# cancels and the reference divides by zero.
+XF_SMOOTH_TRACES = [
+    ("smooth_xf_boundary0_dx1e6_s1", "boundary0", 1, 400, 3, 400, 1.0, (1e6, 0.0)),
+    ("smooth_xf_boundary0_d1e8_s1", "boundary0", 1, 400, 3, 400, 1.0, (1e8, -1e8)),
+    ("smooth_xf_boundary0_x1em2_s1", "boundary0", 1, 400, 3, 400, 1e-2, (0.0, 0.0)),
+    ("smooth_xf_boundary0_x1e3_d1e6_s1", "boundary0", 1, 400, 3, 400, 1e3, (1e6, -1e6)),
+    ("smooth_xf_boundary16_x1e2_s1", "boundary16", 1, 400, 3, 400, 1e2, (0.0, 0.0)),
+    ("smooth_xf_boundary16_x1em2_s1", "boundary16", 1, 400, 3, 400, 1e-2, (0.0, 0.0)),     # every call stops after <= 2 sweeps
+    ("smooth_xf_boundary16_dx1e8_s1", "boundary16", 1, 400, 3, 400, 1.0, (1e8, 0.0)),      # the ring of xf_boundary16_dx1e8_s7
+]
+
+
+def main_smooth(only=()):
+    for name, dom, seed, T, every, iteration, *xf in SMOOTH_TRACES + XF_SMOOTH_TRACES:
+        if only and name not in only:
+            continue
+        pts = transform(H.domain_points(dom), *xf) if xf else H.domain_points(dom)
+        tr = H.record_smooth_trace(pts, H.biased_actions(seed, T), every, iteration=iteration, max_v=4096)
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **tr)
         print(f"{name}: {T} steps, {int(tr['valid'].sum())} valid, {int(tr['n_calls'])} smooth_pave calls, sweeps "
               f"{tr['call_sweeps'].tolist() if tr['n_calls'] else []}")
@@ -241,11 +261,26 @@ def odd_ring(n, radius):
              round(radius * (1 + 0.08 * math.sin(3 * k)) * math.sin(-2 * math.pi * k / n), 2)) for k in range(n)]
 
 
-def main_final_smooth():
-    for name, dom, kind, seed, T, iteration in FINAL_SMOOTH_TRACES:
+# finished meshes on transformed domains: (fixture name, domain, stream kind, seed, T, iteration cap, max calls, scale,
+# (dx, dy)).  RING13 ends on fronts of 5; star x 1e2 holds a call that stops at the 400-sweep cap.
+XF_FINAL_SMOOTH_TRACES = [
+    ("smoothfinal_xf_ring13_dx1e6_s4", "RING13", "biased", 4, 1500, 400, 12, 1.0, (1e6, 0.0)),
+    ("smoothfinal_xf_ring13_x1em2_s4", "RING13", "biased", 4, 1500, 400, 12, 1e-2, (0.0, 0.0)),
+    ("smoothfinal_xf_star_d1e8_s4", "star", "biased", 4, 1500, 400, 12, 1.0, (1e8, -1e8)),
+    ("smoothfinal_xf_star_x1e2_s4", "star", "biased", 4, 1500, 400, 12, 1e2, (0.0, 0.0)),
+]
+
+
+def main_final_smooth(only=()):
+    for name, dom, kind, seed, T, iteration, *xf in FINAL_SMOOTH_TRACES + XF_FINAL_SMOOTH_TRACES:
+        if only and name not in only:
+            continue
         acts = (H.uniform_actions if kind == "uniform" else H.biased_actions)(seed, T)
         pts = odd_ring(int(dom[4:]), 0.9 * int(dom[4:]) / 6) if dom.startswith("RING") else H.domain_points(dom)
-        tr = H.record_final_smooth_trace(pts, acts, iteration=iteration, max_calls=24)
+        max_calls = 24
+        if xf:
+            max_calls, pts = xf[0], transform(pts, xf[1], xf[2])
+        tr = H.record_final_smooth_trace(pts, acts, iteration=iteration, max_calls=max_calls)
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **tr)
         print(f"{name}: {T} steps, {int(tr['n_calls'])} smooth() calls, sweeps "
               f"{tr['call_sweeps'].tolist() if tr['n_calls'] else []}, front {tr['call_nr'].tolist() if tr['n_calls'] else []}, "
@@ -262,9 +297,22 @@ FRONT_SMOOTH_TRACES = [
 ]
 
 
-def main_front_smooth():
-    for name, dom, seed, T, every in FRONT_SMOOTH_TRACES:
-        tr = H.record_front_smooth_trace(H.domain_points(dom), H.biased_actions(seed, T), every)
+# front smoothing on transformed domains: (fixture name, domain, seed, T, every, scale, (dx, dy)), iteration cap 400
+XF_FRONT_SMOOTH_TRACES = [
+    ("smoothfront_xf_boundary0_dx1e6_s1", "boundary0", 1, 400, 3, 1.0, (1e6, 0.0)),
+    ("smoothfront_xf_boundary0_d1e8_s1", "boundary0", 1, 400, 3, 1.0, (1e8, -1e8)),
+    ("smoothfront_xf_boundary0_x1em2_s1", "boundary0", 1, 400, 3, 1e-2, (0.0, 0.0)),
+    ("smoothfront_xf_boundary0_x1e3_d1e6_s1", "boundary0", 1, 400, 3, 1e3, (1e6, -1e6)),
+    ("smoothfront_xf_boundary16_x1e2_s1", "boundary16", 1, 400, 3, 1e2, (0.0, 0.0)),
+]
+
+
+def main_front_smooth(only=()):
+    for name, dom, seed, T, every, *xf in FRONT_SMOOTH_TRACES + XF_FRONT_SMOOTH_TRACES:
+        if only and name not in only:
+            continue
+        pts = transform(H.domain_points(dom), *xf) if xf else H.domain_points(dom)
+        tr = H.record_front_smooth_trace(pts, H.biased_actions(seed, T), every)
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **tr)
         nc = int(tr["n_calls"])
         print(f"{name}: {T} steps, {int(tr['valid'].sum())} valid, {nc} smooth_pave(interior=False) calls, "
@@ -558,10 +606,11 @@ def main():
     if "--transformed-only" in sys.argv:
         main_transformed(only=[a for a in sys.argv[1:] if a.startswith("xf_")])
         return
-    if "--smooth-only" in sys.argv:
-        main_smooth()
-        main_final_smooth()
-        main_front_smooth()
+    if "--smooth-only" in sys.argv:     # all of them, or the fixtures named after the flag (smooth_* / smoothfinal_* / smoothfront_*)
+        only = [a for a in sys.argv[1:] if a.startswith("smooth")]
+        main_smooth(only)
+        main_final_smooth(only)
+        main_front_smooth(only)
         return
     if "--quality-only" in sys.argv:
         quality_fixture()

@@ -77,6 +77,8 @@ def input_rows(n_real=5000):
         name = os.path.basename(f)
         if name.startswith(("quality_", "samples_", "front_", "plot_")):
             continue
+        if name.startswith(("smooth_xf_", "smoothfront_xf_", "smoothfinal_xf_")):
+            continue      # the smoothing records on transformed domains came later: the rows (and every recorded bit) stay
         z = np.load(f)
         if "obs" in z.files and z["obs"].ndim == 2 and z["obs"].shape[1] == 18:
             real.append(z["obs"].astype(np.float32))

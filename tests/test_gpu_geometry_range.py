@@ -257,8 +257,28 @@ def test_create_refuses_coordinates_beyond_1e100(torch_cuda):
     MeshVecEnv([[(x * 1e90, y * 1e90) for x, y in ring]], n_envs=64).close()
 
 
-def _move_lockstep(torch, doms, params, n, T):
-    """move() on the device against RefEnv.move with the same constants; returns the accepted moves."""
+MOVE_TRANSFORMS = [t for t in TRANSFORMS if t[0] in ("x1em2", "x1e2", "dx1e6", "dx1e8", "x1e3_d1e6")]
+
+
+@pytest.mark.parametrize("tid,scale,dx,dy", MOVE_TRANSFORMS, ids=[t[0] for t in MOVE_TRANSFORMS])
+def test_transformed_domains_move_lockstep(torch_cuda, tid, scale, dx, dy):
+    """move() on transformed boundary(0) and d1, 128 envs, 30 moves, against the oracle: codes, flags, observations, rings.
+    A rejected move that empties not_valid_points ran move()'s smooth_pave(interior=False) branch (the front smoother,
+    the interior relaxation, the rebuild: rl/boundary_env.py:405-426) on the transformed coordinates; those moves are
+    counted.  (The oracle's MOVE_NEEDS_SMOOTHING code is something else -- its refusal when the element log overflowed --
+    and is counted apart: it does not occur with a log of 256.)"""
+    t0 = time.time()
+    doms = _transform(_rings()[:2], scale, dx, dy)
+    stats = {}
+    mv = _move_lockstep(torch_cuda, doms, None, n=128, T=30, stats=stats)
+    print(f"{tid}: move valid {mv}, codes {stats['codes']}, moves through the smoothing branch {stats['smoothed']}, "
+          f"with code MOVE_NEEDS_SMOOTHING {stats['codes'][3]} in {time.time() - t0:.1f} s")
+    assert stats["smoothed"] > 0, (tid, stats)      # under every transform, hence also summed over them
+
+
+def _move_lockstep(torch, doms, params, n, T, stats=None):
+    """move() on the device against RefEnv.move with the same constants; returns the accepted moves.  stats (a dict):
+    filled with `codes` (moves per oracle code) and `smoothed` (moves that went through move()'s smooth_pave branch)."""
     from oracle.ref_lib import RefEnv
     from reinforcementlearning4meshgeneration_amd import MeshVecEnv
     env_domain = (np.arange(n) % len(doms)).astype(np.int32)
@@ -267,7 +287,8 @@ def _move_lockstep(torch, doms, params, n, T):
     obs = env.reset(static=True).cpu().numpy()
     np.testing.assert_array_equal(obs, np.stack([r.reset(static=True)[0] for r in refs]))
     rng = np.random.default_rng(29)
-    valid = 0
+    valid = smoothed = 0
+    codes = [0] * 5
     for t in range(T):
         pts = np.stack([rng.uniform(0.05, 0.45, n), rng.uniform(0.2, 1.5, n)], axis=1)
         typ = rng.uniform(0, 1, n)
@@ -275,8 +296,14 @@ def _move_lockstep(torch, doms, params, n, T):
         reset_mask = np.zeros(n, np.uint8)
         for k in range(n):
             n_before = refs[k].scalars()["n_elem"]
+            nv_before = refs[k].not_valid_count()
             o_r, d_r, c_r, code_r = refs[k].move(pts[k], typ[k])
             assert code[k] == code_r, (t, k, code[k], code_r)
+            codes[code_r] += 1
+            # a rejected move that leaves not_valid_points empty went through smooth_pave (B:405-426); so did one in
+            # which the reference raises inside it
+            smoothed += int((code_r not in (2, 3) and refs[k].scalars()["n_elem"] == n_before and nv_before > 0
+                             and refs[k].not_valid_count() == 0) or code_r == 4)
             if code_r != 2:
                 assert bool(d[k]) == d_r and bool(c[k]) == c_r, (t, k)
             if code_r == 0:
@@ -293,6 +320,8 @@ def _move_lockstep(torch, doms, params, n, T):
         np.testing.assert_array_equal(st["ring_ids"], ids)
         assert np.array_equal(st["ring_xy"], xy)
     env.close()
+    if stats is not None:
+        stats.update(codes=codes, smoothed=smoothed)
     assert valid >= 0.05 * n * T, valid
     return valid
 

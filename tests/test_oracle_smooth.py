@@ -81,6 +81,81 @@ def test_final_smooth_fixtures_cover_all_three_branches_and_both_front_sizes():
     assert any((t["call_sweeps"] == int(t["iteration"])).any() for t in trs)
 
 
+# The transformed fixtures (oracle/gen_golden.py XF_SMOOTH_TRACES / XF_FINAL_SMOOTH_TRACES / XF_FRONT_SMOOTH_TRACES):
+# <family>_xf_<domain>_<tag>_s<seed>, tag -> (scale, dx, dy); domain -> an untransformed fixture that holds its ring.
+XF_TAGS = {"dx1e6": (1.0, 1e6, 0.0), "dx1e8": (1.0, 1e8, 0.0), "d1e8": (1.0, 1e8, -1e8), "x1em2": (1e-2, 0.0, 0.0),
+           "x1e2": (1e2, 0.0, 0.0), "x1e3_d1e6": (1e3, 1e6, -1e6)}
+XF_BASE = {"boundary0": "smooth_boundary0_s1", "boundary16": "smooth_boundary16_s2", "ring13": "smoothfinal_ring13_s4",
+           "star": "smoothfinal_star_s6"}
+
+
+def xf_fixture_transform(name):
+    """(domain, scale, dx, dy) of a *_xf_* smoothing fixture, from its name."""
+    dom, rest = name.split("_xf_")[1].split("_", 1)
+    tag = rest.rsplit("_", 1)[0]
+    return (dom,) + XF_TAGS[tag]
+
+
+def _load(name):
+    return dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
+
+
+def test_transformed_smooth_fixtures_cover_what_the_transforms_change():
+    """Conditions on the recorded inputs, not on any implementation: the transformed fixtures are what their names say,
+    hold enough calls that move vertices, and reach the sweep-count shifts the absolute 0.001 stop rule produces under
+    scaling (longer runs scaled up, collapsed runs scaled down), all three branches of smooth(), fronts of 4 and 5 and
+    the iteration cap."""
+    interior = [n for n in smooth_golden_names() if "_xf_" in n]
+    front = [n for n in front_smooth_golden_names() if "_xf_" in n]
+    final = [n for n in final_smooth_golden_names() if "_xf_" in n]
+    assert len(interior) >= 4 and len(front) >= 4 and len(final) >= 4, (interior, front, final)
+    for name in interior + front + final:
+        tr = _load(name)
+        dom, scale, dx, dy = xf_fixture_transform(name)
+        base = _load(XF_BASE[dom])["domain_xy"]
+        M = float(np.abs(tr["domain_xy"]).max())
+        want = np.stack([scale * base[:, 0] + dx, scale * base[:, 1] + dy], axis=1)
+        assert np.array_equal(tr["domain_xy"], want) and not np.array_equal(tr["domain_xy"], base), \
+            f"{name}: domain_xy is not x -> {scale} x + ({dx}, {dy}) of {XF_BASE[dom]}; largest |coordinate| {M}"
+        assert (M > 10 * np.abs(base).max()) or (M < 0.1 * np.abs(base).max()), f"{name}: largest |coordinate| {M}"
+    for name in interior + front:
+        tr = _load(name)
+        nc = int(tr["n_calls"])
+        assert nc >= 8, (name, nc)
+        moved = sum(int(np.any(tr["call_after"][k, :nv] != tr["call_before"][k, :nv], axis=1).sum())
+                    for k, nv in enumerate(tr["call_nv"]))
+        assert moved > 0, name
+    trs = {n: _load(n) for n in interior}
+    assert any(((t["call_sweeps"] > 1) & (t["call_sweeps"] < int(t["iteration"]))).any() for t in trs.values())
+    longer = collapsed = 0
+    for n, t in trs.items():
+        dom, scale, _, _ = xf_fixture_transform(n)
+        if scale > 1:
+            plain = [_load(p)["call_sweeps"].max() for p in smooth_golden_names()
+                     if "_xf_" not in p and p.startswith("smooth_" + dom + "_")]
+            assert plain, dom
+            longer += int(t["call_sweeps"].max() > max(plain))
+        if scale < 1:
+            collapsed += int((t["call_sweeps"] <= 20).all())
+    assert longer >= 1 and collapsed >= 1, (longer, collapsed)
+    fin = [_load(n) for n in final]
+    visits = np.sum([t["call_branch"].sum(axis=0) for t in fin], axis=0)
+    assert (visits > 0).all(), visits                     # 1 / 2 / >= 3 related elements
+    fronts = np.concatenate([t["call_nr"] for t in fin])
+    assert (fronts == 4).any() and (fronts == 5).any()
+    assert any((t["call_sweeps"] == int(t["iteration"])).any() for t in fin)
+
+
+def test_smooth_final_m0_is_the_largest_coordinate_of_the_untransformed_fixtures():
+    """The constant the GPU replay scales its vertex tolerance by (tests/test_gpu_smooth.py)."""
+    from test_gpu_smooth import SMOOTH_FINAL_M0, smooth_final_vertex_tol
+    names = [n for n in final_smooth_golden_names() if "_xf_" not in n]
+    assert len(names) >= 6
+    assert max(float(np.abs(_load(n)["domain_xy"]).max()) for n in names) == SMOOTH_FINAL_M0
+    assert all(smooth_final_vertex_tol(_load(n)["domain_xy"], False) == 1e-11 for n in names)
+    assert smooth_final_vertex_tol(np.array([[2.0 * SMOOTH_FINAL_M0, 0.0]]), True) == 2e-11
+
+
 @pytest.mark.parametrize("name", front_smooth_golden_names())
 def test_oracle_front_smoother_matches_reference_records(name):
     """smooth_pave(..., interior=False) -- smooth_current_boundary_3 (general/mesh.py:939-1028) + the interior relaxation +

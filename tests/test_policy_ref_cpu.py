@@ -190,3 +190,13 @@ def test_inputs_cover_the_observation_range(rows):
     assert len(real) >= 4000 and real.min() < -1.57 and real.max() > 6.28
     nz = (obs[:33] != 0).sum(axis=1)
     assert (nz == 1).sum() >= 18 and (nz == 0).sum() >= 2 and (np.abs(obs[:33]).max(axis=1) == 100).sum() == 8
+
+
+def test_input_rows_do_not_change_when_fixtures_are_added():
+    """input_rows() draws its real observations from the recorded traces under tests/golden/: a new fixture with an `obs`
+    array would silently change the inputs of every policy / gradient test, the bit-recorded ones included.  The rows are
+    pinned; a fixture added later is excluded by name in policy_ref.input_rows (as the smooth*_xf_* records are)."""
+    import hashlib
+    x = R.input_rows()
+    assert x.shape == (5028, 18) and x.dtype == np.float32
+    assert hashlib.sha256(x.tobytes()).hexdigest() == "7c506f41970a2853c4f8015569accfdd6066c18ccaf1ebaf183b141bf7479e9f"
