@@ -10,7 +10,8 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "DeviceReplayBuffer", "ReplayBufferSamples", "FusedTDTarget", "TDTargetSpec", "FusedCriticGrad", "CriticGradSpec",
            "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
            "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
-           "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs"]
+           "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
+           "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -65,4 +66,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs"):
         from . import offpolicy_train
         return getattr(offpolicy_train, name)
+    if name in ("FusedOffPolicyLearn", "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats"):
+        from . import offpolicy_learn
+        return getattr(offpolicy_learn, name)
     raise AttributeError(name)

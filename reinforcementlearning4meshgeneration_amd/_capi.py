@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_offpolicy_train.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -114,6 +114,15 @@ EXPORTS_OFFPOLICY_TRAIN = [
 OFFTRAIN_OUTPUTS, OFFTRAIN_MAX_STEPS = 8, 65536
 OFFTRAIN_SAMPLE_FLOATS, REPLAY_BATCHES_MAX_SAMPLES = 41, 2 ** 24
 
+# every symbol include/meshenv_offpolicy_learn.h declares: the live SAC behaviour actor, the warm-up actions and their steps, the
+# episode statistics
+EXPORTS_OFFPOLICY_LEARN = [
+    "meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_actor_last_error", "meshenv_uniform_actions",
+    "meshenv_step_actions_multi", "meshenv_episode_stats_create", "meshenv_episode_stats_destroy",
+    "meshenv_episode_stats_set_stream", "meshenv_episode_stats_last_error", "meshenv_episode_stats_update",
+]
+UNIFORM_PHILOX_TAG, EPISODE_RING_DOUBLES = 4, 3
+
 
 class MeshOptimScalars(C.Structure):
     """include/meshenv_optim.h MeshOptimScalars: the host-computed scalars of one step, a kernel argument."""
@@ -219,7 +228,8 @@ def load():
                                           ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
                                           ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True),
                                           ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True),
-                                          ("meshenv_onpolicy_train", [], True), ("meshenv_offpolicy_train", [], True)):
+                                          ("meshenv_onpolicy_train", [], True), ("meshenv_offpolicy_train", [], True),
+                                          ("meshenv_episode_stats", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -271,6 +281,15 @@ def load():
     L.meshenv_offpolicy_train_run.argtypes = [vp] * 7 + [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
                                               C.POINTER(vp), C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(MeshOptimScalars),
                                               C.POINTER(MeshOptimScalars), C.c_int, vp]
+    L.meshenv_actor_bind.argtypes = [vp, C.POINTER(vp), C.c_int]
+    L.meshenv_actor_refresh.argtypes = [vp]
+    L.meshenv_actor_last_error.argtypes, L.meshenv_actor_last_error.restype = [vp], C.c_char_p
+    L.meshenv_uniform_actions.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), vp, vp]
+    L.meshenv_step_actions_multi.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int]
+    L.meshenv_episode_stats_update.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 9
+    for name in ("meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_uniform_actions", "meshenv_step_actions_multi",
+                 "meshenv_episode_stats_update"):
+        getattr(L, name).restype = C.c_int
     for name in ("meshenv_replay_sample_batches", "meshenv_offpolicy_train_run", "meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
                  "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",

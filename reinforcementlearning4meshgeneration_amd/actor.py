@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import sb3_nets
+from . import _capi, sb3_nets
 from ._handle import Handle
 from .vec_env import ACTION_HIGH, ACTION_LOW
 
@@ -54,6 +54,43 @@ class FusedActor(Handle):
             raise ValueError(f"actor.latent_pi has {len(linears)} Linear layers; the fused actor is MlpPolicy's ReLU [128, 128, 128] "
                              "(rl/baselines/RL_Mesh.py:183-196)")
         return cls.from_torch(linears, actor.mu, actor.log_std, device=device, low=low, high=high)
+
+    # ---------------------------------------------------------------- live parameters
+    @staticmethod
+    def live_params(policy):
+        """The ten LIVE tensors of an SB3 SAC model, SACPolicy or Actor in bind order (w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w
+        log_std_b), with the refusals of ``sb3_nets.sac_actor`` / ``sac_actor_params``.  No device is needed."""
+        actor = policy
+        if not hasattr(actor, "latent_pi"):
+            if not hasattr(actor, "actor") and hasattr(actor, "policy"):
+                actor = actor.policy
+            actor = getattr(actor, "actor", actor)
+        if not hasattr(actor, "latent_pi") or not hasattr(actor, "mu") or not hasattr(actor, "log_std"):
+            raise ValueError("not an SB3 SAC actor (latent_pi, mu, log_std)")
+        return sb3_nets.sac_actor_params(sb3_nets.sac_actor(actor), actor.mu, actor.log_std)
+
+    def _check_live(self, rc, what):
+        if rc != 0:
+            msg = self._L.meshenv_actor_last_error(self._h)
+            raise _capi.MeshEnvError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+    def bind_live(self, policy) -> None:
+        """Record the LIVE parameters of ``policy`` (an SB3 SAC model, SACPolicy or Actor) so that refresh() can carry them
+        into this object's packed weights: what SB3 does implicitly when collect_rollouts reads the parameters
+        ``actor.optimizer.step()`` has just written.  The object must have been loaded (from_torch / from_sb3 lay the packed
+        buffer out) and the tensors must be on this device.  Again after anything that reallocates the parameters."""
+        params = self.live_params(policy)
+        sb3_nets.check_device(params, self.device, "FusedActor.bind_live")
+        self._check_live(self._L.meshenv_actor_bind(self._h, self._ptrs(params), len(params)), "meshenv_actor_bind")
+        self._live = params      # keeps the storages alive
+
+    def refresh(self) -> None:
+        """The bound parameters, as they are now, into the packed weights: one launch on the current stream, no host copy, no
+        synchronisation.  Launches that follow on the same stream see the new weights."""
+        if getattr(self, "_live", None) is None:
+            raise ValueError("refresh() needs bind_live(model) first")
+        self._bind_stream()
+        self._check_live(self._L.meshenv_actor_refresh(self._h), "meshenv_actor_refresh")
 
     def forward(self, obs, noise=None, out=None):
         """obs: float32 CUDA [n, 18]; noise: float32 CUDA [n, 3] of N(0,1) samples or None (deterministic).

@@ -72,6 +72,13 @@ __device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t counter, 
     return rad * (which == 1 ? sn : cs);
 }
 
+// SB3's policy.unscale_action: s in [-1, 1] to the action Box, four fp32 operations (k_policy_forward's deterministic kind,
+// k_uniform_actions)
+__device__ __forceinline__ float unscale_action(float s, float low, float high)
+{
+    return low + 0.5f * (s + 1.0f) * (high - low);
+}
+
 constexpr int kActWaves = 8;    // wavefronts per workgroup = 16-neuron output tiles of a hidden layer
 
 template <int G>  // G = K / 16 float4 groups per tile

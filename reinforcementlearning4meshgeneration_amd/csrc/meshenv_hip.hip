@@ -10,6 +10,7 @@
 #include "../../include/meshenv_rollout.h"
 #include "../../include/meshenv_onpolicy_train.h"
 #include "../../include/meshenv_offpolicy_train.h"
+#include "../../include/meshenv_offpolicy_learn.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -42,6 +43,7 @@
 #include "meshenv_rollout.h"
 #include "meshenv_onpolicy_train.h"
 #include "meshenv_offpolicy_train.h"
+#include "meshenv_learn.h"
 
 using namespace meshenv;
 
@@ -1731,6 +1733,9 @@ struct MeshActor : HandleBase {
     size_t nfloat = 0;
     ActorWeights W{};
     bool loaded = false;
+    PackTable table{};     // meshenv_actor_bind: the live tensors and where meshenv_actor_refresh packs them
+    int n_copies = 0;
+    bool live = false;
 };
 
 int meshenv_actor_create(int device, void *stream, MeshActor **out)
@@ -3709,6 +3714,129 @@ int meshenv_offpolicy_train_run(MeshOffPolicyTrain *t, MeshEnv *env, MeshTarget 
     return launch(t, guard, "meshenv_offpolicy_train_run", [&] {
         hipLaunchKernelGGL(k_offpolicy_finish, dim3(1), dim3(kTrFinishThreads), 0, t->stream, A);
     }, "finish launch");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the off-policy learn loop
+// (include/meshenv_offpolicy_learn.h, csrc/meshenv_learn.h)
+static_assert(MESHENV_UNIFORM_PHILOX_TAG == kUniformPhiloxTag, "include/meshenv_offpolicy_learn.h and csrc/meshenv_learn.h disagree");
+
+struct MeshEpisodeStats : HandleBase {};
+
+extern "C" {
+
+// ---- live weights into a loaded FusedActor (the SAC twin of meshenv_policy_bind / meshenv_policy_refresh)
+int meshenv_actor_bind(MeshActor *a, const float *const *tensors_dev, int n)
+{
+    if (!a) return MESHENV_E_ARG;
+    if (!a->loaded) return fail(a, MESHENV_E_STATE, "meshenv_actor_bind: no weights loaded (meshenv_actor_load lays the buffer out)");
+    if (!tensors_dev || n != 10)
+        return fail(a, MESHENV_E_ARG, "meshenv_actor_bind: the SAC actor takes 10 tensors (w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w log_std_b)");
+    for (int i = 0; i < n; i++)
+        if (!tensors_dev[i]) return fail(a, MESHENV_E_ARG, "meshenv_actor_bind: null tensor");
+    constexpr int H = kActHid, G = kActHid / 16;
+    a->n_copies = 0;
+    auto add = [&](const float *src, const float *dst, int out, int in, int groups, int tiles, int n_off, int kind) {
+        PackCopy &c = a->table.c[a->n_copies++];
+        c.src = src; c.dst = const_cast<float *>(dst); c.out = out; c.in = in; c.groups = groups; c.tiles = tiles; c.n_off = n_off; c.kind = kind;
+    };
+    const float *const *t = tensors_dev;
+    // the layout of meshenv_actor_load: [tile 8][K / 16][lane 64][4] per hidden layer, one 16-wide head tile (mu at column 0,
+    // log_std at column 3), which is what k_target_pack writes
+    add(t[0], a->W.w1p, H, kActIn, kActInPad / 16, G, 0, kPackMatrix); add(t[1], a->W.b1, H, 0, 0, 0, 0, kPackVector);
+    add(t[2], a->W.w2p, H, H, G, G, 0, kPackMatrix); add(t[3], a->W.b2, H, 0, 0, 0, 0, kPackVector);
+    add(t[4], a->W.w3p, H, H, G, G, 0, kPackMatrix); add(t[5], a->W.b3, H, 0, 0, 0, 0, kPackVector);
+    add(t[6], a->W.whp, kActOut, H, G, 1, 0, kPackMatrix); add(t[7], a->W.bh, kActOut, 0, 0, 0, 0, kPackVector);
+    add(t[8], a->W.whp, kActOut, H, G, 1, kActOut, kPackMatrix); add(t[9], a->W.bh, kActOut, 0, 0, 0, kActOut, kPackVector);
+    static_assert(10 <= kTgtMaxCopies, "the copy table holds the 10 sources");
+    a->live = true;
+    return MESHENV_OK;
+}
+
+int meshenv_actor_refresh(MeshActor *a)
+{
+    if (!a) return MESHENV_E_ARG;
+    if (!a->loaded || !a->live) return fail(a, MESHENV_E_STATE, "meshenv_actor_refresh: no tensors bound (meshenv_actor_bind)");
+    DeviceGuard guard(a->device);
+    // the largest copy is a 128 x 128 matrix: 64 blocks of 256 threads cover it in one pass
+    return launch(a, guard, "meshenv_actor_refresh", [&] {
+        hipLaunchKernelGGL(k_target_pack, dim3(kActHid * kActHid / 256, a->n_copies), dim3(256), 0, a->stream, a->table);
+    });
+}
+
+const char *meshenv_actor_last_error(const MeshActor *a) { return last_error(a); }
+
+// ---- warm-up actions and the steps that take them
+int meshenv_uniform_actions(MeshEnv *h, int T, uint64_t seed, uint64_t counter, const float *low_high_host, float *actions_dev,
+                            float *buffer_actions_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (T < 1 || !low_high_host || !actions_dev || !buffer_actions_dev)
+        return fail_arg(h, "meshenv_uniform_actions: T >= 1, the six bounds and both outputs are required");
+    UniformArgs A{};
+    for (int k = 0; k < 3; k++) {
+        A.low[k] = low_high_host[k]; A.high[k] = low_high_host[3 + k];
+        if (!std::isfinite(A.low[k]) || !std::isfinite(A.high[k]) || !(A.high[k] > A.low[k]))
+            return fail_arg(h, "meshenv_uniform_actions: the bounds must be finite with high > low");
+    }
+    A.T = T; A.n = h->n_envs; A.seed = seed; A.counter = counter; A.actions = actions_dev; A.buffer_actions = buffer_actions_dev;
+    MESHENV_ON_DEVICE(h);
+    const long long total = (long long)T * h->n_envs;
+    const long long want = (total + 255) / 256;
+    const int blocks = want < 4096 ? (int)want : 4096;   // the kernel strides over the rest
+    hipLaunchKernelGGL(k_uniform_actions, dim3(blocks), dim3(256), 0, h->stream, A);
+    HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+int meshenv_step_actions_multi(MeshEnv *h, int T, const float *actions_dev, float *obs_dev, double *reward_dev, uint8_t *done_dev,
+                               uint8_t *complete_dev, float *terminal_obs_dev, int auto_reset)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (T < 1 || !actions_dev || !obs_dev || !reward_dev || !done_dev || !complete_dev)
+        return fail_arg(h, "meshenv_step_actions_multi: T >= 1 and non-null actions, obs, reward, done and complete are required");
+    const size_t n = (size_t)h->n_envs;
+    for (int t = 0; t < T; t++) {
+        const int rc = launch_step(h, 1, actions_dev + (size_t)t * n * 3, obs_dev + (size_t)(t + 1) * n * kObsDim, reward_dev + (size_t)t * n,
+                                   done_dev + (size_t)t * n, complete_dev + (size_t)t * n,
+                                   terminal_obs_dev ? terminal_obs_dev + (size_t)t * n * kObsDim : nullptr, auto_reset);
+        if (rc != MESHENV_OK) return rc;
+    }
+    return MESHENV_OK;
+}
+
+// ---- episode statistics
+int meshenv_episode_stats_create(int device, void *stream, MeshEpisodeStats **out)
+{
+    return create_handle("meshenv_episode_stats_create", device, stream, out);
+}
+
+void meshenv_episode_stats_destroy(MeshEpisodeStats *s) { destroy_handle(s, nullptr); }
+
+const char *meshenv_episode_stats_last_error(const MeshEpisodeStats *s) { return last_error(s); }
+
+int meshenv_episode_stats_set_stream(MeshEpisodeStats *s, void *stream) { return set_stream(s, stream); }
+
+int meshenv_episode_stats_update(MeshEpisodeStats *s, int T, int n, int window, const double *reward_dev, const uint8_t *done_dev,
+                                 const uint8_t *complete_dev, double *carry_return_dev, int32_t *carry_len_dev, double *ring_dev,
+                                 uint64_t *count_dev, double *work_return_dev, int32_t *work_len_dev)
+{
+    if (!s) return MESHENV_E_ARG;
+    if (T < 1 || n < 1 || window < 1 || (long long)T * n >= (1LL << 31))
+        return fail(s, MESHENV_E_ARG, "meshenv_episode_stats_update: T, n, window >= 1 and T * n < 2^31 are required");
+    if (!reward_dev || !done_dev || !complete_dev || !carry_return_dev || !carry_len_dev || !ring_dev || !count_dev || !work_return_dev ||
+        !work_len_dev)
+        return fail(s, MESHENV_E_ARG, "meshenv_episode_stats_update: null device pointer");
+    if ((uintptr_t)count_dev % 8 != 0) return fail(s, MESHENV_E_ARG, "meshenv_episode_stats_update: count_dev must be 8-byte aligned");
+    EpisodeArgs A{};
+    A.T = T; A.n = n; A.W = window; A.reward = reward_dev; A.done = done_dev; A.complete = complete_dev;
+    A.carry_return = carry_return_dev; A.carry_len = carry_len_dev; A.ring = ring_dev; A.count = (unsigned long long *)count_dev;
+    A.work_return = work_return_dev; A.work_len = work_len_dev;
+    DeviceGuard guard(s->device);
+    return launch(s, guard, "meshenv_episode_stats_update", [&] {
+        hipLaunchKernelGGL(k_episode_stats, dim3(1), dim3(kEpThreads), 0, s->stream, A);
+    });
 }
 
 }  // extern "C"

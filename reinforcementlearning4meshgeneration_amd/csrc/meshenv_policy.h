@@ -180,7 +180,7 @@ __device__ __forceinline__ void policy_pass(const PolicyTower &T, const float *_
             float s = tanhf(mean);
             if (noisy) s = fminf(fmaxf(s + scale * eps, -1.0f), 1.0f);
             ba = s;
-            act = low + 0.5f * (s + 1.0f) * (high - low);
+            act = unscale_action(s, low, high);
         }
         // sum over the three action components (lanes e, e + 1, e + 2 of the row), in torch's order
         const float lp1 = __shfl(lp, lane + 1, 64), lp2 = __shfl(lp, lane + 2, 64);

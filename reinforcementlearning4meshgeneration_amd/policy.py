@@ -151,6 +151,17 @@ class PolicySpec:
         return ptrs + [self.low.ctypes.data, self.high.ctypes.data]
 
 
+def live_deterministic(model):
+    """(hidden, activation, the six live tensors w1 b1 w2 b2 w3 b3) of the LIVE actor of an SB3 TD3 model, TD3Policy or Actor,
+    through ``sb3_nets.td3_live_actor`` (its refusals: a SAC model, no Tanh tail, other widths, non-float32 parameters)."""
+    if not hasattr(model, "actor") and hasattr(model, "mu"):
+        import types
+        model = types.SimpleNamespace(actor=model)
+    layers, mu = N.td3_live_actor(model)
+    params = N.td3_actor_params(layers, mu)
+    return N.HIDDEN[N.KIND_TD3][0], "relu", params
+
+
 class FusedPolicy(Handle):
     """A PolicySpec loaded on one GPU.  forward / sample / value return dicts of float32 CUDA tensors."""
     PREFIX = "meshenv_policy"
@@ -181,13 +192,17 @@ class FusedPolicy(Handle):
 
     # ---------------------------------------------------------------- live parameters
     def bind_live(self, policy) -> None:
-        """Record the LIVE parameters of ``policy`` (an SB3 ActorCriticPolicy, or a PPO / A2C object through ``.policy``) so
-        that refresh() can carry them into this object's packed weights: what SB3 does implicitly when collect_rollouts reads
-        the parameters ``policy.optimizer.step()`` has just written.  The shapes and the activation must be the loaded ones
-        and the tensors on this device.  Again after anything that reallocates the parameters (``.to()``)."""
+        """Record the LIVE parameters of ``policy`` (an SB3 ActorCriticPolicy, or a PPO / A2C object through ``.policy``; for
+        the deterministic kind an SB3 TD3 model, TD3Policy or Actor: ``actor.mu``) so that refresh() can carry them into this
+        object's packed weights: what SB3 does implicitly when collect_rollouts reads the parameters
+        ``policy.optimizer.step()`` has just written.  The shapes and the activation must be the loaded ones and the tensors
+        on this device.  Again after anything that reallocates the parameters (``.to()``)."""
         if self.spec.kind != KIND_ACTOR_CRITIC:
-            raise ValueError("bind_live takes an actor-critic policy; the deterministic kind is rebuilt with from_sb3")
-        H, act, params = N.actor_critic_live(policy, widths=HIDDEN_WIDTHS)
+            # the deterministic kind: the live actor of an SB3 TD3 model (``model.actor``, ReLU [256, 256], six tensors); sigma,
+            # low and high stay as loaded
+            H, act, params = live_deterministic(policy)
+        else:
+            H, act, params = N.actor_critic_live(policy, widths=HIDDEN_WIDTHS)
         if H != self.spec.hidden or act != self.spec.activation:
             raise ValueError(f"the live policy is {act} [{H}, {H}]; this FusedPolicy was loaded as {self.spec.activation} "
                              f"[{self.spec.hidden}, {self.spec.hidden}]")

@@ -615,6 +615,62 @@ class MeshVecEnv:
                                  gae_lambda), episode_starts=starts)
         return out
 
+    def uniform_actions(self, T: int, seed: int = 0, counter: int = 0):
+        """SB3's ``_sample_action`` before ``learning_starts`` for T vector steps, one launch (k_uniform_actions):
+        ``(actions, buffer_actions)``, both float32 CUDA [T, n, 3]; buffer_actions uniform in [-1, 1) (Philox keyed by
+        ``seed``, step t at ``counter + t``, a stream of its own), actions the same rescaled to the action Box."""
+        t = self._torch
+        n, T = self.num_envs, int(T)
+        if T <= 0:
+            raise ValueError("T must be positive")
+        actions = t.empty((T, n, 3), dtype=t.float32, device=self.device)
+        buffer_actions = t.empty((T, n, 3), dtype=t.float32, device=self.device)
+        space = self.action_space
+        lh = (C.c_float * 6)(*np.asarray(space.low, np.float32).tolist(), *np.asarray(space.high, np.float32).tolist())
+        self._bind_stream()
+        rc = self._L.meshenv_uniform_actions(self._handle, T, C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(counter & (2 ** 64 - 1)),
+                                             lh, actions.data_ptr(), buffer_actions.data_ptr())
+        self._check(rc, "meshenv_uniform_actions")
+        return actions, buffer_actions
+
+    def step_actions_T(self, actions, buffer_actions=None):
+        """T vector steps with given actions [T, n, 3] in one C call (meshenv_step_actions_multi: T x the one-step launch on
+        slices of the histories, no host synchronisation).  Returns the dict of collect_rollout's shape: obs [T, n, 18] (what
+        each action met; the first T slices of a [T + 1] block), actions, buffer_actions when given, reward [T, n] float64,
+        done / complete [T, n] uint8, terminal_obs [T, n, 18] (zeros where not done).  env.obs / reward / done / complete end
+        as after T single steps."""
+        t = self._torch
+        n = self.num_envs
+        if actions.dtype != t.float32 or not actions.is_contiguous() or actions.device != self.device:
+            actions = actions.to(device=self.device, dtype=t.float32).contiguous()
+        if actions.dim() != 3 or tuple(actions.shape[1:]) != (n, 3) or actions.shape[0] < 1:
+            raise ValueError(f"actions must have shape (T, {n}, 3) with T >= 1, got {tuple(actions.shape)}")
+        T = int(actions.shape[0])
+        f32 = dict(dtype=t.float32, device=self.device)
+        obs = t.empty((T + 1, n, _capi.OBS_DIM), **f32)
+        obs[0].copy_(self.obs)
+        out = dict(obs=obs[:T], actions=actions, reward=t.empty((T, n), dtype=t.float64, device=self.device),
+                   done=t.empty((T, n), dtype=t.uint8, device=self.device),
+                   complete=t.empty((T, n), dtype=t.uint8, device=self.device),
+                   terminal_obs=t.zeros((T, n, _capi.OBS_DIM), **f32))
+        if buffer_actions is not None:
+            out["buffer_actions"] = buffer_actions
+        self._bind_stream()
+        rc = self._L.meshenv_step_actions_multi(self._handle, T, actions.data_ptr(), obs.data_ptr(), out["reward"].data_ptr(),
+                                                out["done"].data_ptr(), out["complete"].data_ptr(), out["terminal_obs"].data_ptr(),
+                                                1 if self.auto_reset else 0)
+        self._check(rc, "meshenv_step_actions_multi")
+        self.obs.copy_(obs[T])
+        self.reward.copy_(out["reward"][T - 1]); self.done.copy_(out["done"][T - 1]); self.complete.copy_(out["complete"][T - 1])
+        return out
+
+    def collect_uniform(self, T: int, seed: int = 0, counter: int = 0):
+        """T warm-up vector steps (SB3's collect_rollouts while ``num_timesteps < learning_starts``): uniform_actions, then
+        step_actions_T on them -- two C calls, nothing read back.  The dict is what ``DeviceReplayBuffer.add_rollout`` takes
+        unchanged (it stores buffer_actions as they are)."""
+        actions, buffer_actions = self.uniform_actions(T, seed, counter)
+        return self.step_actions_T(actions, buffer_actions)
+
     def compute_gae(self, reward, value, done, last_value, terminal_value=None, gamma: float = 0.99,
                     gae_lambda: float = 0.95):
         """SB3's RolloutBuffer.compute_returns_and_advantage (GAE) with collect_rollouts' bootstrap of truncated episodes
