@@ -11,7 +11,7 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
            "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
            "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
-           "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats"]
+           "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -69,4 +69,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedOffPolicyLearn", "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats"):
         from . import offpolicy_learn
         return getattr(offpolicy_learn, name)
+    if name == "DeviceEvalCallback":
+        from .eval_callback import DeviceEvalCallback
+        return DeviceEvalCallback
     raise AttributeError(name)

@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -123,6 +123,21 @@ EXPORTS_OFFPOLICY_LEARN = [
 ]
 UNIFORM_PHILOX_TAG, EPISODE_RING_DOUBLES = 4, 3
 
+# every symbol include/meshenv_eval_callback.h declares: the queued evaluation, the reduction of its records with the best-mean
+# gate, the gated copy of the live parameters
+EXPORTS_EVAL_CALLBACK = [
+    "meshenv_evaluate_queued", "meshenv_eval_callback_create", "meshenv_eval_callback_destroy", "meshenv_eval_callback_set_stream",
+    "meshenv_eval_callback_last_error", "meshenv_eval_reduce", "meshenv_keep_best",
+]
+EVAL_ROW_DOUBLES, EVAL_STATE_DOUBLES, KEEP_BEST_MAX_ENTRIES = 9, 4, 64
+EVAL_COLUMNS = ("num_timesteps", "mean_reward", "std_reward", "mean_ep_length", "recorded", "short", "complete_rate",
+                "mean_n_elements", "improved")
+
+
+class MeshKeepEntry(C.Structure):
+    """include/meshenv_eval_callback.h MeshKeepEntry: one tensor of a meshenv_keep_best call."""
+    _fields_ = [("src_dev", C.c_void_p), ("dst_offset", C.c_int64), ("numel", C.c_int64)]
+
 
 class MeshOptimScalars(C.Structure):
     """include/meshenv_optim.h MeshOptimScalars: the host-computed scalars of one step, a kernel argument."""
@@ -229,7 +244,7 @@ def load():
                                           ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True),
                                           ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True),
                                           ("meshenv_onpolicy_train", [], True), ("meshenv_offpolicy_train", [], True),
-                                          ("meshenv_episode_stats", [], True)):
+                                          ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -287,8 +302,11 @@ def load():
     L.meshenv_uniform_actions.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), vp, vp]
     L.meshenv_step_actions_multi.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int]
     L.meshenv_episode_stats_update.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 9
+    L.meshenv_evaluate_queued.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, evp]
+    L.meshenv_eval_reduce.argtypes = [vp, C.c_int, C.c_int, evp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
+    L.meshenv_keep_best.argtypes = [vp, C.POINTER(MeshKeepEntry), C.c_int, vp, C.c_int64, vp]
     for name in ("meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_uniform_actions", "meshenv_step_actions_multi",
-                 "meshenv_episode_stats_update"):
+                 "meshenv_episode_stats_update", "meshenv_evaluate_queued", "meshenv_eval_reduce", "meshenv_keep_best"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_replay_sample_batches", "meshenv_offpolicy_train_run", "meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",

@@ -11,6 +11,7 @@
 #include "../../include/meshenv_onpolicy_train.h"
 #include "../../include/meshenv_offpolicy_train.h"
 #include "../../include/meshenv_offpolicy_learn.h"
+#include "../../include/meshenv_eval_callback.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -44,6 +45,7 @@
 #include "meshenv_onpolicy_train.h"
 #include "meshenv_offpolicy_train.h"
 #include "meshenv_learn.h"
+#include "meshenv_eval_callback.h"
 
 using namespace meshenv;
 
@@ -3836,6 +3838,139 @@ int meshenv_episode_stats_update(MeshEpisodeStats *s, int T, int n, int window, 
     DeviceGuard guard(s->device);
     return launch(s, guard, "meshenv_episode_stats_update", [&] {
         hipLaunchKernelGGL(k_episode_stats, dim3(1), dim3(kEpThreads), 0, s->stream, A);
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the evaluation callback
+// (include/meshenv_eval_callback.h, csrc/meshenv_eval_callback.h)
+static_assert(MESHENV_EVAL_ROW_DOUBLES == kEvalRowDoubles && MESHENV_EVAL_STATE_DOUBLES == kEvalStateDoubles &&
+              MESHENV_KEEP_BEST_MAX_ENTRIES == kKeepMaxEntries, "include/meshenv_eval_callback.h and csrc/meshenv_eval_callback.h disagree");
+static_assert(sizeof(KeepTable) <= 2048, "the copy table travels as a kernel argument");
+
+struct MeshEvalCallback : HandleBase {};
+
+extern "C" {
+
+// meshenv_evaluate's loop with eval_read_short and the pinned word taken out: what is enqueued depends on `steps` alone
+int meshenv_evaluate_queued(MeshEnv *h, MeshPolicy *policy, MeshActor *actor, int sample, uint64_t seed, uint64_t counter, int steps,
+                            const MeshEvalBuffers *bufs)
+{
+    if (!h) return MESHENV_E_ARG;
+    if ((policy != nullptr) == (actor != nullptr)) return fail_arg(h, "meshenv_evaluate_queued: give exactly one of policy and actor");
+    if (steps < 1) return fail_arg(h, "meshenv_evaluate_queued: steps must be >= 1");
+    if (policy ? !policy->loaded : !actor->loaded) {
+        h->err = "meshenv_evaluate_queued: the policy / actor has no weights loaded";
+        return MESHENV_E_STATE;
+    }
+    if (policy ? (policy->device != h->device || policy->stream != h->stream) : (actor->device != h->device || actor->stream != h->stream)) {
+        h->err = "meshenv_evaluate_queued: env and policy / actor must be on the same device and stream";
+        return MESHENV_E_STATE;
+    }
+    EvalTallyArgs A;
+    int rc = eval_check(h, "meshenv_evaluate_queued", bufs, &A);
+    if (rc != MESHENV_OK) return rc;
+    MESHENV_ON_DEVICE(h);
+    const size_t n = (size_t)h->n_envs;
+    // every allocation before the first launch: nothing is allocated on the per-step path
+    if (!h->eval_act && (rc = dev_alloc(h, &h->eval_act, 2 * n * 3)) != MESHENV_OK) return rc;
+    if (!bufs->obs_dev && !h->eval_obs) {
+        if ((rc = dev_alloc(h, &h->eval_obs, n * kObsDim)) != MESHENV_OK || (rc = dev_alloc(h, &h->eval_reward, n)) != MESHENV_OK ||
+            (rc = dev_alloc(h, &h->eval_done, n)) != MESHENV_OK || (rc = dev_alloc(h, &h->eval_complete, n)) != MESHENV_OK)
+            return rc;
+    }
+    float *obs = bufs->obs_dev ? bufs->obs_dev : h->eval_obs;
+    double *reward = bufs->obs_dev ? bufs->reward_dev : h->eval_reward;
+    uint8_t *done = bufs->obs_dev ? bufs->done_dev : h->eval_done;
+    uint8_t *complete = bufs->obs_dev ? bufs->complete_dev : h->eval_complete;
+    float *act[2] = {h->eval_act, h->eval_act + n * 3};
+    if ((rc = meshenv_reset(h, nullptr, obs)) != MESHENV_OK) return rc;
+    if ((rc = eval_begin_launch(h, A)) != MESHENV_OK) return rc;
+    if (actor && (rc = actor_launch(actor, "meshenv_evaluate_queued", (int)n, obs, nullptr, act[0], sample, seed, counter, nullptr)) != MESHENV_OK) {
+        h->err = actor->err;
+        return rc;
+    }
+    PolicyArgs P{};
+    P.n = (int)n; P.obs = obs; P.sample = sample ? 1 : 0; P.seed = seed; P.actions = act[0];
+    for (int t = 0; t < steps; t++) {
+        if (policy) {
+            P.counter = counter + (uint64_t)t;
+            if ((rc = policy_launch(policy, "meshenv_evaluate_queued", P)) != MESHENV_OK) {
+                h->err = policy->err;
+                return rc;
+            }
+            rc = launch_step(h, 1, act[0], obs, reward, done, complete, nullptr, 1);
+        } else {
+            rc = meshenv_step_actor(h, actor, act[t & 1], obs, reward, done, complete, nullptr, 1, sample, seed, counter + (uint64_t)t + 1,
+                                    act[(t + 1) & 1], nullptr);
+        }
+        if (rc != MESHENV_OK) return rc;
+        if ((rc = eval_tally_launch(h, A, t, reward, done, complete)) != MESHENV_OK) return rc;
+    }
+    return MESHENV_OK;
+}
+
+int meshenv_eval_callback_create(int device, void *stream, MeshEvalCallback **out)
+{
+    return create_handle("meshenv_eval_callback_create", device, stream, out);
+}
+
+void meshenv_eval_callback_destroy(MeshEvalCallback *c) { destroy_handle(c, nullptr); }
+
+const char *meshenv_eval_callback_last_error(const MeshEvalCallback *c) { return last_error(c); }
+
+int meshenv_eval_callback_set_stream(MeshEvalCallback *c, void *stream) { return set_stream(c, stream); }
+
+int meshenv_eval_reduce(MeshEvalCallback *c, int n_envs, int total, const MeshEvalBuffers *bufs, int row, int capacity,
+                        double num_timesteps, double *history_dev, double *state_dev, int32_t *improved_dev)
+{
+    if (!c) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_eval_reduce";
+    if (n_envs < 1 || total < 0 || capacity < 1 || row < 0 || row >= capacity)
+        return fail(c, MESHENV_E_ARG, fn + ": n_envs >= 1, total >= 0 and 0 <= row < capacity are required");
+    if (!bufs || bufs->struct_size != (int32_t)sizeof(MeshEvalBuffers))
+        return fail(c, MESHENV_E_ARG, fn + ": MeshEvalBuffers missing or struct_size mismatch");
+    if (!bufs->target_dev || !bufs->offset_dev || !bufs->count_dev || !bufs->ep_return_dev || !bufs->ep_length_dev || !bufs->ep_flags_dev ||
+        !bufs->ep_n_elements_dev || !bufs->short_dev)
+        return fail(c, MESHENV_E_ARG, fn + ": target, offset, count, ep_return, ep_length, ep_flags, ep_n_elements and short are required");
+    if (!history_dev || !state_dev || !improved_dev || ((uintptr_t)history_dev & 7) || ((uintptr_t)state_dev & 7) || ((uintptr_t)improved_dev & 3))
+        return fail(c, MESHENV_E_ARG, fn + ": 8-byte aligned history_dev and state_dev and a 4-byte aligned improved_dev are required");
+    EvalReduceArgs A{};
+    A.n = n_envs; A.total = total; A.row = row; A.num_timesteps = num_timesteps;
+    A.target = bufs->target_dev; A.offset = bufs->offset_dev; A.count = bufs->count_dev;
+    A.ep_return = bufs->ep_return_dev; A.ep_length = bufs->ep_length_dev; A.ep_flags = bufs->ep_flags_dev; A.ep_n_elem = bufs->ep_n_elements_dev;
+    A.short_envs = bufs->short_dev; A.history = history_dev; A.state = state_dev; A.improved = improved_dev;
+    DeviceGuard guard(c->device);
+    return launch(c, guard, "meshenv_eval_reduce", [&] {
+        hipLaunchKernelGGL(k_eval_reduce, dim3(1), dim3(64), 0, c->stream, A);
+    });
+}
+
+int meshenv_keep_best(MeshEvalCallback *c, const MeshKeepEntry *entries_host, int n_entries, float *best_dev, int64_t best_floats,
+                      const int32_t *improved_dev)
+{
+    if (!c) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_keep_best";
+    if (!entries_host || n_entries < 1 || n_entries > kKeepMaxEntries)
+        return fail(c, MESHENV_E_ARG, fn + ": 1 to " + std::to_string(kKeepMaxEntries) + " entries are required");
+    if (!best_dev || !improved_dev || best_floats < 1 || ((uintptr_t)best_dev & 3) || ((uintptr_t)improved_dev & 3))
+        return fail(c, MESHENV_E_ARG, fn + ": 4-byte aligned best_dev and improved_dev and best_floats >= 1 are required");
+    KeepTable T{};
+    int64_t longest = 0;
+    for (int i = 0; i < n_entries; i++) {
+        const MeshKeepEntry &e = entries_host[i];
+        if (!e.src_dev || ((uintptr_t)e.src_dev & 3)) return fail(c, MESHENV_E_ARG, fn + ": entry " + std::to_string(i) + " has a NULL or misaligned source");
+        if (e.numel < 1 || e.dst_offset < 0 || e.dst_offset > best_floats || e.numel > best_floats - e.dst_offset)
+            return fail(c, MESHENV_E_ARG, fn + ": entry " + std::to_string(i) + " lies outside the " + std::to_string(best_floats) + " floats of best_dev");
+        T.e[i].src = e.src_dev; T.e[i].dst_off = e.dst_offset; T.e[i].numel = e.numel;
+        if (e.numel > longest) longest = e.numel;
+    }
+    const int64_t want = (longest / 4 + kKeepThreads - 1) / kKeepThreads + 1;   // one 16-byte copy per thread, the rest strides
+    const int chunks = want < kKeepMaxChunks ? (int)want : kKeepMaxChunks;
+    DeviceGuard guard(c->device);
+    return launch(c, guard, "meshenv_keep_best", [&] {
+        hipLaunchKernelGGL(k_keep_best, dim3(chunks, n_entries), dim3(kKeepThreads), 0, c->stream, best_dev, improved_dev, T);
     });
 }
 

@@ -292,11 +292,26 @@ class FusedOffPolicyLearn:
         self.collect_calls["behaviour"] += 1
         return out
 
-    def learn(self, total_timesteps: int, seed: int = 0, log_interval=None) -> OffPolicyLearnLogs:
+    def _check_callback(self, callback, num: int, total: int, n: int, T: int) -> None:
+        """The refusals of ``learn(callback=...)``, made before anything is enqueued."""
+        from .eval_callback import DeviceEvalCallback, schedule
+        if not isinstance(callback, DeviceEvalCallback):
+            raise TypeError(f"callback must be a DeviceEvalCallback, got {type(callback).__name__}")
+        if callback.eval_venv is self.venv:
+            raise ValueError("the callback's eval_venv is the training env: an evaluation resets its env; give it a MeshVecEnv of its own")
+        if callback.eval_venv.device != self.venv.device:
+            raise ValueError(f"the callback's eval envs are on {callback.eval_venv.device}, the training envs on {self.venv.device}")
+        if callback.model is not self.model:
+            raise ValueError("the callback keeps another model's parameters")
+        callback.room(len(schedule(callback.n_calls, num, total, n, T, callback.eval_freq)[0]))
+
+    def learn(self, total_timesteps: int, seed: int = 0, log_interval=None, callback=None) -> OffPolicyLearnLogs:
         """SB3's ``learn(total_timesteps, reset_num_timesteps=False)``: continues from ``model.num_timesteps`` for
         ``total_timesteps`` more (a first call starts at 0).  Everything is enqueued on the current stream; nothing is copied
         to the host and nothing synchronises.  seed keys the warm-up draw, the behaviour noise and the minibatch draw (three
-        Philox streams of their own).  log_interval is accepted for SB3's signature; read the returned object instead."""
+        Philox streams of their own).  log_interval is accepted for SB3's signature; read the returned object instead.
+        callback: a DeviceEvalCallback; the evaluations SB3's EvalCallback would make during a collect are enqueued in front
+        of it (the parameters change only in train()), each stamped with SB3's num_timesteps at its call."""
         spec, model, env = self.spec, self.model, self.venv
         if isinstance(total_timesteps, bool) or not isinstance(total_timesteps, (int, np.integer)) or total_timesteps < 0:
             raise ValueError(f"total_timesteps must be an int >= 0, got {total_timesteps!r}")
@@ -305,7 +320,11 @@ class FusedOffPolicyLearn:
         total = int(total_timesteps) + num
         seed = int(seed)
         iterations = 0
+        if callback is not None:
+            self._check_callback(callback, num, total, n, T)
         for W, P, after, K in plan(num, total, n, T, int(model.learning_starts), getattr(model, "gradient_steps", 1)):
+            if callback is not None:
+                callback.before_collect(self.behaviour, after - T * n, T, n)
             if W:
                 out = env.collect_uniform(W, seed=seed, counter=self.steps & MASK64)
                 self.buffer.add_rollout(out)
