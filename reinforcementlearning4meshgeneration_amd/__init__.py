@@ -11,7 +11,8 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "FusedActorGrad", "ActorGradSpec", "FusedOptimStep", "OptimStepSpec", "FusedTD3ActorGrad", "TD3ActorGradSpec",
            "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
            "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
-           "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback"]
+           "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback", "FusedOnPolicyLearn",
+           "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -69,6 +70,9 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedOffPolicyLearn", "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats"):
         from . import offpolicy_learn
         return getattr(offpolicy_learn, name)
+    if name in ("FusedOnPolicyLearn", "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter"):
+        from . import onpolicy_learn
+        return getattr(onpolicy_learn, name)
     if name == "DeviceEvalCallback":
         from .eval_callback import DeviceEvalCallback
         return DeviceEvalCallback

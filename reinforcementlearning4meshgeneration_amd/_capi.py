@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -106,6 +106,14 @@ EXPORTS_ONPOLICY_TRAIN = [
 ]
 TRAIN_OUTPUTS, TRAIN_MAX_MINIBATCHES = 12, 65536
 
+# every symbol include/meshenv_onpolicy_learn.h declares: the counted train() of a PPO learn loop with a target_kl
+EXPORTS_ONPOLICY_LEARN = [
+    "meshenv_onpolicy_learn_create", "meshenv_onpolicy_learn_destroy", "meshenv_onpolicy_learn_set_stream",
+    "meshenv_onpolicy_learn_last_error", "meshenv_onpolicy_learn_bind", "meshenv_onpolicy_learn_run",
+]
+LEARN_WORDS, LEARN_MAX_ENTRIES = 3, 2 ** 20
+LEARN_WORD_N_UPDATES, LEARN_WORD_ERROR, LEARN_WORD_STEPS = 0, 1, 2
+
 # every symbol include/meshenv_offpolicy_train.h declares: SAC.train / TD3.train as one call, and the draw of all its minibatches
 EXPORTS_OFFPOLICY_TRAIN = [
     "meshenv_offpolicy_train_create", "meshenv_offpolicy_train_destroy", "meshenv_offpolicy_train_set_stream",
@@ -142,6 +150,12 @@ class MeshKeepEntry(C.Structure):
 class MeshOptimScalars(C.Structure):
     """include/meshenv_optim.h MeshOptimScalars: the host-computed scalars of one step, a kernel argument."""
     _fields_ = [(name, C.c_float * OPTIM_BLOCKS) for name in ("step_size", "bc2_sqrt", "w1", "beta2", "w2", "eps")] + [
+        ("tau", C.c_float), ("one_minus_tau", C.c_float)]
+
+
+class MeshOptimCounted(C.Structure):
+    """include/meshenv_onpolicy_learn.h MeshOptimCounted: the scalars of every step of one counted train()."""
+    _fields_ = [("lr", C.c_double * OPTIM_BLOCKS)] + [(name, C.c_float * OPTIM_BLOCKS) for name in ("w1", "beta2", "w2", "eps")] + [
         ("tau", C.c_float), ("one_minus_tau", C.c_float)]
 
 
@@ -243,7 +257,8 @@ def load():
                                           ("meshenv_critic_grad", [C.c_int], True), ("meshenv_actor_grad", [f32, f32], True),
                                           ("meshenv_optim", [], True), ("meshenv_td3_actor_grad", [], True),
                                           ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True),
-                                          ("meshenv_onpolicy_train", [], True), ("meshenv_offpolicy_train", [], True),
+                                          ("meshenv_onpolicy_train", [], True), ("meshenv_onpolicy_learn", [], True),
+                                          ("meshenv_offpolicy_train", [], True),
                                           ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
@@ -292,7 +307,11 @@ def load():
     L.meshenv_onpolicy_train_run.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_double, f32, f32, C.c_int, C.c_int, f32, C.c_double,
                                              C.POINTER(MeshOptimScalars), C.c_int, vp]
-    L.meshenv_replay_sample_batches.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 7
+    L.meshenv_onpolicy_learn_bind.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_int, vp, C.c_int64]
+    L.meshenv_onpolicy_learn_run.argtypes = [vp] + L.meshenv_onpolicy_train_run.argtypes[:22] + [C.POINTER(MeshOptimCounted), vp, C.c_int,
+                                                                                              C.c_int]
+    L.meshenv_onpolicy_learn_bind.restype = L.meshenv_onpolicy_learn_run.restype = C.c_int
+    L.meshenv_replay_sample_batches.argtypes =[vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 7
     L.meshenv_offpolicy_train_run.argtypes = [vp] * 7 + [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
                                               C.POINTER(vp), C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(MeshOptimScalars),
                                               C.POINTER(MeshOptimScalars), C.c_int, vp]

@@ -9,6 +9,7 @@
 #include "../../include/meshenv_ppo_grad.h"
 #include "../../include/meshenv_rollout.h"
 #include "../../include/meshenv_onpolicy_train.h"
+#include "../../include/meshenv_onpolicy_learn.h"
 #include "../../include/meshenv_offpolicy_train.h"
 #include "../../include/meshenv_offpolicy_learn.h"
 #include "../../include/meshenv_eval_callback.h"
@@ -3236,13 +3237,14 @@ struct MeshOptim : HandleBase {
 namespace {
 
 // The launch of a bound program: k_optim_step, or with a gate (meshenv_onpolicy_train_run) k_optim_step_gated, or with a note
-// (meshenv_offpolicy_train_run) k_optim_step_noted, over the same tables.  A noted program must not step what the note reads:
-// the caller has looked (optim_program_writes).
+// (meshenv_offpolicy_train_run) k_optim_step_noted, or with a gate and a count (meshenv_onpolicy_learn_run, which passes no
+// scalars) k_optim_step_counted, over the same tables.  A noted program must not step what the note reads: the caller has
+// looked (optim_program_writes).
 int optim_step_launch(MeshOptim *o, int program, const MeshOptimScalars *scalars, const TrainGate *gate, const char *fn,
-                      const OptNote *note = nullptr)
+                      const OptNote *note = nullptr, const OptCounted *counted = nullptr)
 {
     if (!o) return MESHENV_E_ARG;
-    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || !scalars)
+    if (program < 0 || program >= MESHENV_OPTIM_PROGRAMS || (!scalars && !(counted && gate)))
         return fail(o, MESHENV_E_ARG, std::string(fn) + ": program out of range or no scalars");
     OptProgram &P = o->prog[program];
     if (!P.bound) return fail(o, MESHENV_E_STATE, std::string(fn) + ": program " + std::to_string(program) + " is not bound (meshenv_optim_bind)");
@@ -3254,10 +3256,13 @@ int optim_step_launch(MeshOptim *o, int program, const MeshOptimScalars *scalars
         P.ordered = o->stream;
     }
     o->last_stream = o->stream;
-    OptScalars S;
-    std::memcpy(&S, scalars, sizeof(S));
+    OptScalars S{};
+    if (scalars) std::memcpy(&S, scalars, sizeof(S));
     return launch(o, guard, fn, [&] {
-        if (note)
+        if (counted)
+            hipLaunchKernelGGL(k_optim_step_counted, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
+                               (const OptJob *)(P.dev + P.jobs_at), *counted, *gate);
+        else if (note)
             hipLaunchKernelGGL(k_optim_step_noted, dim3(P.n_jobs), dim3(kOptThreads), 0, o->stream, (const OptSeg *)P.dev,
                                (const OptJob *)(P.dev + P.jobs_at), S, *note);
         else if (gate)
@@ -3493,14 +3498,67 @@ const char *meshenv_onpolicy_train_last_error(const MeshOnPolicyTrain *t) { retu
 
 int meshenv_onpolicy_train_set_stream(MeshOnPolicyTrain *t, void *stream) { return set_stream(t, stream); }
 
-int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *o, int program, MeshRolloutBuffer *r,
-                               MeshPolicy *policy, int T, int n_envs, const float *const *in_dev, float *const *gather_dev,
-                               const void *perm_dev, int perm_bytes, int n_epochs, int batch_size, int a2c, double clip_range,
-                               float ent_coef, float vf_coef, int normalize_advantage, int clip_grad, float max_grad_norm,
-                               double target_kl, const MeshOptimScalars *scalars, int n_scalars, double *out_dev)
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the counted train() of learn()
+static_assert(MESHENV_LEARN_MAX_ENTRIES == 1 << 20, "include/meshenv_onpolicy_learn.h");
+
+struct MeshOnPolicyLearn : HandleBase {
+    char *table = nullptr;         // [entries][blocks][2] doubles on the device
+    char *host = nullptr;          // pinned staging of the same layout
+    size_t cap = 0;                // bytes of both
+    hipEvent_t copied = nullptr;   // the last upload from `host`
+    hipStream_t ordered = nullptr; // the stream that is known to be ordered after that upload and the zeroing of the words
+    int32_t *words = nullptr;      // the caller's: MESHENV_LEARN_WORDS words, then count[1 ..]
+    int64_t n_words = 0;
+    int entries = 0, blocks = 0;
+    int64_t claimed = 0;           // entries that the runs since the bind may reach: the sum of their K
+    bool used = false, bound = false;
+};
+
+namespace {
+
+// What meshenv_onpolicy_learn_run adds to a train(): the handle, the scalars, the history row.
+struct CountedRun {
+    MeshOnPolicyLearn *l;
+    const MeshOptimCounted *hyper;
+    double *row;
+};
+
+// The refusals of a counted run that need K, and the claim of its K entries: before anything is enqueued.
+int counted_claim(MeshOnPolicyTrain *t, const std::string &fn, const CountedRun &c, const MeshOptim *o, int program, long long K)
 {
-    if (!t) return MESHENV_E_ARG;
-    const std::string fn = "meshenv_onpolicy_train_run";
+    MeshOnPolicyLearn *l = c.l;
+    if (l->claimed + K > l->entries)
+        return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(K) + " minibatches after " + std::to_string((long long)l->claimed) +
+                       " claimed since the bind; the table has " + std::to_string(l->entries) + " entries");
+    if (l->n_words < MESHENV_LEARN_WORDS + K)
+        return fail(t, MESHENV_E_ARG, fn + ": the bound words hold fewer than " + std::to_string(MESHENV_LEARN_WORDS + K));
+    const OptProgram &P = o->prog[program];
+    const OptSeg *segs = reinterpret_cast<const OptSeg *>(P.host);
+    for (int i = 0; i < P.n_seg; i++) {
+        if (segs[i].block >= l->blocks) return fail(t, MESHENV_E_ARG, fn + ": the program reads a block that the table does not have");
+        if (!std::isfinite(c.hyper->lr[segs[i].block])) return fail(t, MESHENV_E_ARG, fn + ": lr is not finite");
+    }
+    if (l->ordered != t->stream) {           // the table was uploaded on another stream: order this one after the upload
+        DeviceGuard guard(t->device);
+        if (guard.err != hipSuccess || hipStreamWaitEvent(t->stream, l->copied, 0) != hipSuccess)
+            return fail(t, MESHENV_E_HIP, fn + ": hipStreamWaitEvent failed");
+        l->ordered = t->stream;
+    }
+    l->claimed += K;
+    l->used = true;
+    return MESHENV_OK;
+}
+
+// The body of meshenv_onpolicy_train_run (counted: NULL) and of meshenv_onpolicy_learn_run under the name `fn`.
+int onpolicy_train_enqueue(const std::string &fn, MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *o, int program,
+                           MeshRolloutBuffer *r, MeshPolicy *policy, int T, int n_envs, const float *const *in_dev,
+                           float *const *gather_dev, const void *perm_dev, int perm_bytes, int n_epochs, int batch_size, int a2c,
+                           double clip_range, float ent_coef, float vf_coef, int normalize_advantage, int clip_grad,
+                           float max_grad_norm, double target_kl, const MeshOptimScalars *scalars, int n_scalars, double *out_dev,
+                           const CountedRun *counted)
+{
     if (!g || !o || !r) return fail(t, MESHENV_E_ARG, fn + ": the gradient, optimiser and rollout-buffer handles are required");
     if (g->device != t->device || o->device != t->device || r->device != t->device || (policy && policy->device != t->device))
         return fail(t, MESHENV_E_ARG, fn + ": the handles are on different devices");
@@ -3515,7 +3573,7 @@ int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *
     if (!(target_kl >= 0.0)) return fail(t, MESHENV_E_ARG, fn + ": target_kl must be >= 0 (+inf: none), not negative or NaN");
     if (T < 1 || n_envs < 1 || (long long)T * n_envs > MESHENV_ROLLOUT_MAX_ROWS)
         return fail(t, MESHENV_E_ARG, fn + ": T >= 1, n_envs >= 1 and T * n_envs <= 2^24 - 16 are required");
-    if (!in_dev || !gather_dev || !perm_dev || !scalars || !out_dev || ((uintptr_t)out_dev & 7))
+    if (!in_dev || !gather_dev || !perm_dev || (!scalars && !counted) || !out_dev || ((uintptr_t)out_dev & 7))
         return fail(t, MESHENV_E_ARG, fn + ": in_dev, gather_dev, perm_dev, scalars and an 8-byte aligned out_dev are required");
     if (perm_bytes != 4 && perm_bytes != 8) return fail(t, MESHENV_E_ARG, fn + ": perm_bytes is 4 (int32) or 8 (int64)");
     const int rows = T * n_envs;
@@ -3523,9 +3581,23 @@ int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *
     const long long K = (long long)n_epochs * per_epoch;
     if (K > MESHENV_TRAIN_MAX_MINIBATCHES)
         return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(K) + " minibatches; at most " + std::to_string(MESHENV_TRAIN_MAX_MINIBATCHES));
-    if (n_scalars != K) return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(n_scalars) + " scalar sets for " + std::to_string(K) + " minibatches");
+    if (!counted && n_scalars != K)
+        return fail(t, MESHENV_E_ARG, fn + ": " + std::to_string(n_scalars) + " scalar sets for " + std::to_string(K) + " minibatches");
     for (int f = 0; f < MESHENV_ROLLOUT_FIELDS; f++)
         if (!in_dev[f] || !gather_dev[f]) return fail(t, MESHENV_E_ARG, fn + ": null pointer for field " + std::to_string(f));
+    OptCounted C{};
+    if (counted) {
+        const int rc = counted_claim(t, fn, *counted, o, program, K);
+        if (rc != MESHENV_OK) return rc;
+        const MeshOnPolicyLearn *l = counted->l;
+        const MeshOptimCounted &h = *counted->hyper;
+        C.table = reinterpret_cast<const double *>(l->table);
+        C.error = l->words + MESHENV_LEARN_WORD_ERROR;
+        C.entries = l->entries; C.blocks = l->blocks;
+        for (int b = 0; b < kOptBlocks; b++) { C.lr[b] = h.lr[b]; C.w1[b] = h.w1[b]; C.beta2[b] = h.beta2[b]; C.w2[b] = h.w2[b]; C.eps[b] = h.eps[b]; }
+        C.tau = h.tau; C.one_minus_tau = h.one_minus_tau;
+    }
+    int32_t *count = counted ? counted->l->words + MESHENV_LEARN_WORD_STEPS : nullptr;   // count[0] is the step word
     double *tally = reinterpret_cast<double *>(t->buf);
     int32_t *stop = reinterpret_cast<int32_t *>(t->buf + kTrTallyFloats);
     float *pg_out = t->buf + kTrTallyFloats + kTrStopFloats;
@@ -3545,18 +3617,139 @@ int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *
             TrainGate G{};
             G.stop = stop + m; G.pg_out = out_m; G.tally = tally; G.kl_limit = 1.5 * target_kl;
             G.first_of_epoch = k == 0; G.first_of_train = m == 0;
-            rc = optim_step_launch(o, program, scalars + m, &G, "meshenv_onpolicy_train_run");
+            if (counted) {
+                C.count = count + m;
+                rc = optim_step_launch(o, program, nullptr, &G, fn.c_str(), nullptr, &C);
+            } else {
+                rc = optim_step_launch(o, program, scalars + m, &G, fn.c_str());
+            }
             if (rc != MESHENV_OK) return fail(t, rc, fn + ": " + o->err);
         }
     }
     DeviceGuard guard(t->device);
-    int rc = launch(t, guard, "meshenv_onpolicy_train_run", [&] {
-        hipLaunchKernelGGL(k_train_finish, dim3(1), dim3(kTrFinishThreads), 0, t->stream, in_dev[2], in_dev[5], rows, g->log_std,
-                           (const double *)tally, out_dev);
+    int rc = launch(t, guard, fn.c_str(), [&] {
+        if (counted)
+            hipLaunchKernelGGL(k_learn_finish, dim3(1), dim3(kTrFinishThreads), 0, t->stream, in_dev[2], in_dev[5], rows, g->log_std,
+                               (const double *)tally, out_dev, count, (int)K, counted->l->words + MESHENV_LEARN_WORD_N_UPDATES);
+        else
+            hipLaunchKernelGGL(k_train_finish, dim3(1), dim3(kTrFinishThreads), 0, t->stream, in_dev[2], in_dev[5], rows, g->log_std,
+                               (const double *)tally, out_dev);
     }, "finish launch");
     if (rc != MESHENV_OK || !policy) return rc;
     rc = meshenv_policy_refresh(policy);
     return rc == MESHENV_OK ? rc : fail(t, rc, fn + ": " + policy->err);
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_onpolicy_train_run(MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *o, int program, MeshRolloutBuffer *r,
+                               MeshPolicy *policy, int T, int n_envs, const float *const *in_dev, float *const *gather_dev,
+                               const void *perm_dev, int perm_bytes, int n_epochs, int batch_size, int a2c, double clip_range,
+                               float ent_coef, float vf_coef, int normalize_advantage, int clip_grad, float max_grad_norm,
+                               double target_kl, const MeshOptimScalars *scalars, int n_scalars, double *out_dev)
+{
+    if (!t) return MESHENV_E_ARG;
+    return onpolicy_train_enqueue("meshenv_onpolicy_train_run", t, g, o, program, r, policy, T, n_envs, in_dev, gather_dev, perm_dev,
+                                  perm_bytes, n_epochs, batch_size, a2c, clip_range, ent_coef, vf_coef, normalize_advantage, clip_grad,
+                                  max_grad_norm, target_kl, scalars, n_scalars, out_dev, nullptr);
+}
+
+int meshenv_onpolicy_learn_create(int device, void *stream, MeshOnPolicyLearn **out)
+{
+    return create_handle("meshenv_onpolicy_learn_create", device, stream, out);
+}
+
+void meshenv_onpolicy_learn_destroy(MeshOnPolicyLearn *l)
+{
+    if (!l) return;
+    DeviceGuard guard(l->device);
+    (void)hipStreamSynchronize(l->stream);
+    if (l->copied) {
+        (void)hipEventSynchronize(l->copied);
+        (void)hipEventDestroy(l->copied);
+    }
+    if (l->table) (void)hipFree(l->table);
+    if (l->host) (void)hipHostFree(l->host);
+    delete l;
+}
+
+const char *meshenv_onpolicy_learn_last_error(const MeshOnPolicyLearn *l) { return last_error(l); }
+
+int meshenv_onpolicy_learn_set_stream(MeshOnPolicyLearn *l, void *stream) { return set_stream(l, stream); }
+
+int meshenv_onpolicy_learn_bind(MeshOnPolicyLearn *l, const double *table_host, int entries, int blocks, int32_t *words_dev,
+                                int64_t n_words)
+{
+    if (!l) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_onpolicy_learn_bind";
+    if (!table_host || !words_dev || ((uintptr_t)words_dev & 3))
+        return fail(l, MESHENV_E_ARG, fn + ": table_host and a 4-byte aligned words_dev are required");
+    if (entries < 1 || entries > MESHENV_LEARN_MAX_ENTRIES)
+        return fail(l, MESHENV_E_ARG, fn + ": " + std::to_string(entries) + " entries; 1 .. " + std::to_string(MESHENV_LEARN_MAX_ENTRIES));
+    if (blocks < 1 || blocks > MESHENV_OPTIM_BLOCKS) return fail(l, MESHENV_E_ARG, fn + ": blocks is 1 .. " + std::to_string(MESHENV_OPTIM_BLOCKS));
+    if (n_words < MESHENV_LEARN_WORDS + 1)
+        return fail(l, MESHENV_E_ARG, fn + ": words_dev holds the " + std::to_string(MESHENV_LEARN_WORDS) + " words and count[1 ..] of a train()");
+    const size_t doubles = (size_t)entries * blocks * 2, bytes = doubles * sizeof(double);
+    for (size_t i = 0; i < doubles; i++)
+        if (!std::isfinite(table_host[i]) || (i % 2 == 0 && table_host[i] == 0.0))
+            return fail(l, MESHENV_E_ARG, fn + ": entry " + std::to_string(i / 2 / blocks) + " is not finite or has bias_correction1 = 0");
+    DeviceGuard guard(l->device);
+    if (guard.err != hipSuccess) return fail(l, MESHENV_E_HIP, fn + ": hipSetDevice failed");
+    // the staging block is free once its last upload is done
+    if (l->copied && hipEventSynchronize(l->copied) != hipSuccess) return fail(l, MESHENV_E_HIP, fn + ": hipEventSynchronize failed");
+    l->bound = false;
+    if (bytes > l->cap) {
+        // a launch in flight reads the old table
+        if (l->used && hipStreamSynchronize(l->ordered) != hipSuccess)
+            return fail(l, MESHENV_E_HIP, fn + ": hipStreamSynchronize failed");
+        if (l->table) (void)hipFree(l->table);
+        if (l->host) (void)hipHostFree(l->host);
+        l->table = l->host = nullptr;
+        l->cap = 0;
+        if (hipMalloc((void **)&l->table, bytes) != hipSuccess || hipHostMalloc((void **)&l->host, bytes, hipHostMallocDefault) != hipSuccess ||
+            (!l->copied && hipEventCreateWithFlags(&l->copied, hipEventDisableTiming) != hipSuccess))
+            return fail(l, MESHENV_E_HIP, fn + ": allocation failed");
+        l->cap = bytes;
+    }
+    std::memcpy(l->host, table_host, bytes);
+    if (hipMemcpyAsync(l->table, l->host, bytes, hipMemcpyHostToDevice, l->stream) != hipSuccess ||
+        hipMemsetAsync(words_dev, 0, MESHENV_LEARN_WORDS * sizeof(int32_t), l->stream) != hipSuccess ||
+        hipEventRecord(l->copied, l->stream) != hipSuccess)
+        return fail(l, MESHENV_E_HIP, fn + ": upload failed");
+    l->ordered = l->stream;
+    l->words = words_dev;
+    l->n_words = n_words;
+    l->entries = entries;
+    l->blocks = blocks;
+    l->claimed = 0;
+    l->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_onpolicy_learn_run(MeshOnPolicyLearn *l, MeshOnPolicyTrain *t, MeshPpoGrad *g, MeshOptim *o, int program,
+                               MeshRolloutBuffer *r, MeshPolicy *policy, int T, int n_envs, const float *const *in_dev,
+                               float *const *gather_dev, const void *perm_dev, int perm_bytes, int n_epochs, int batch_size, int a2c,
+                               double clip_range, float ent_coef, float vf_coef, int normalize_advantage, int clip_grad,
+                               float max_grad_norm, double target_kl, const MeshOptimCounted *counted, double *history_dev,
+                               int iteration, int iterations)
+{
+    if (!l) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_onpolicy_learn_run";
+    if (!t) return fail(l, MESHENV_E_ARG, fn + ": the train handle is required");
+    if (!counted || !history_dev || ((uintptr_t)history_dev & 7))
+        return fail(l, MESHENV_E_ARG, fn + ": counted and an 8-byte aligned history_dev are required");
+    if (iterations < 1 || iteration < 0 || iteration >= iterations)
+        return fail(l, MESHENV_E_ARG, fn + ": iteration " + std::to_string(iteration) + " is outside [0, " + std::to_string(iterations) + ")");
+    if (!l->bound) return fail(l, MESHENV_E_STATE, fn + ": no table bound (meshenv_onpolicy_learn_bind)");
+    if (l->device != t->device) return fail(l, MESHENV_E_ARG, fn + ": the handles are on different devices");
+    if (l->stream != t->stream) return fail(l, MESHENV_E_STATE, fn + ": the handles are on different streams (set_stream them to one)");
+    const CountedRun run{l, counted, history_dev + (size_t)iteration * MESHENV_TRAIN_OUTPUTS};
+    const int rc = onpolicy_train_enqueue(fn, t, g, o, program, r, policy, T, n_envs, in_dev, gather_dev, perm_dev, perm_bytes, n_epochs,
+                                          batch_size, a2c, clip_range, ent_coef, vf_coef, normalize_advantage, clip_grad, max_grad_norm,
+                                          target_kl, nullptr, 0, run.row, &run);
+    return rc == MESHENV_OK ? rc : fail(l, rc, t->err);
 }
 
 }  // extern "C"

@@ -94,6 +94,52 @@ __global__ __launch_bounds__(kOptThreads) void k_optim_step_gated(const OptSeg *
     else opt_chunk<kOptAdamPolyak>(s, c, job.first);
 }
 
+// k_optim_step_counted (include/meshenv_onpolicy_learn.h) is k_optim_step_gated without the host-computed
+// OptScalars: how many steps the device has applied is a word on the device, so the Adam bias corrections of a step are looked
+// up by it.  count[K + 1] (int32) is a chain like stop[]: count[m] is the number of steps applied since the table's origin before
+// minibatch m, read by every workgroup; thread 0 of workgroup 0 writes count[m + 1] = count[m] + (stopped ? 0 : 1), which only
+// later launches read.  table[entries][blocks][2] (doubles) holds bias_correction1 and bias_correction2_sqrt of the
+// (j + 1)-th step after the origin, formed by the host as adam_scalars forms them; lr arrives as a double and
+//     step_size = (float)(lr / bias_correction1)           bc2_sqrt = (float)bias_correction2_sqrt
+// are the IEEE division and the round-to-nearest conversions that the host's lr / bc1 stored into a float are, so an applied
+// step has k_optim_step_gated's bits.  A count outside [0, entries) never indexes the table: the launch behaves as stopped and
+// thread 0 of workgroup 0 sets *error, which the host reads with the count.
+struct OptCounted {
+    int32_t *count;         // &count[m]: [0] is read, [1] is written
+    const double *table;    // [entries][blocks][2]
+    int32_t *error;         // set to 1 by a launch whose count is outside the table
+    int32_t entries, blocks;
+    double lr[kOptBlocks];
+    float w1[kOptBlocks], beta2[kOptBlocks], w2[kOptBlocks], eps[kOptBlocks];
+    float tau, one_minus_tau;
+};
+
+__global__ __launch_bounds__(kOptThreads) void k_optim_step_counted(const OptSeg *__restrict__ segs, const OptJob *__restrict__ jobs,
+                                                                     OptCounted C, TrainGate G)
+{
+    const bool was_stopped = G.stop[0] != 0;
+    const int32_t n = C.count[0];
+    const bool outside = n < 0 || n >= C.entries;
+    const bool stopped = was_stopped || outside || (double)G.pg_out[4] > G.kl_limit;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        train_tally(G, was_stopped, stopped);
+        C.count[1] = n + (stopped ? 0 : 1);
+        if (outside) *C.error = 1;
+    }
+    if (stopped) return;
+    const OptJob job = jobs[blockIdx.x];
+    const OptSeg s = segs[job.seg];
+    const int b = s.block;
+    const double *e = C.table + ((size_t)n * C.blocks + b) * 2;
+    OptCoef c;
+    c.neg_step = -(float)(C.lr[b] / e[0]); c.bc2_sqrt = (float)e[1]; c.w1 = C.w1[b]; c.beta2 = C.beta2[b]; c.w2 = C.w2[b];
+    c.eps = C.eps[b]; c.tau = C.tau; c.omt = C.one_minus_tau;
+    if (s.op == kOptAdam) opt_chunk<kOptAdam>(s, c, job.first);
+    else if (s.op == kOptPolyak) opt_chunk<kOptPolyak>(s, c, job.first);
+    else if (s.op == kOptRmsprop) opt_chunk<kOptRmsprop>(s, c, job.first);
+    else opt_chunk<kOptAdamPolyak>(s, c, job.first);
+}
+
 // pg_block_sum over doubles: the sum to every thread, in a fixed order
 __device__ __forceinline__ double train_block_sum(double s, double *red, int t)
 {
@@ -108,9 +154,9 @@ __device__ __forceinline__ double train_block_sum(double s, double *red, int t)
     return r;
 }
 
-__global__ void __launch_bounds__(kTrFinishThreads)
-k_train_finish(const float *__restrict__ values, const float *__restrict__ returns, int rows, const float *__restrict__ log_std,
-               const double *__restrict__ tally, double *__restrict__ out)
+// The whole of k_train_finish by its one workgroup; true for the thread that wrote the outputs
+__device__ __forceinline__ bool train_finish(const float *__restrict__ values, const float *__restrict__ returns, int rows,
+                                             const float *__restrict__ log_std, const double *__restrict__ tally, double *__restrict__ out)
 {
     __shared__ double red[kTrFinishThreads];
     const int t = threadIdx.x;
@@ -132,7 +178,7 @@ k_train_finish(const float *__restrict__ values, const float *__restrict__ retur
     }
     const double var_r = train_block_sum(sr, red, t) / (double)rows;
     const double var_d = train_block_sum(sd, red, t) / (double)rows;
-    if (t != 0) return;
+    if (t != 0) return false;
     const float e0 = (float)exp((double)log_std[0]), e1 = (float)exp((double)log_std[1]), e2 = (float)exp((double)log_std[2]);
     const float std_mean = ((e0 + e1) + e2) / 3.0f;
     const double n = tally[kTlEvaluated];
@@ -148,6 +194,26 @@ k_train_finish(const float *__restrict__ values, const float *__restrict__ retur
     out[9] = tally[kTlEpochs];
     out[10] = n;
     out[11] = tally[kTlNorm];
+    return true;
+}
+
+__global__ void __launch_bounds__(kTrFinishThreads)
+k_train_finish(const float *__restrict__ values, const float *__restrict__ returns, int rows, const float *__restrict__ log_std,
+               const double *__restrict__ tally, double *__restrict__ out)
+{
+    train_finish(values, returns, rows, log_std, tally, out);
+}
+
+// k_train_finish for a counted train() (k_optim_step_counted): the same outputs into a row of the learn()'s history, and the
+// hand-over to the next train() of the queue: count[K] into count[0], epochs_run added to the running _n_updates word.  One
+// workgroup; the words are read and written by thread 0 alone, after every step launch of this train() and before any of the next.
+__global__ void __launch_bounds__(kTrFinishThreads)
+k_learn_finish(const float *__restrict__ values, const float *__restrict__ returns, int rows, const float *__restrict__ log_std,
+               const double *__restrict__ tally, double *__restrict__ out, int32_t *count, int K, int32_t *n_updates)
+{
+    if (!train_finish(values, returns, rows, log_std, tally, out)) return;
+    count[0] = count[K];
+    *n_updates = *n_updates + (int32_t)tally[kTlEpochs];
 }
 
 }  // namespace meshenv

@@ -263,7 +263,7 @@ class FusedOnPolicyTrain(Handle):
             return t.randperm(rows, device=self.device).unsqueeze(0)
         return t.stack([t.randperm(rows, device=self.device) for _ in range(n_epochs)])
 
-    def train(self, out, perms=None) -> TrainLogs:
+    def train(self, out, perms=None, counted=None) -> TrainLogs:
         """The whole of ``train()`` on the rollout ``out`` (the dict ``collect_rollout(..., gamma=...)`` returns; references
         are kept, nothing is copied).  perms: None draws one ``torch.randperm(rows)`` per epoch on the device; else an int32 or
         int64 tensor [n_epochs, rows] (``np.random.permutation`` per epoch reproduces SB3's minibatches).
@@ -272,7 +272,12 @@ class FusedOnPolicyTrain(Handle):
         this one, after the C call and on a stream of their own, while the device works through the queue:
         ``torch.randperm`` costs the host about as much as everything else in front of the call together.  They are used when the next call has the same rows, epochs
         and stream, and drawn again otherwise.  A ``torch.manual_seed`` between two calls therefore reaches the permutations
-        one ``train()`` later; set ``draw_ahead = False`` (or pass ``perms``) where that matters."""
+        one ``train()`` later; set ``draw_ahead = False`` (or pass ``perms``) where that matters.
+
+        counted: a bound ``StepCounter`` (onpolicy_learn.py) makes this a COUNTED train(): the optimiser steps look their Adam
+        scalars up by the counter's device-resident step count, the outputs go to the counter's next history row, and
+        nothing is read back: ``step`` and ``_n_updates`` are the counter's to write at its one read-back (``StepCounter.read``).
+        It refuses, before anything is enqueued, a train() whose K minibatches the counter's table has no entries left for."""
         t, model, pg, fo, rb = self._torch, self.model, self.pg, self.fo, self.rb
         hp = hyper(model)
         update_learning_rate(model, fo.spec.policy)
@@ -291,6 +296,8 @@ class FusedOnPolicyTrain(Handle):
         mgn = 0.0 if hp["max_grad_norm"] is None else N.finite(hp["max_grad_norm"], "max_grad_norm")
         if hp["max_grad_norm"] is not None and not mgn > 0.0:
             raise ValueError(f"max_grad_norm must be > 0 (or None), got {hp['max_grad_norm']!r}")
+        if counted is not None:
+            counted.check(self, K)
         stream = t.cuda.current_stream(self.device).cuda_stream
         drawn = perms is None
         if drawn:
@@ -307,20 +314,23 @@ class FusedOnPolicyTrain(Handle):
         gathered = rb._outputs()
         # prepare's checks once; the K scalar sets from the state as it is
         plan, key = self._prepared()
-        for h in (self, pg, fo, rb, self.policy):
+        for h in (self, pg, fo, rb, self.policy, counted):
             if h is not None and h._stream != stream:
                 h._bind_stream()
         if fo._bound.get("policy") != key:
             fo._bind(plan, key)
-        scalars, values = scalar_sets(fo.spec, plan, K)
-        out_dev = t.empty(_capi.TRAIN_OUTPUTS, dtype=t.float64, device=self.device)
         target_kl = hp["target_kl"]
-        rc = self._L.meshenv_onpolicy_train_run(
-            self._h, pg._h, fo._h, PROGRAMS.index("policy"), rb._h, None if self.policy is None else self.policy._h, rb.T, rb.n_envs,
-            self._ptrs(rb._in), self._ptrs(gathered), perms.data_ptr(), perms.element_size(), n_epochs, batch, 1 if a2c else 0,
-            C.c_double(clip), C.c_float(ent), C.c_float(vf), 1 if hp["normalize_advantage"] else 0, 0 if hp["max_grad_norm"] is None else 1,
-            C.c_float(mgn), C.c_double(math.inf if target_kl is None else target_kl), scalars, K, out_dev.data_ptr())
-        self._check(rc, "meshenv_onpolicy_train_run")
+        head = (self._h, pg._h, fo._h, PROGRAMS.index("policy"), rb._h, None if self.policy is None else self.policy._h, rb.T, rb.n_envs,
+                self._ptrs(rb._in), self._ptrs(gathered), perms.data_ptr(), perms.element_size(), n_epochs, batch, 1 if a2c else 0,
+                C.c_double(clip), C.c_float(ent), C.c_float(vf), 1 if hp["normalize_advantage"] else 0, 0 if hp["max_grad_norm"] is None else 1,
+                C.c_float(mgn), C.c_double(math.inf if target_kl is None else target_kl))
+        if counted is not None:
+            out_dev = counted.run(self, head, fo.spec, plan, K)
+        else:
+            scalars, values = scalar_sets(fo.spec, plan, K)
+            out_dev = t.empty(_capi.TRAIN_OUTPUTS, dtype=t.float64, device=self.device)
+            rc = self._L.meshenv_onpolicy_train_run(*head, scalars, K, out_dev.data_ptr())
+            self._check(rc, "meshenv_onpolicy_train_run")
         self.calls += 1
         rb.launches += n_epochs
         if drawn and self.draw_ahead:                    # the next train()'s permutations, while the device works through the queue
@@ -334,7 +344,10 @@ class FusedOnPolicyTrain(Handle):
             nxt.record_stream(main)                      # allocated on the side stream, read by the next train() on this one
             self._ahead = ((rows, n_epochs, stream), nxt, done)
         logs = TrainLogs(out_dev, a2c, hp["clip_range"], model)
-        if target_kl is None:                            # known on the host: nothing is read back
+        if counted is not None:                          # step and _n_updates: at the counter's one read-back
+            counted.pending.append(logs)
+            return logs
+        if target_kl is None:                          # known on the host: nothing is read back
             steps, epochs = K, n_epochs
         else:                                            # ONE read-back per train(), after the queue drains
             v = logs.values()

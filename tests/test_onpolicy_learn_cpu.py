@@ -1,0 +1,207 @@
+"""CPU: the host half of ``FusedOnPolicyLearn`` / ``StepCounter`` (reinforcementlearning4meshgeneration_amd/onpolicy_learn.py): the
+table of bias corrections against the scalars ``scalar_sets`` stores (bit for bit), the plan against a literal restatement of
+SB3's while-loop, the segments, every refusal (all before any device call: this file runs without a GPU), and the packaging."""
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+import on_policy_stubs as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _L():
+    from reinforcementlearning4meshgeneration_amd import onpolicy_learn
+    return onpolicy_learn
+
+
+def _model(kind="ppo", **attrs):
+    model, _ = S.model(kind)
+    model.n_steps, model.num_timesteps, model._n_updates = 3, 0, 0
+    for k, v in attrs.items():
+        setattr(model, k, v)
+    return model
+
+
+# ----------------------------------------------------------------------------------------------------------- 1. the table
+def _lr_schedule(progress):
+    return 2.5e-4 * progress
+
+
+@pytest.mark.parametrize("step0", [0, 7, 2 ** 24 - 3])
+@pytest.mark.parametrize("lr", [3e-4, 1e-3, 7e-5, _lr_schedule(0.375)])
+def test_table_entries_round_to_the_scalars_scalar_sets_stores(step0, lr):
+    """For every entry, np.float32(lr / bc1) and np.float32(bc2s) are the step_size and bc2_sqrt that scalar_sets stores for the
+    same step.  Past 2^24 a float32 ``step += 1`` no longer moves: the table repeats its last entry as scalar_sets does."""
+    import torch
+
+    from reinforcementlearning4meshgeneration_amd import onpolicy_train as T
+    from reinforcementlearning4meshgeneration_amd.optim_step import Plan
+    L = _L()
+    entries = 9
+    beta1, beta2 = 0.9, 0.999
+    group = dict(lr=lr, betas=(beta1, beta2), eps=1e-5)
+    plan = Plan("policy", [], [(group, [torch.tensor(float(step0), dtype=torch.float32)])])
+    arr, values = T.scalar_sets(types.SimpleNamespace(tau=0.005), plan, entries)
+    table = L.bias_table(float(step0), entries, beta1, beta2)
+    assert len(table) == entries and values[0] == T.step_values(float(step0), entries)
+    for j, (bc1, bc2s) in enumerate(table):
+        assert isinstance(bc1, float) and isinstance(bc2s, float)
+        want_step, want_bc2 = np.float32(arr[j].step_size[0]), np.float32(arr[j].bc2_sqrt[0])
+        assert np.float32(lr / bc1).view(np.int32) == want_step.view(np.int32), (step0, lr, j)
+        assert np.float32(bc2s).view(np.int32) == want_bc2.view(np.int32), (step0, lr, j)
+    if step0 == 2 ** 24 - 3:
+        assert values[0][3:] == [float(2 ** 24)] * 7 and table[2] == table[8]      # the float32 step saturates
+
+
+# ----------------------------------------------------------------------------------------------------------- 2. the plan
+def _sb3_loop(num_timesteps, total_timesteps, n_envs, n_steps):
+    """SB3's OnPolicyAlgorithm.learn, literally: _setup_learn(reset_num_timesteps=False) has made the target absolute."""
+    out = []
+    while num_timesteps < total_timesteps:
+        before = num_timesteps
+        for _ in range(n_steps):                     # collect_rollouts: self.num_timesteps += env.num_envs per step
+            num_timesteps += n_envs
+        progress = 1.0 - float(num_timesteps) / float(total_timesteps)
+        out.append((before, num_timesteps, progress))
+    return out
+
+
+@pytest.mark.parametrize("extra", [-1, 0, 1])
+def test_plan_is_sb3s_loop_below_at_and_above_a_multiple(extra):
+    L = _L()
+    n, T = 11, 3
+    total = 4 * n * T + extra
+    got = L.plan(0, total, n, T)
+    assert got == _sb3_loop(0, total, n, T)
+    assert len(got) == (5 if extra > 0 else 4) and got[-1][1] >= total and got[-1][0] < total
+    assert L.plan(0, 0, n, T) == []
+
+
+def test_plan_of_a_continued_learn():
+    L = _L()
+    n, T = 11, 3
+    first = L.plan(0, 100, n, T)
+    num = first[-1][1]
+    assert num == 132                                                    # four collects: 99 < 100
+    second = L.plan(num, num + 50, n, T)
+    assert second == _sb3_loop(num, num + 50, n, T) and [b for b, _, _ in second] == [132, 165]
+    assert second[-1][2] == 1.0 - 198.0 / 182.0                           # negative: the overshoot, as SB3 leaves it
+
+
+def test_segments_hold_whole_trains():
+    L = _L()
+    assert L.segments(5, 15, 2 ** 20) == [(0, 5)]
+    assert L.segments(5, 15, 30) == [(0, 2), (2, 2), (4, 1)]
+    assert L.segments(5, 15, 7) == [(i, 1) for i in range(5)]              # a cap below K: one train() per segment
+    assert L.segments(0, 15, 7) == []
+    assert L.TABLE_CAP == 2 ** 20
+    model = _model(n_epochs=3, batch_size=8)
+    assert L.minibatches(model, 33) == 15 and L.minibatches(_model("a2c"), 33) == 1
+
+
+# ----------------------------------------------------------------------------------------------------------- 3. refusals
+def test_spec_refusals_name_the_attribute():
+    L = _L()
+    spec = L.OnPolicyLearnSpec(_model(), 11)
+    assert (spec.n_steps, spec.n_envs, spec.rows) == (3, 11, 33) and not spec.counted()
+    assert L.OnPolicyLearnSpec(_model(target_kl=0.01), 11).counted() and not L.OnPolicyLearnSpec(_model("a2c", target_kl=0.01), 11).counted()
+    model = _model()
+    model.policy.use_sde = True
+    with pytest.raises(ValueError, match="use_sde"):
+        L.OnPolicyLearnSpec(model, 11)
+    with pytest.raises(ValueError, match="use_sde"):
+        L.OnPolicyLearnSpec(_model(use_sde=True), 11)
+    with pytest.raises(ValueError, match="auto_reset"):
+        L.OnPolicyLearnSpec(_model(), 11, auto_reset=False)
+    model = _model()
+    del model.n_steps
+    with pytest.raises(ValueError, match="n_steps"):
+        L.OnPolicyLearnSpec(model, 11)
+    with pytest.raises(ValueError, match="n_steps must be a positive int"):
+        L.OnPolicyLearnSpec(_model(n_steps=0), 11)
+    with pytest.raises(ValueError, match="ROLLOUT_MAX_ROWS"):
+        L.OnPolicyLearnSpec(_model(n_steps=2 ** 12), 2 ** 12)
+    with pytest.raises(ValueError, match="not an actor-critic policy"):
+        L.OnPolicyLearnSpec(types.SimpleNamespace(policy=types.SimpleNamespace(actor=object()), n_steps=3), 11)
+    with pytest.raises(ValueError, match="not an actor-critic policy"):
+        L.OnPolicyLearnSpec(_model(actor=object()), 11)
+    with pytest.raises(ValueError, match="target_kl"):
+        L.OnPolicyLearnSpec(_model(target_kl=-1.0), 11)
+    with pytest.raises(ValueError, match="num_timesteps"):
+        L.OnPolicyLearnSpec(_model(num_timesteps=-1), 11).num_timesteps()
+
+
+def test_foreign_policy_and_train_are_refused():
+    from reinforcementlearning4meshgeneration_amd import sb3_nets as N
+    from reinforcementlearning4meshgeneration_amd.policy import HIDDEN_WIDTHS, KIND_ACTOR_CRITIC, KIND_DETERMINISTIC
+    L = _L()
+    model, other = _model(), _model()
+    live = lambda m: N.actor_critic_live(m, widths=HIDDEN_WIDTHS)[2]   # noqa: E731
+    ac = types.SimpleNamespace(kind=KIND_ACTOR_CRITIC)
+    mine = types.SimpleNamespace(spec=ac, _live=live(model))
+    unbound = types.SimpleNamespace(spec=ac, _live=None)
+    L.check_handles(model, None, None)
+    L.check_handles(model, mine, None)
+    L.check_handles(model, unbound, None)
+    L.check_handles(model, mine, types.SimpleNamespace(model=model, policy=mine))
+    with pytest.raises(ValueError, match="not an actor-critic FusedPolicy"):
+        L.check_handles(model, types.SimpleNamespace(spec=types.SimpleNamespace(kind=KIND_DETERMINISTIC), _live=None), None)
+    with pytest.raises(ValueError, match="another model's parameters"):
+        L.check_handles(model, types.SimpleNamespace(spec=ac, _live=live(other)), None)
+    with pytest.raises(ValueError, match="train drives another model"):
+        L.check_handles(model, mine, types.SimpleNamespace(model=other, policy=mine))
+    with pytest.raises(ValueError, match="another rollout policy"):
+        L.check_handles(model, mine, types.SimpleNamespace(model=model, policy=unbound))
+    with pytest.raises(ValueError, match="no rollout policy"):
+        L.check_handles(model, None, types.SimpleNamespace(model=model, policy=None))
+
+
+def test_from_sb3_refuses_before_any_device_call():
+    """The venv is a stand-in with no device behind it: every refusal below is raised before anything touches one."""
+    L = _L()
+    venv = types.SimpleNamespace(num_envs=11, auto_reset=True)
+    with pytest.raises(ValueError, match="use_sde"):
+        L.FusedOnPolicyLearn.from_sb3(_model(use_sde=True), venv)
+    with pytest.raises(ValueError, match="auto_reset"):
+        L.FusedOnPolicyLearn.from_sb3(_model(), types.SimpleNamespace(num_envs=11, auto_reset=False))
+    model = _model()
+    foreign = types.SimpleNamespace(model=_model(), policy=None)
+    with pytest.raises(ValueError, match="train drives another model"):
+        L.FusedOnPolicyLearn.from_sb3(model, venv, train=foreign)
+
+
+# ----------------------------------------------------------------------------------------------------------- packaging
+def test_exports_declarations_and_header():
+    import reinforcementlearning4meshgeneration_amd as pkg
+    from reinforcementlearning4meshgeneration_amd import _capi, build
+    L = _L()
+    for k in ("FusedOnPolicyLearn", "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter"):
+        assert k in pkg.__all__ and getattr(pkg, k) is getattr(L, k)
+    assert L.StepCounter.PREFIX == "meshenv_onpolicy_learn"
+    names = _capi.EXPORTS_ONPOLICY_LEARN
+    assert sorted(names) == sorted("meshenv_onpolicy_learn_" + s for s in ("create", "destroy", "set_stream", "last_error", "bind", "run"))
+    assert "meshenv_onpolicy_learn.h" in build.PUBLIC_HEADERS
+    header = open(os.path.join(ROOT, "include", "meshenv_onpolicy_learn.h")).read()
+    declared = set(re.findall(r"\b(meshenv_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
+    assert declared == set(names)
+    defines = dict(re.findall(r"#define\s+(MESHENV_[A-Z_]+)\s+(\d+)", header))
+    assert int(defines["MESHENV_LEARN_WORDS"]) == _capi.LEARN_WORDS == 3
+    assert int(defines["MESHENV_LEARN_MAX_ENTRIES"]) == _capi.LEARN_MAX_ENTRIES == 2 ** 20
+    words = dict(re.findall(r"MESHENV_LEARN_WORD_([A-Z_]+) = (\d+)", header))
+    assert (int(words["N_UPDATES"]), int(words["ERROR"]), int(words["STEPS"])) == \
+        (_capi.LEARN_WORD_N_UPDATES, _capi.LEARN_WORD_ERROR, _capi.LEARN_WORD_STEPS)
+    kernels = open(os.path.join(ROOT, "reinforcementlearning4meshgeneration_amd", "csrc", "meshenv_onpolicy_train.h")).read()
+    assert "k_optim_step_counted" in kernels and "k_learn_finish" in kernels
+    lib = _capi.load()
+    for name in names:
+        assert hasattr(lib, name), name
+    import ctypes as C
+    assert C.sizeof(_capi.MeshOptimCounted) == 8 * 4 + 4 * 4 * 4 + 8
+    assert lib.meshenv_onpolicy_learn_run.argtypes[1:23] == lib.meshenv_onpolicy_train_run.argtypes[:22]
+    assert lib.meshenv_onpolicy_learn_bind(None, None, 1, 1, None, 4) == _capi.E_ARG           # a NULL handle is refused
+    assert lib.meshenv_onpolicy_learn_run(None, None, None, None, 0, None, None, 0, 0, None, None, None, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0, 0,
+                                          0.0, 0.0, None, None, 0, 0) == _capi.E_ARG
