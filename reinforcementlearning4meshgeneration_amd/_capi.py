@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -140,6 +140,11 @@ EXPORTS_EVAL_CALLBACK = [
 EVAL_ROW_DOUBLES, EVAL_STATE_DOUBLES, KEEP_BEST_MAX_ENTRIES = 9, 4, 64
 EVAL_COLUMNS = ("num_timesteps", "mean_reward", "std_reward", "mean_ep_length", "recorded", "short", "complete_rate",
                 "mean_n_elements", "improved")
+
+# every symbol include/meshenv_topology.h declares: the topology report of the generated meshes, and its attachment to the tally
+EXPORTS_TOPOLOGY = ["meshenv_mesh_topology", "meshenv_eval_set_topology"]
+TOPOLOGY_DIM = 16
+TOPO_OK, TOPO_MASKED, TOPO_LOG_OVERFLOW, TOPO_DEGREE, TOPO_NOT_ARCHIVED = 0, 1, 2, 3, 4
 
 
 class MeshKeepEntry(C.Structure):
@@ -324,6 +329,8 @@ def load():
     L.meshenv_evaluate_queued.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, evp]
     L.meshenv_eval_reduce.argtypes = [vp, C.c_int, C.c_int, evp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
     L.meshenv_keep_best.argtypes = [vp, C.POINTER(MeshKeepEntry), C.c_int, vp, C.c_int64, vp]
+    L.meshenv_mesh_topology.argtypes, L.meshenv_mesh_topology.restype = [vp, C.c_int, vp, vp, vp], C.c_int
+    L.meshenv_eval_set_topology.argtypes, L.meshenv_eval_set_topology.restype = [vp, vp], C.c_int
     for name in ("meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_uniform_actions", "meshenv_step_actions_multi",
                  "meshenv_episode_stats_update", "meshenv_evaluate_queued", "meshenv_eval_reduce", "meshenv_keep_best"):
         getattr(L, name).restype = C.c_int

@@ -13,6 +13,7 @@
 #include "../../include/meshenv_offpolicy_train.h"
 #include "../../include/meshenv_offpolicy_learn.h"
 #include "../../include/meshenv_eval_callback.h"
+#include "../../include/meshenv_topology.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -47,6 +48,7 @@
 #include "meshenv_offpolicy_train.h"
 #include "meshenv_learn.h"
 #include "meshenv_eval_callback.h"
+#include "meshenv_topology.h"
 
 using namespace meshenv;
 
@@ -190,6 +192,7 @@ struct MeshEnv {
     double *eval_reward = nullptr;
     uint8_t *eval_done = nullptr, *eval_complete = nullptr;
     int32_t *eval_host = nullptr;
+    int32_t *eval_topology = nullptr;   // the caller's [sum of target][16] buffer (meshenv_eval_set_topology), NULL = detached
 };
 
 namespace {
@@ -1522,6 +1525,40 @@ int meshenv_element_quality(MeshEnv *h, int which, double *elem_dev, double *sta
     return MESHENV_OK;
 }
 
+static_assert(MESHENV_TOPOLOGY_DIM == kTopologyDim && MESHENV_TOPO_MASKED == kTopoMasked && MESHENV_TOPO_LOG_OVERFLOW == kTopoLogOverflow &&
+              MESHENV_TOPO_DEGREE == kTopoDegree && MESHENV_TOPO_NOT_ARCHIVED == kTopoNotArchived,
+              "include/meshenv_topology.h and csrc/meshenv_topology.h disagree");
+
+int meshenv_mesh_topology(MeshEnv *h, int which, const uint8_t *mask_dev, int32_t *report_dev, uint8_t *valence_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (which != 0 && which != 1) return fail_arg(h, "meshenv_mesh_topology: which must be 0 (running) or 1 (archived)");
+    if (!report_dev) return fail_arg(h, "meshenv_mesh_topology: report_dev is NULL");
+    const int log_cap = h->S.prm.log_cap;
+    if (log_cap <= 0) {
+        h->err = "meshenv_mesh_topology: handle was created with log_capacity = 0 (the mesh is read from the element log)";
+        return MESHENV_E_STATE;
+    }
+    if (h->max_ring + log_cap > 65535)
+        return fail_arg(h, "meshenv_mesh_topology: max ring + log_capacity must be <= 65535 (16-bit vertex indices)");
+    MESHENV_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_mesh_topology, dim3(h->n_envs), dim3(64), 0, h->stream, h->S, which, mask_dev, report_dev, valence_dev,
+                       h->max_ring + log_cap);
+    HIP_TRY(h, hipGetLastError());
+    return MESHENV_OK;
+}
+
+int meshenv_eval_set_topology(MeshEnv *h, int32_t *ep_topology_dev)
+{
+    if (!h) return MESHENV_E_ARG;
+    if (ep_topology_dev && (h->S.prm.log_cap <= 0 || h->max_ring + h->S.prm.log_cap > 65535)) {
+        h->err = "meshenv_eval_set_topology: needs a handle created with 0 < log_capacity <= 65535 - max ring";
+        return MESHENV_E_STATE;
+    }
+    h->eval_topology = ep_topology_dev;
+    return MESHENV_OK;
+}
+
 int meshenv_quad_quality(MeshEnv *h, int n, const double *quad_xy_dev, int index, double *out_dev)
 {
     if (!h || n < 0 || (n > 0 && (!quad_xy_dev || !out_dev))) return MESHENV_E_ARG;
@@ -2415,6 +2452,11 @@ int eval_tally_launch(MeshEnv *h, EvalTallyArgs A, int step, const double *rewar
     A.step = step; A.reward = reward; A.done = done; A.complete = complete;
     hipLaunchKernelGGL(k_eval_tally, dim3((h->n_envs + 63) / 64), dim3(64 * kEvalWaves), 0, h->stream, h->S, A);
     HIP_TRY(h, hipGetLastError());
+    if (h->eval_topology) {   // include/meshenv_topology.h: the topology of the meshes this step recorded
+        hipLaunchKernelGGL(k_eval_topology, dim3((h->n_envs + 63) / 64), dim3(64 * kEvalWaves), 0, h->stream, h->S, A,
+                           h->eval_topology);
+        HIP_TRY(h, hipGetLastError());
+    }
     return MESHENV_OK;
 }
 

@@ -46,6 +46,21 @@ class EpisodeTools:
         rec, _, cnt = self._vec.element_quality("current")
         return rec[self._k, :int(cnt[self._k])].cpu().numpy()
 
+    def topology(self, which="last"):
+        """{field: value} of this env's topology report (MeshVecEnv.TOPOLOGY_FIELDS: status, n_elements, n_vertices,
+        singularity, the valence bins, the edge counts) -- which="last": the archived finished episode, "current": the running
+        one.  Launched with a mask that selects this env alone: a call per env does no whole-batch work."""
+        vec = self._vec
+        mask = vec._torch.zeros(vec.num_envs, dtype=vec._torch.uint8, device=vec.device)
+        mask[self._k] = 1
+        report, _ = vec.mesh_topology(which, mask=mask)
+        return {name: int(v) for name, v in zip(vec.TOPOLOGY_FIELDS, report[self._k].cpu().numpy())}
+
+    def singularity(self, which="last"):
+        """`Singularity` of general/post_processing.py:145-151 for this env's mesh: the vertices contained in elements whose
+        element count is not 1, 2 or 4."""
+        return self.topology(which)["singularity"]
+
     # ------------------------------------------------------------------ get_quality / save_meshes / save_samples
     def get_quality(self, element, index=0):
         """MeshGeneration.get_quality(element, index), general/mesh.py:1728-1747 -- e.g. ``env.get_quality(env.generated_meshes[i],

@@ -21,6 +21,37 @@ import numpy as np
 
 QUALITY_MEASURES = ("min_angle_deg", "max_angle_deg", "scaled_jacobian", "stretch", "taper", "robust", "area", "default")
 FLAG_COMPLETE, FLAG_OVERFLOW = 1, 2
+# the 16 words of a topology report (include/meshenv_topology.h)
+TOPOLOGY_FIELDS = ("status", "n_elements", "n_vertices", "singularity", "valence_1", "valence_2", "valence_3", "valence_4",
+                   "valence_5", "valence_6", "valence_7", "valence_8_or_more", "n_edges", "boundary_edges", "nonmanifold_edges",
+                   "front_edges")
+
+
+def topology_report(reports) -> dict:
+    """The topology column of the reference's results table (general/post_processing.py:93-161: Singularity, num_vertices,
+    num_elements per mesh) over a batch of reports [n, 16] (MeshVecEnv.mesh_topology, EvalResult.topology).
+
+    Counted: the rows with status 0 and n_elements > 0.  meshes, elements, vertices (sums); singularity = dict(average, std,
+    min, max, total) over the meshes (std: numpy's population value); singular_fraction = total singular / total vertices;
+    valence_histogram = the summed bins (1 .. 7, >= 8 elements per vertex); closed = meshes with front_edges == 0;
+    nonmanifold = meshes with nonmanifold_edges > 0; euler = [V - E + F per mesh]; skipped = {status: rows} of the rows with
+    a status other than 0."""
+    r = np.asarray(reports, dtype=np.int64).reshape(-1, len(TOPOLOGY_FIELDS))
+    live = (r[:, 0] == 0) & (r[:, 1] > 0)
+    m = r[live]
+    sing = m[:, 3]
+    have = len(m) > 0
+    verts = int(m[:, 2].sum())
+    bad, counts = np.unique(r[r[:, 0] != 0, 0], return_counts=True)
+    return {"meshes": int(live.sum()), "elements": int(m[:, 1].sum()), "vertices": verts,
+            "singularity": dict(average=float(sing.mean()) if have else float("nan"),
+                                std=float(sing.std()) if have else float("nan"),
+                                min=int(sing.min()) if have else 0, max=int(sing.max()) if have else 0, total=int(sing.sum())),
+            "singular_fraction": float(sing.sum()) / verts if verts else float("nan"),
+            "valence_histogram": [int(x) for x in m[:, 4:12].sum(axis=0)],
+            "closed": int((m[:, 15] == 0).sum()), "nonmanifold": int((m[:, 14] > 0).sum()),
+            "euler": [int(x) for x in m[:, 2] - m[:, 12] + m[:, 1]],
+            "skipped": {int(k): int(c) for k, c in zip(bad, counts)}}
 
 
 def episode_targets(n_envs: int, n_eval_episodes: Optional[int] = None, episodes_per_env=None) -> np.ndarray:
@@ -53,7 +84,9 @@ class EvalResult:
     float32 rewards), reward_raw = float64 sum of the float64 rewards; complete, overflow (the element log outgrew
     log_capacity); n_elements (0: the episode ended without an element; -1: no element log); archive = the
     ``get_last_episode(env)["episodes"]`` value of the finished mesh (0: none); quality [N, 8, 4] min / mean / max / variance
-    of the QUALITY_MEASURES (None when not requested).  steps = vector steps run; finished = every env reached its target."""
+    of the QUALITY_MEASURES (None when not requested).  steps = vector steps run; finished = every env reached its target.
+    topology [N, 16] int32: the TOPOLOGY_FIELDS of each finished mesh, scored at the tally like quality (None when not
+    requested; 16 zeros for an episode without elements)."""
     env: np.ndarray
     domain: np.ndarray
     step: np.ndarray
@@ -68,23 +101,26 @@ class EvalResult:
     targets: np.ndarray
     steps: int
     finished: bool
+    topology: Optional[np.ndarray] = None
 
     @classmethod
     def from_records(cls, rec: dict, targets, steps: int, finished: bool) -> "EvalResult":
         """rec: per-episode arrays in any order (keys env, domain, step, length, return, return_raw, flags, n_elements and
-        optionally archive, quality); sorted here by (step, env)."""
+        optionally archive, quality, topology); sorted here by (step, env)."""
         order = np.lexsort((np.asarray(rec["env"]), np.asarray(rec["step"])))
         take = lambda k, dt: np.asarray(rec[k])[order].astype(dt)   # noqa: E731
         flags = take("flags", np.int32)
         n = len(order)
         q = rec.get("quality")
+        tp = rec.get("topology")
         return cls(env=take("env", np.int32), domain=take("domain", np.int32), step=take("step", np.int64),
                    length=take("length", np.int64), reward=take("return", np.float64),
                    reward_raw=take("return_raw", np.float64), complete=(flags & FLAG_COMPLETE) != 0,
                    overflow=(flags & FLAG_OVERFLOW) != 0, n_elements=take("n_elements", np.int32),
                    archive=take("archive", np.int32) if rec.get("archive") is not None else np.zeros(n, np.int32),
                    quality=None if q is None else np.asarray(q, np.float64).reshape(-1, 8, 4)[order],
-                   targets=np.asarray(targets, np.int32), steps=int(steps), finished=bool(finished))
+                   targets=np.asarray(targets, np.int32), steps=int(steps), finished=bool(finished),
+                   topology=None if tp is None else np.asarray(tp, np.int32).reshape(-1, len(TOPOLOGY_FIELDS))[order])
 
     def __len__(self):
         return len(self.env)
@@ -130,6 +166,13 @@ class EvalResult:
                 out[name] = dict(average=float(st[:, 1].mean()), std=float(np.sqrt(np.abs(st[:, 3])).mean()),
                                  min=float(st[:, 0].min()), max=float(st[:, 2].max()))
         return out
+
+    def topology_report(self) -> dict:
+        """evaluation.topology_report over the recorded meshes: Singularity / vertices / elements as the reference tabulates
+        them, the valence histogram, closed and non-manifold meshes; episodes without elements are skipped."""
+        if self.topology is None:
+            raise ValueError("this evaluation ran with topology=False")
+        return topology_report(self.topology)
 
 
 def as_fused(model, device: int = 0):

@@ -25,6 +25,7 @@ from . import _capi
 from .compat import VEC_ENV_BASE
 from .domains import Point, domain_constants
 from .episode_tools import EpisodeTools
+from .evaluation import TOPOLOGY_FIELDS
 
 ACTION_LOW = np.array([-1.0, -1.5, 0.0], dtype=np.float32)   # rl/boundary_env.py:27
 ACTION_HIGH = np.array([1.0, 1.5, 1.5], dtype=np.float32)
@@ -714,7 +715,8 @@ class MeshVecEnv:
         return out
 
     def evaluate(self, policy, n_eval_episodes: Optional[int] = None, episodes_per_env=None, deterministic: bool = True,
-                 seed: int = 0, counter: int = 0, max_steps: int = 20000, check_every: int = 32, quality: bool = True):
+                 seed: int = 0, counter: int = 0, max_steps: int = 20000, check_every: int = 32, quality: bool = True,
+                 topology: bool = False):
         """SB3's evaluate_policy loop on the device (meshenv_evaluate): every env is reset, then per vector step the policy,
         a step with auto-reset and one k_eval_tally launch, with no host synchronisation except a read of the envs-still-short
         counter every check_every steps; the run stops when every env has recorded its target or after max_steps steps.
@@ -724,6 +726,7 @@ class MeshVecEnv:
         their target keep stepping and are not recorded.  deterministic=False samples with Philox noise; the actions of
         vector step t use noise counter counter + t (the same stream as collect_rollout(policy, T, seed, counter) /
         step_actor_T after a reset).  quality=True scores each finished mesh on the device (needs log_capacity > 0).
+        topology=True adds its topology report (EvalResult.topology, the TOPOLOGY_FIELDS), scored by one more launch per step.
         Returns an EvalResult (records sorted by (step, env)); finished is False, with a RuntimeWarning, when max_steps cut
         the run short.  env.obs / reward / done / complete hold the last step afterwards."""
         import warnings
@@ -746,6 +749,9 @@ class MeshVecEnv:
                             "converts SB3 models)")
         if policy.device != self.device:
             raise ValueError(f"policy is on {policy.device}, the envs on {self.device}")
+        if topology and self.log_capacity <= 0:
+            raise _capi.MeshEnvError("topology=True needs a MeshVecEnv created with log_capacity > 0 (the finished meshes are "
+                                     "read from the element log)")
         if quality and self.log_capacity <= 0:
             raise _capi.MeshEnvError("quality=True needs a MeshVecEnv created with log_capacity > 0 (the finished meshes are "
                                      "read from the element log); pass quality=False")
@@ -771,15 +777,24 @@ class MeshVecEnv:
         self._bind_stream()
         (pol if pol is not None else act)._bind_stream()
         steps, short = C.c_int32(0), C.c_int32(0)
-        rc = self._L.meshenv_evaluate(self._handle, pol._h if pol is not None else None, act._h if act is not None else None,
-                                      0 if deterministic else 1, C.c_uint64(seed & (2 ** 64 - 1)),
-                                      C.c_uint64(counter & (2 ** 64 - 1)), int(max_steps), int(check_every), C.byref(B),
-                                      C.byref(steps), C.byref(short))
+        ep_topology = t.zeros((m, _capi.TOPOLOGY_DIM), **i32) if topology else None
+        if topology:   # not a MeshEvalBuffers field (its layout is fixed): attached to the handle for this call
+            self._check(self._L.meshenv_eval_set_topology(self._handle, ep_topology.data_ptr()), "meshenv_eval_set_topology")
+        try:
+            rc = self._L.meshenv_evaluate(self._handle, pol._h if pol is not None else None, act._h if act is not None else None,
+                                          0 if deterministic else 1, C.c_uint64(seed & (2 ** 64 - 1)),
+                                          C.c_uint64(counter & (2 ** 64 - 1)), int(max_steps), int(check_every), C.byref(B),
+                                          C.byref(steps), C.byref(short))
+        finally:
+            if topology:
+                self._L.meshenv_eval_set_topology(self._handle, None)
         self._check(rc, "meshenv_evaluate")
         counts = buf["count_dev"].cpu().numpy()
         owner = np.repeat(np.arange(n), targets)
         keep = (np.arange(total) - offsets[owner]) < counts[owner]      # slots of episodes that were recorded
         rec = {k[3:-4]: buf[k][:total].cpu().numpy()[keep] for k in buf if k.startswith("ep_")}
+        if topology:
+            rec["topology"] = ep_topology[:total].cpu().numpy()[keep]
         res = EvalResult.from_records(rec, targets, steps.value, short.value == 0)
         if not res.finished:
             warnings.warn(f"evaluate: max_steps = {max_steps} reached with {short.value} envs short of their episode target "
@@ -959,6 +974,45 @@ class MeshVecEnv:
                 out[name] = dict(average=float(st[:, 1].mean()), std=float(np.sqrt(np.abs(st[:, 3])).mean()),
                                  min=float(st[:, 0].min()), max=float(st[:, 2].max()))
         return out
+
+    TOPOLOGY_FIELDS = TOPOLOGY_FIELDS   # the 16 words of a report, in order (evaluation.py)
+
+    def mesh_topology(self, which: str = "last", mask=None, per_vertex: bool = False):
+        """Topology report of every env's mesh in one launch (meshenv_mesh_topology, include/meshenv_topology.h): the
+        Singularity / num_vertices / num_elements of general/post_processing.py:93-161, the valence histogram and the edge
+        counts, as the TOPOLOGY_FIELDS.
+
+        which: "last" = the archived finished episodes, "current" = the running ones.  mask: uint8/bool CUDA [n], None = all;
+        a masked env gets status _capi.TOPO_MASKED and zeros.  Returns (report [n, 16] int32, valence [n, max_ring +
+        log_capacity] uint8 or None), CUDA tensors: valence[k, v] = elements that contain vertex v of env k, in the vertex
+        numbering of get_elements.  Nothing is read back: report[:, 0] (status) says which rows count."""
+        if which not in ("current", "last"):
+            raise ValueError("which must be 'current' or 'last'")
+        if self.log_capacity <= 0:
+            raise _capi.MeshEnvError("create the MeshVecEnv with log_capacity > 0 to read generated meshes")
+        t = self._torch
+        n = self.num_envs
+        report = t.zeros((n, _capi.TOPOLOGY_DIM), dtype=t.int32, device=self.device)
+        valence = t.zeros((n, self.max_ring + self.log_capacity), dtype=t.uint8, device=self.device) if per_vertex else None
+        mptr = None
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=t.uint8).contiguous()
+            if tuple(mask.shape) != (n,):
+                raise ValueError(f"mask must have shape ({n},)")
+            mptr = mask.data_ptr()
+        self._bind_stream()
+        rc = self._L.meshenv_mesh_topology(self._handle, 1 if which == "last" else 0, mptr, report.data_ptr(),
+                                           valence.data_ptr() if per_vertex else None)
+        self._check(rc, "meshenv_mesh_topology")
+        return report, valence
+
+    def topology_report(self, which: str = "last") -> dict:
+        """evaluation.topology_report over the envs' meshes: meshes, elements, vertices, singularity (average, std, min, max,
+        total), singular_fraction, valence_histogram, closed, nonmanifold, euler, skipped -- the topological columns of the
+        reference's results table next to quality_report's; envs without elements are skipped."""
+        from .evaluation import topology_report
+        report, _ = self.mesh_topology(which)
+        return topology_report(report.cpu().numpy())
 
     def counters(self) -> dict:
         out = (C.c_uint64 * 4)()

@@ -1,0 +1,266 @@
+"""GPU: the topology report (include/meshenv_topology.h, csrc/meshenv_topology.h: k_mesh_topology, k_eval_topology) against
+the host restatement tests/topology_ref.py, integer for integer.
+
+The meshes are those of tests/test_gpu_quality.py::test_archive_and_quality_report_match_oracle: three domains (30, 68 and
+44 ring vertices -- 68 is the smallest ring there for which the 64-lane vertex loop wraps), 96 envs, 420 biased random
+steps; both log halves of every env are compared."""
+
+import numpy as np
+import pytest
+
+import topology_ref as TR
+
+pytestmark = pytest.mark.gpu
+
+N, T, LOG_CAP = 96, 420, 160
+CANARY32, CANARY8 = -1234567, 0xA5
+
+
+def _biased(rng, T, n):
+    a = rng.uniform([-1, -1.5, 0], [1, 1.5, 1.5], size=(T, n, 3))
+    pick = rng.random((T, n)) < 0.6
+    b = np.stack([rng.uniform(-1, 1, (T, n)), rng.uniform(0.2, 1.0, (T, n)), rng.uniform(0.3, 1.2, (T, n))], axis=2)
+    a[pick] = b[pick]
+    return a.astype(np.float32)
+
+
+def _expected(env, n0s, which):
+    """(report [n, 16], valence [n, width], flags) of the restatement over the meshes read back env by env."""
+    width = env.max_ring + env.log_capacity
+    rep = np.zeros((env.num_envs, 16), np.int32)
+    val = np.zeros((env.num_envs, width), np.uint8)
+    complete = np.zeros(env.num_envs, bool)
+    overflow = np.zeros(env.num_envs, bool)
+    if which == "current":
+        overflow = (env.status().cpu().numpy() & 2) != 0
+    for k in range(env.num_envs):
+        if which == "last":
+            le = env.get_last_episode(k)
+            quads, complete[k], overflow[k] = le["quads"], le["is_complete"], le["overflow"]
+            if le["episodes"] == 0:
+                rep[k, 0] = 4
+                continue
+        else:
+            if overflow[k]:
+                rep[k, 0] = 2
+                continue
+            quads = env.get_elements(k)[0]
+        if overflow[k]:
+            rep[k, 0] = 2
+            continue
+        rep[k], val[k] = TR.topology(quads, int(n0s[k]), width=width)
+    return rep, val, complete
+
+
+@pytest.fixture(scope="module")
+def meshes():
+    import torch
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, boundary, random_domain
+    doms = [boundary(0), random_domain(7), random_domain(8)]
+    assert [len(d) for d in doms] == [30, 68, 44]
+    env_domain = (np.arange(N) % len(doms)).astype(np.int32)
+    env = MeshVecEnv(doms, env_domain=env_domain, auto_reset=True, log_capacity=LOG_CAP)
+    env.reset()
+    acts = torch.from_numpy(_biased(np.random.default_rng(21), T, N)).cuda()
+    for t in range(T):
+        env.step(acts[t])
+    n0s = np.array([len(doms[d]) for d in env_domain])
+    exp = {w: _expected(env, n0s, w) for w in ("last", "current")}
+    yield env, n0s, exp
+    env.close()
+
+
+def test_three_domains_both_halves(meshes):
+    import torch
+    env, n0s, exp = meshes
+    for which in ("last", "current"):
+        report, valence = env.mesh_topology(which, per_vertex=True)
+        assert report.dtype == torch.int32 and tuple(report.shape) == (N, 16) and report.is_cuda
+        assert valence.dtype == torch.uint8 and tuple(valence.shape) == (N, env.max_ring + LOG_CAP)
+        rep, val, _ = exp[which]
+        got, gotv = report.cpu().numpy(), valence.cpu().numpy()
+        for k in range(N):
+            assert got[k].tolist() == rep[k].tolist(), (which, k)
+            assert np.array_equal(gotv[k], val[k]), (which, k)
+        only, none = env.mesh_topology(which)
+        assert none is None and np.array_equal(only.cpu().numpy(), rep)
+    # the comparison is not over trivial meshes
+    rep, _, complete = exp["last"]
+    live = (rep[:, 0] == 0) & (rep[:, 1] > 0)
+    print("archived meshes", int(live.sum()), "complete", int((complete & live).sum()), "singularity",
+          int(rep[live, 3].min()), "..", int(rep[live, 3].max()), "histogram", rep[live, 4:12].sum(axis=0).tolist(),
+          "running with a front", int((exp["current"][0][:, 15] > 0).sum()))
+    assert int((complete & live).sum()) >= 3
+    assert int((rep[live, 3] > 0).sum()) >= 5
+    assert rep[live, 6].sum() > 0 and rep[live, 8].sum() > 0           # valence 3 and valence 5
+    assert (exp["current"][0][:, 15] > 0).any()
+    for which in ("last", "current"):
+        assert set(exp[which][0][:, 0].tolist()) <= {0, 4}
+    # a complete mesh is closed and a disc
+    for k in np.nonzero(complete & live)[0]:
+        assert rep[k, 15] == 0 and rep[k, 14] == 0 and rep[k, 13] == n0s[k] and TR.euler(rep[k]) == 1
+    agg = env.topology_report("last")
+    assert agg["meshes"] == int(live.sum()) and agg["elements"] == int(rep[live, 1].sum())
+    assert agg["singularity"]["total"] == int(rep[live, 3].sum()) and agg["closed"] >= int((complete & live).sum())
+    assert agg["skipped"] == ({4: int((rep[:, 0] == 4).sum())} if (rep[:, 0] == 4).any() else {})
+
+
+def test_mask(meshes):
+    import torch
+    env, n0s, exp = meshes
+    width = env.max_ring + LOG_CAP
+    mask = torch.from_numpy((np.arange(N) % 3 != 1).astype(np.uint8)).cuda()
+    for which in ("last", "current"):
+        report = torch.full((N, 16), CANARY32, dtype=torch.int32, device="cuda")
+        valence = torch.full((N, width), CANARY8, dtype=torch.uint8, device="cuda")
+        rc = env._L.meshenv_mesh_topology(env._handle, 1 if which == "last" else 0, mask.data_ptr(), report.data_ptr(),
+                                          valence.data_ptr())
+        assert rc == 0
+        got, gotv = report.cpu().numpy(), valence.cpu().numpy()
+        rep, val, _ = exp[which]
+        for k in range(N):
+            if k % 3 == 1:
+                assert got[k].tolist() == [1] + [CANARY32] * 15 and (gotv[k] == CANARY8).all(), (which, k)
+            else:
+                assert got[k].tolist() == rep[k].tolist() and np.array_equal(gotv[k], val[k]), (which, k)
+        # the Python call starts from zeros
+        got = env.mesh_topology(which, mask=mask)[0].cpu().numpy()
+        assert all(got[k].tolist() == ([1] + [0] * 15 if k % 3 == 1 else rep[k].tolist()) for k in range(N))
+
+
+def test_per_env_view(meshes):
+    env, _, exp = meshes
+    rep = exp["last"][0]
+    live = np.nonzero((rep[:, 0] == 0) & (rep[:, 1] > 0))[0]
+    picks = [int(live[0]), int(live[len(live) // 2]), int(live[-1]), int(np.argmax(rep[:, 3])), 1]
+    for k in picks:
+        assert env.envs[k].singularity() == rep[k, 3]
+        top = env.envs[k].topology()
+        assert list(top) == list(env.TOPOLOGY_FIELDS) and list(top.values()) == rep[k].tolist()
+    cur = exp["current"][0]
+    k = int(np.argmax(cur[:, 15]))
+    assert env.envs[k].topology("current")["front_edges"] == cur[k, 15] > 0
+    assert env.env_method("singularity", indices=picks[:2]) == [int(rep[k, 3]) for k in picks[:2]]
+
+
+def test_status_codes():
+    import torch
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, _capi, boundary
+    n = 64
+    env = MeshVecEnv([boundary(0)], n_envs=n, auto_reset=True, log_capacity=8)
+    env.reset()
+    last, val = env.mesh_topology("last", per_vertex=True)
+    assert last.cpu().numpy().tolist() == [[4] + [0] * 15] * n and not val.any()
+    cur = env.mesh_topology("current")[0].cpu().numpy()
+    assert not cur[:, :15].any() and (cur[:, 15] == 30).all()   # status 0, no element: the whole ring is front
+    acts = torch.from_numpy(_biased(np.random.default_rng(3), 300, n)).cuda()
+    for t in range(300):
+        env.step(acts[t])
+    n0s = np.full(n, 30)
+    seen = set()
+    for which in ("last", "current"):
+        rep, val, _ = _expected(env, n0s, which)
+        report, valence = env.mesh_topology(which, per_vertex=True)
+        assert np.array_equal(report.cpu().numpy(), rep), which
+        assert np.array_equal(valence.cpu().numpy(), val), which
+        seen |= set(rep[:, 0].tolist())
+        print(which, "statuses", np.unique(rep[:, 0], return_counts=True))
+    assert {0, 2} <= seen
+    # refusals
+    L, h = env._L, env._handle
+    buf = torch.zeros((n, 16), dtype=torch.int32, device="cuda")
+    assert L.meshenv_mesh_topology(h, 2, None, buf.data_ptr(), None) == _capi.E_ARG
+    assert L.meshenv_mesh_topology(h, 0, None, None, None) == _capi.E_ARG
+    assert L.meshenv_mesh_topology(None, 0, None, buf.data_ptr(), None) == _capi.E_ARG
+    with pytest.raises(ValueError):
+        env.mesh_topology("first")
+    env.close()
+    env = MeshVecEnv([boundary(0)], n_envs=4, log_capacity=0)
+    with pytest.raises(_capi.MeshEnvError):
+        env.mesh_topology("current")
+    buf = torch.zeros((4, 16), dtype=torch.int32, device="cuda")
+    assert env._L.meshenv_mesh_topology(env._handle, 0, None, buf.data_ptr(), None) == _capi.E_STATE
+    assert env._L.meshenv_eval_set_topology(env._handle, buf.data_ptr()) == _capi.E_STATE
+    assert env._L.meshenv_eval_set_topology(env._handle, None) == 0
+    env.close()
+
+
+def _policy(seed):
+    """tests/test_gpu_eval.py's deterministic-kind policy: fixed random weights, mean action near the centre of the biased
+    random actions, Philox noise of their spread."""
+    import torch
+    from reinforcementlearning4meshgeneration_amd.policy import FusedPolicy
+    low, high = np.array([-1.0, -1.5, 0.0]), np.array([1.0, 1.5, 1.5])
+    mean, spread = np.array([0.0, 0.6, 0.75]), np.array([0.6, 0.25, 0.3])
+    torch.manual_seed(seed)
+    tower = [torch.nn.Linear(18, 64), torch.nn.Linear(64, 64)]
+    head = torch.nn.Linear(64, 3)
+    with torch.no_grad():
+        head.weight.mul_(0.3)
+        head.bias.copy_(torch.tensor(np.arctanh((mean - low) / (high - low) * 2 - 1)))
+    return FusedPolicy.deterministic(tower, head, activation="relu", sigma=spread * 2 / (high - low))
+
+
+def _against_archive(env, res, n0s):
+    """Every record whose archive is still the env's last episode equals the restatement of that archive; records without
+    elements are 16 zeros.  Returns (records with elements, records that could be compared)."""
+    with_elements = comparable = 0
+    for i in range(len(res)):
+        k = int(res.env[i])
+        if res.n_elements[i] <= 0:
+            assert not res.topology[i].any()
+            continue
+        with_elements += 1
+        le = env.get_last_episode(k)
+        if le["episodes"] != res.archive[i]:
+            continue                                    # a later episode of the env has replaced the archive since
+        comparable += 1
+        exp = np.array([2] + [0] * 15) if res.overflow[i] else TR.topology(le["quads"], int(n0s[k]))[0]
+        assert res.topology[i].tolist() == exp.tolist(), (i, k)
+        if not res.overflow[i]:
+            assert res.topology[i, 1] == res.n_elements[i]
+    return with_elements, comparable
+
+
+@pytest.mark.parametrize("deterministic", [True, False], ids=["deterministic", "noise"])
+def test_evaluation_scores_topology_at_the_tally(deterministic):
+    """deterministic: the envs of a domain run the same episode, so the one-episode evaluation ends with every archive in
+    place (one distinct mesh; the random domain's episodes end without an element).  noise: Philox action noise gives 64
+    different episodes and most archives are replaced before the evaluation ends -- the variety for the two-episode check."""
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, boundary, random_domain
+    doms = [boundary(0), random_domain(8)]
+    n = 64
+    env = MeshVecEnv(doms, n_envs=n, log_capacity=LOG_CAP)
+    n0s = np.array([len(doms[k % 2]) for k in range(n)])
+    pol = _policy(3)
+    kw = dict(deterministic=deterministic, seed=5, counter=1000, max_steps=3000, check_every=1)
+    one = env.evaluate(pol, episodes_per_env=1, topology=True, **kw)
+    assert one.finished and len(one) == n and one.topology.shape == (n, 16) and one.topology.dtype == np.int32
+    with_elements, comparable = _against_archive(env, one, n0s)
+    print("records with elements", with_elements, "comparable", comparable, one.topology_report())
+    assert with_elements >= n // 2 and comparable > 0
+    if deterministic:
+        assert 2 * comparable >= with_elements and (one.n_elements == 0).any() and one.topology[:, 3].max() > 0
+    assert one.topology_report()["meshes"] == int(((one.topology[:, 0] == 0) & (one.topology[:, 1] > 0)).sum())
+    # two episodes per env: the first-episode records were scored before the second episode replaced the archive
+    two = env.evaluate(pol, episodes_per_env=2, topology=True, **kw)
+    assert two.finished and len(two) == 2 * n
+    _against_archive(env, two, n0s)
+    replaced = 0
+    for k in range(n):
+        first = int(np.nonzero(two.env == k)[0][0])      # records are sorted by step
+        i = int(np.nonzero(one.env == k)[0][0])
+        assert two.step[first] == one.step[i] and two.topology[first].tolist() == one.topology[i].tolist(), k
+        replaced += int(two.n_elements[first] > 0 and env.get_last_episode(k)["episodes"] != two.archive[first])
+    assert replaced >= n // 4, replaced
+    # detached afterwards: nothing else changed
+    plain = env.evaluate(pol, episodes_per_env=2, **kw)
+    assert plain.topology is None
+    for name in ("env", "domain", "step", "length", "reward", "reward_raw", "complete", "overflow", "n_elements", "quality",
+                 "targets"):
+        a, b = getattr(plain, name), getattr(two, name)
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), name
+    assert np.array_equal(plain.archive > 0, two.archive > 0)      # (the archive counter itself runs on between evaluations)
+    assert plain.steps == two.steps and plain.finished == two.finished
+    pol.close()
+    env.close()
