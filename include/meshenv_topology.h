@@ -52,6 +52,22 @@ int meshenv_mesh_topology(MeshEnv *h, int which, const uint8_t *mask_dev, int32_
  * MESHENV_E_ARG: h NULL; MESHENV_E_STATE: a non-NULL buffer on a handle created with log_capacity = 0. */
 int meshenv_eval_set_topology(MeshEnv *h, int32_t *ep_topology_dev);
 
+/* TEST ENTRY POINT (as meshenv_selftest: no handle, host pointers, null stream, synchronises before it returns): the counting
+ * part of the two kernels above on element logs the caller wrote, grid = n_meshes, one wavefront per mesh.  Mesh m is the
+ * records elem_offsets_host[m] .. elem_offsets_host[m + 1] (elem_offsets_host[0] = 0, non-decreasing) of quads_host [total][4]
+ * on a domain ring of n0_host[m] >= 3 vertices with n_new_host[m] >= 0 generated ones, in the vertex numbering of
+ * meshenv_get_elements (domain vertex i -> i, k-th generated vertex -> n0 + k); the call stores generated ids as the log does.
+ * THE CONTRACT FOR A RECORD -- of this call and of the element log the kernels read: four DISTINCT ids, each < n0 + n_new.
+ * The report of a mesh with a record outside it is undefined.  (This call refuses an id outside [0, n0 + n_new); that the
+ * four ids differ is left to the caller.)  Elements are counted as given: a repeated record counts twice.
+ * report_host [n_meshes][16] and valence_host (NULL = off) [n_meshes][width] are copied to the device before the launch and
+ * back after it, so a caller sees which words and bytes the kernel wrote.  Status is MESHENV_TOPO_OK or MESHENV_TOPO_DEGREE.
+ * MESHENV_E_ARG: n_meshes <= 0, a NULL pointer other than valence_host, width <= 0 or > 65535 (16-bit vertex indices),
+ * width < n0 + n_new of some mesh, offsets or ids as excluded above; MESHENV_E_HIP: the device refused something. */
+int meshenv_topology_selftest(int device, int n_meshes, const int32_t *elem_offsets_host, const int32_t *quads_host,
+                              const int32_t *n0_host, const int32_t *n_new_host, int width, int32_t *report_host,
+                              uint8_t *valence_host);
+
 #ifdef __cplusplus
 }
 #endif

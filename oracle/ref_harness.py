@@ -89,6 +89,94 @@ def load_reference():
     return _loaded
 
 
+# general/post_processing.py and what it imports (general/mesh.py, rl/boundary_env.py, rl/baselines/MeshCanvas.py) pull in
+# plotting, GUI and CUDA libraries that none of the functions used here touch
+POST_PROCESSING_OPTIONAL = ("pycuda", "pygame", "turtle", "meshio", "pandas", "seaborn")
+
+
+class _Harmless:
+    """What a stubbed module hands out: any attribute, call, item or iteration gives something harmless."""
+
+    def __getattr__(self, name):
+        if name.startswith("__") and name.endswith("__"):
+            raise AttributeError(name)
+        return self
+
+    def __call__(self, *a, **k):
+        return self
+
+    def __getitem__(self, key):
+        return self
+
+    def __iter__(self):
+        return iter(())
+
+    def __mro_entries__(self, bases):      # `class X(stub.Base):` becomes a plain class
+        return ()
+
+
+class _StubModule(types.ModuleType):
+    def __getattr__(self, name):
+        if name.startswith("__") and name.endswith("__"):
+            raise AttributeError(name)
+        return _Harmless()
+
+
+class _StubFinder:
+    """Meta path finder placed in FRONT of the regular ones: `turtle` exists in the standard library and has to be shadowed,
+    because its own import of tkinter fails where no Tk is installed."""
+
+    def __init__(self, names):
+        self.names = tuple(names)
+
+    def find_spec(self, fullname, path=None, target=None):
+        import importlib.machinery
+        if any(fullname == n or fullname.startswith(n + ".") for n in self.names):
+            return importlib.machinery.ModuleSpec(fullname, self, is_package=True)
+        return None
+
+    def create_module(self, spec):
+        m = _StubModule(spec.name)
+        m.__path__ = []
+        return m
+
+    def exec_module(self, module):
+        pass
+
+
+_post_processing = None
+
+
+def load_post_processing():
+    """Import the reference's general/post_processing.py; returns (module, names that were stubbed).  Of
+    POST_PROCESSING_OPTIONAL only the libraries whose own import fails here are replaced by stub modules."""
+    global _post_processing
+    if _post_processing is not None:
+        return _post_processing
+    import importlib
+    load_reference()                       # MPLBACKEND, and the gym / stable_baselines3 stand-ins rl/boundary_env.py needs too
+    missing = []
+    for name in POST_PROCESSING_OPTIONAL:
+        if name in sys.modules:
+            continue
+        try:
+            importlib.import_module(name)
+        except Exception:                  # turtle: ImportError from tkinter, or TclError without a display
+            for k in [k for k in sys.modules if k == name or k.startswith(name + ".")]:
+                del sys.modules[k]
+            missing.append(name)
+    if missing:
+        sys.meta_path.insert(0, _StubFinder(missing))
+    if REFERENCE_ROOT not in sys.path:
+        sys.path.append(REFERENCE_ROOT)    # behind v2/src: `general` and `rl` exist only at the root
+    import contextlib
+    import io
+    with contextlib.redirect_stdout(io.StringIO()):
+        module = importlib.import_module("general.post_processing")
+    _post_processing = (module, tuple(missing))
+    return _post_processing
+
+
 def domain_points(name: str):
     """Python-typed coordinates exactly as the reference builds them.
 

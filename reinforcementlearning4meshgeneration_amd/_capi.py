@@ -141,8 +141,9 @@ EVAL_ROW_DOUBLES, EVAL_STATE_DOUBLES, KEEP_BEST_MAX_ENTRIES = 9, 4, 64
 EVAL_COLUMNS = ("num_timesteps", "mean_reward", "std_reward", "mean_ep_length", "recorded", "short", "complete_rate",
                 "mean_n_elements", "improved")
 
-# every symbol include/meshenv_topology.h declares: the topology report of the generated meshes, and its attachment to the tally
-EXPORTS_TOPOLOGY = ["meshenv_mesh_topology", "meshenv_eval_set_topology"]
+# every symbol include/meshenv_topology.h declares: the topology report of the generated meshes, its attachment to the tally, and
+# the test entry point that runs the counting on element logs the caller wrote
+EXPORTS_TOPOLOGY = ["meshenv_mesh_topology", "meshenv_eval_set_topology", "meshenv_topology_selftest"]
 TOPOLOGY_DIM = 16
 TOPO_OK, TOPO_MASKED, TOPO_LOG_OVERFLOW, TOPO_DEGREE, TOPO_NOT_ARCHIVED = 0, 1, 2, 3, 4
 
@@ -331,6 +332,7 @@ def load():
     L.meshenv_keep_best.argtypes = [vp, C.POINTER(MeshKeepEntry), C.c_int, vp, C.c_int64, vp]
     L.meshenv_mesh_topology.argtypes, L.meshenv_mesh_topology.restype = [vp, C.c_int, vp, vp, vp], C.c_int
     L.meshenv_eval_set_topology.argtypes, L.meshenv_eval_set_topology.restype = [vp, vp], C.c_int
+    L.meshenv_topology_selftest.argtypes, L.meshenv_topology_selftest.restype = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp], C.c_int
     for name in ("meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_uniform_actions", "meshenv_step_actions_multi",
                  "meshenv_episode_stats_update", "meshenv_evaluate_queued", "meshenv_eval_reduce", "meshenv_keep_best"):
         getattr(L, name).restype = C.c_int
@@ -354,6 +356,26 @@ def default_params() -> MeshEnvParams:
     p = MeshEnvParams()
     load().meshenv_default_params(C.byref(p))
     return p
+
+
+def topology_selftest(meshes, n0, n_new, width, valence_fill=None, report_fill=0, device=0):
+    """meshenv_topology_selftest (include/meshenv_topology.h): the counting of k_mesh_topology / k_eval_topology on element logs
+    the caller wrote.  meshes: one [n, 4] id array per mesh (domain vertex i -> i, k-th generated vertex -> n0 + k), n0 / n_new:
+    one int per mesh.  Returns (rc, report int32 [M, 16], valence uint8 [M, width] or None); the two arrays start as
+    report_fill / valence_fill (None = no valence rows), so what the kernel did not write keeps that value."""
+    import numpy as np
+    quads = [np.asarray(q, np.int32).reshape(-1, 4) for q in meshes]
+    offsets = np.concatenate([[0], np.cumsum([len(q) for q in quads])]).astype(np.int32)
+    flat = np.ascontiguousarray(np.concatenate(quads + [np.zeros((1, 4), np.int32)]))    # never an empty buffer
+    n0 = np.ascontiguousarray(n0, np.int32)
+    n_new = np.ascontiguousarray(n_new, np.int32)
+    if not (len(quads) == len(n0) == len(n_new)):
+        raise ValueError("topology_selftest: one n0 and one n_new per mesh")
+    report = np.full((len(quads), TOPOLOGY_DIM), report_fill, np.int32)
+    valence = None if valence_fill is None else np.full((len(quads), max(int(width), 0)), valence_fill, np.uint8)
+    rc = load().meshenv_topology_selftest(device, len(quads), offsets.ctypes.data, flat.ctypes.data, n0.ctypes.data, n_new.ctypes.data,
+                                          int(width), report.ctypes.data, None if valence is None else valence.ctypes.data)
+    return rc, report, valence
 
 
 def check(handle, rc: int, what: str):

@@ -1559,6 +1559,55 @@ int meshenv_eval_set_topology(MeshEnv *h, int32_t *ep_topology_dev)
     return MESHENV_OK;
 }
 
+int meshenv_topology_selftest(int device, int n_meshes, const int32_t *elem_offsets_host, const int32_t *quads_host,
+                              const int32_t *n0_host, const int32_t *n_new_host, int width, int32_t *report_host,
+                              uint8_t *valence_host)
+{
+    if (n_meshes <= 0 || !elem_offsets_host || !quads_host || !n0_host || !n_new_host || !report_host) return MESHENV_E_ARG;
+    if (width <= 0 || width > 65535 || elem_offsets_host[0] != 0) return MESHENV_E_ARG;
+    for (int m = 0; m < n_meshes; m++) {
+        if (elem_offsets_host[m + 1] < elem_offsets_host[m] || n0_host[m] < 3 || n_new_host[m] < 0 ||
+            (long long)n0_host[m] + n_new_host[m] > width)
+            return MESHENV_E_ARG;
+    }
+    const size_t total = (size_t)elem_offsets_host[n_meshes];
+    // the log's encoding: the k-th generated vertex is kNewBit | k.  An id outside the mesh is refused here; that the four
+    // ids of a record are distinct is the caller's part of the contract.
+    std::vector<int32_t> log(4 * (total ? total : 1), 0);
+    for (int m = 0; m < n_meshes; m++) {
+        const int n0 = n0_host[m], nv = n0 + n_new_host[m];
+        for (size_t i = 4 * (size_t)elem_offsets_host[m]; i < 4 * (size_t)elem_offsets_host[m + 1]; i++) {
+            const int id = quads_host[i];
+            if (id < 0 || id >= nv) return MESHENV_E_ARG;
+            log[i] = id >= n0 ? (kNewBit | (id - n0)) : id;
+        }
+    }
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return MESHENV_E_HIP;
+    const size_t n = (size_t)n_meshes;
+    int32_t *d_off = nullptr, *d_log = nullptr, *d_n0 = nullptr, *d_new = nullptr, *d_rep = nullptr;
+    uint8_t *d_val = nullptr;
+    bool ok = hipMalloc(&d_off, sizeof(int32_t) * (n + 1)) == hipSuccess && hipMalloc(&d_log, sizeof(int32_t) * log.size()) == hipSuccess &&
+              hipMalloc(&d_n0, sizeof(int32_t) * n) == hipSuccess && hipMalloc(&d_new, sizeof(int32_t) * n) == hipSuccess &&
+              hipMalloc(&d_rep, sizeof(int32_t) * n * kTopologyDim) == hipSuccess &&
+              (!valence_host || hipMalloc(&d_val, n * (size_t)width) == hipSuccess);
+    ok = ok && hipMemcpy(d_off, elem_offsets_host, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_log, log.data(), sizeof(int32_t) * log.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_n0, n0_host, sizeof(int32_t) * n, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_new, n_new_host, sizeof(int32_t) * n, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_rep, report_host, sizeof(int32_t) * n * kTopologyDim, hipMemcpyHostToDevice) == hipSuccess &&
+         (!valence_host || hipMemcpy(d_val, valence_host, n * (size_t)width, hipMemcpyHostToDevice) == hipSuccess);
+    if (ok) {
+        hipLaunchKernelGGL(k_topology_selftest, dim3(n_meshes), dim3(64), 0, nullptr, d_off, reinterpret_cast<const int4 *>(d_log),
+                           d_n0, d_new, d_rep, d_val, width);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    }
+    ok = ok && hipMemcpy(report_host, d_rep, sizeof(int32_t) * n * kTopologyDim, hipMemcpyDeviceToHost) == hipSuccess &&
+         (!valence_host || hipMemcpy(valence_host, d_val, n * (size_t)width, hipMemcpyDeviceToHost) == hipSuccess);
+    (void)hipFree(d_off); (void)hipFree(d_log); (void)hipFree(d_n0); (void)hipFree(d_new); (void)hipFree(d_rep); (void)hipFree(d_val);
+    return ok ? MESHENV_OK : MESHENV_E_HIP;
+}
+
 int meshenv_quad_quality(MeshEnv *h, int n, const double *quad_xy_dev, int index, double *out_dev)
 {
     if (!h || n < 0 || (n > 0 && (!quad_xy_dev || !out_dev))) return MESHENV_E_ARG;

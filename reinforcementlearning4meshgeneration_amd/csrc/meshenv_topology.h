@@ -15,7 +15,7 @@
 //
 // The reference removes elements with equal sorted vertex sets before it counts (post_processing.py:27-32, 81-89).  The
 // environment cannot log such a pair -- the reference vertex of every extraction leaves the ring for good -- so this kernel
-// does NOT dedup: a repeated record would count twice.
+// does NOT dedup: a repeated record counts twice (tests/test_gpu_topology_crafted.py holds it to that).
 #pragma once
 
 #include "meshenv_eval.h"
@@ -98,32 +98,21 @@ __device__ __forceinline__ void scan_vertex_links(const int4 *__restrict__ quads
     }
 }
 
-// The report of ONE env, computed by a whole wave: env and which are wave-uniform and all 64 lanes take part.
-// which = 0: the running episode; 1: the last archived (finished) episode.  report = the env's 16 words; valence_row
-// (nullable) = the env's `width` bytes (width >= n0 + n_new: ring stride + log capacity).  sc = S.scal[env].
-__device__ __forceinline__ void env_topology(const DevState &S, const EnvScalars &sc, const DevCold &cold, int env, int which,
-                                             int32_t *__restrict__ report, uint8_t *__restrict__ valence_row, int width)
+// The counting: the report of ONE mesh, computed by a whole wave (every argument is wave-uniform, all 64 lanes take part).
+// quads = n_elem records of the element log (generated ids carry kNewBit) on a domain ring of n0 vertices with n_new
+// generated ones.  Contract for a record: four distinct ids, each < n0 + n_new; anything else is undefined.  report = the
+// mesh's 16 words; valence_row (nullable) = its `width` bytes, width >= n0 + n_new.  code = the status the caller has
+// arrived at: kTopoOk -> the mesh is counted (status kTopoOk or kTopoDegree); anything else -> nothing is read and the
+// report is that status, words 1..15 and the valence row 0.  (The refusals of env_topology pass through here so that the
+// function has one exit and one store: the two shipped kernels compile to what they were before the split.)
+__device__ __forceinline__ void mesh_topology(const int4 *__restrict__ quads, int n_elem, int n0, int n_new,
+                                              int32_t *__restrict__ report, uint8_t *__restrict__ valence_row, int width,
+                                              int code = kTopoOk)
 {
     const int lane = lane_id();
-    const int log_cap = S.prm.log_cap;
-    int n_elem = uniform_i32(sc.n_elem), n_new = uniform_i32(sc.n_new);
-    const int status = uniform_i32(sc.status);
-    bool overflow = (status & kStLogOverflow) != 0;
-    int half = (status >> 4) & 1;
-    int code = kTopoOk;
-    if (which) {
-        const LastEpisode le = cold.last_ep[env];
-        if (uniform_i32(le.episodes) <= 0) code = kTopoNotArchived;
-        n_elem = uniform_i32(le.n_elem); n_new = uniform_i32(le.n_new);
-        overflow = (uniform_i32(le.flags) & 2) != 0;
-        half ^= 1;
-    }
-    if (code == kTopoOk && (overflow || n_elem > log_cap || n_new > log_cap)) code = kTopoLogOverflow;
     int acc[kTopologyDim] = {};
     if (code == kTopoOk) {
-        const int n0 = uniform_i32(S.dom[uniform_i32(sc.dom)].n0);
         const int nv = n0 + n_new;
-        const int4 *quads = reinterpret_cast<const int4 *>(cold.log_quads + ((size_t)env * 2 + half) * log_cap * 4);
         bool too_many = false;
         for (int v0 = 0; v0 < nv; v0 += 64) {
             const int u_me = v0 + lane;
@@ -169,6 +158,36 @@ __device__ __forceinline__ void env_topology(const DevState &S, const EnvScalars
         }
     }
     if (lane < kTopologyDim) report[lane] = r;
+}
+
+// Reads the env: which = 0: the running episode; 1: the last archived (finished) episode -- element and vertex counts, log
+// half, overflow, n0 -- and hands the log, or the status that keeps it from being read, to mesh_topology.  env and which are
+// wave-uniform and all 64 lanes take part.  report = the env's 16 words; valence_row (nullable) = the env's `width` bytes
+// (width >= n0 + n_new: ring stride + log capacity).  sc = S.scal[env].
+__device__ __forceinline__ void env_topology(const DevState &S, const EnvScalars &sc, const DevCold &cold, int env, int which,
+                                             int32_t *__restrict__ report, uint8_t *__restrict__ valence_row, int width)
+{
+    const int log_cap = S.prm.log_cap;
+    int n_elem = uniform_i32(sc.n_elem), n_new = uniform_i32(sc.n_new);
+    const int status = uniform_i32(sc.status);
+    bool overflow = (status & kStLogOverflow) != 0;
+    int half = (status >> 4) & 1;
+    int code = kTopoOk;
+    if (which) {
+        const LastEpisode le = cold.last_ep[env];
+        if (uniform_i32(le.episodes) <= 0) code = kTopoNotArchived;
+        n_elem = uniform_i32(le.n_elem); n_new = uniform_i32(le.n_new);
+        overflow = (uniform_i32(le.flags) & 2) != 0;
+        half ^= 1;
+    }
+    if (code == kTopoOk && (overflow || n_elem > log_cap || n_new > log_cap)) code = kTopoLogOverflow;
+    int n0 = 0;
+    const int4 *quads = nullptr;
+    if (code == kTopoOk) {
+        n0 = uniform_i32(S.dom[uniform_i32(sc.dom)].n0);
+        quads = reinterpret_cast<const int4 *>(cold.log_quads + ((size_t)env * 2 + half) * log_cap * 4);
+    }
+    mesh_topology(quads, n_elem, n0, n_new, report, valence_row, width, code);
 }
 
 // report [E][16]; valence (nullable) [E][width] uint8, width = ring stride of the public interface (meshenv_max_ring) +
@@ -218,6 +237,18 @@ __global__ void __launch_bounds__(64 * kEvalWaves) k_eval_topology(DevState S, E
         if ((scored_mask >> l) & 1) env_topology(S, S.scal[base + l], cold, base + l, 1, row, nullptr, 0);
         else if (lane < kTopologyDim) row[lane] = 0;
     }
+}
+
+// meshenv_topology_selftest (include/meshenv_topology.h): mesh_topology on logs the caller wrote -- grid = meshes, one wavefront
+// per mesh, mesh m = the records elem_offsets[m] .. elem_offsets[m + 1] of quads.
+__global__ void __launch_bounds__(64)
+k_topology_selftest(const int32_t *__restrict__ elem_offsets, const int4 *__restrict__ quads, const int32_t *__restrict__ n0,
+                    const int32_t *__restrict__ n_new, int32_t *__restrict__ report, uint8_t *__restrict__ valence, int width)
+{
+    const int m = blockIdx.x;
+    const int first = uniform_i32(elem_offsets[m]);
+    mesh_topology(quads + first, uniform_i32(elem_offsets[m + 1]) - first, uniform_i32(n0[m]), uniform_i32(n_new[m]),
+                  report + (size_t)m * kTopologyDim, valence ? valence + (size_t)m * width : nullptr, width);
 }
 
 }  // namespace meshenv

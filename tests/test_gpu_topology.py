@@ -3,7 +3,9 @@ the host restatement tests/topology_ref.py, integer for integer.
 
 The meshes are those of tests/test_gpu_quality.py::test_archive_and_quality_report_match_oracle: three domains (30, 68 and
 44 ring vertices -- 68 is the smallest ring there for which the 64-lane vertex loop wraps), 96 envs, 420 biased random
-steps; both log halves of every env are compared."""
+steps; both log halves of every env are compared.  The tally (k_eval_topology) is run with 64 envs and with 100 envs on a log
+too small for the longer episodes, and through meshenv_evaluate_queued.  Element logs no environment produces are in
+tests/test_gpu_topology_crafted.py."""
 
 import numpy as np
 import pytest
@@ -264,3 +266,106 @@ def test_evaluation_scores_topology_at_the_tally(deterministic):
     assert plain.steps == two.steps and plain.finished == two.finished
     pol.close()
     env.close()
+
+
+N_TWO_GROUPS, SMALL_LOG_CAP = 100, 32
+
+
+def _tally_two_workgroups(log_capacity, seed=6):
+    """One noisy evaluation of 100 envs (two workgroups of k_eval_topology, the second with 36 envs: base = 64 and the
+    env < n guard false in 28 lanes) on a log too small for the longer episodes.  Returns (env, result, n0s, statuses the
+    restatement side saw among the comparable records with elements)."""
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, boundary, random_domain
+    doms = [boundary(0), random_domain(8)]
+    n = N_TWO_GROUPS
+    env = MeshVecEnv(doms, n_envs=n, log_capacity=log_capacity)
+    n0s = np.array([len(doms[k % 2]) for k in range(n)])
+    pol = _policy(3)
+    res = env.evaluate(pol, episodes_per_env=1, topology=True, deterministic=False, seed=seed, counter=1000, max_steps=3000,
+                       check_every=1)
+    pol.close()
+    seen = []
+    for i in range(len(res)):
+        k = int(res.env[i])
+        if res.n_elements[i] > 0 and env.get_last_episode(k)["episodes"] == res.archive[i]:
+            seen.append((2 if res.overflow[i] else 0, k))
+    return env, res, n0s, seen
+
+
+def test_tally_two_workgroups_and_overflowed_archives():
+    """test_evaluation_scores_topology_at_the_tally ran one full workgroup and no overflowed archive.  Here: the same
+    comparison -- every record whose archive is still in place equals the restatement of it, an overflowed one is [2, 0, ...],
+    a record without elements 16 zeros -- with both statuses among the compared records and both workgroups among their envs."""
+    env, res, n0s, seen = _tally_two_workgroups(SMALL_LOG_CAP)
+    n = N_TWO_GROUPS
+    assert res.finished and len(res) == n and res.topology.shape == (n, 16)
+    with_elements, comparable = _against_archive(env, res, n0s)
+    statuses = [s for s, _ in seen]
+    print("records with elements", with_elements, "comparable", comparable, "ok", statuses.count(0), "overflowed", statuses.count(2),
+          "of the second workgroup", sum(k >= 64 for _, k in seen), "all overflowed records", int(res.overflow.sum()))
+    assert comparable == len(seen) and statuses.count(0) > 0 and statuses.count(2) > 0
+    assert any(k >= 64 for _, k in seen) and any(k < 64 for _, k in seen)
+    # whether its archive is still there or not: an overflowed record is the bare status, any other one counts its elements
+    for i in range(n):
+        if res.n_elements[i] <= 0:
+            assert not res.topology[i].any(), i
+        elif res.overflow[i]:
+            assert res.topology[i].tolist() == [2] + [0] * 15, i
+        else:
+            assert res.topology[i, 0] == 0 and res.topology[i, 1] == res.n_elements[i] <= SMALL_LOG_CAP, i
+    assert set(res.topology[:, 0].tolist()) == {0, 2} and (res.env >= 64).sum() == n - 64
+    env.close()
+
+
+def test_queued_evaluation_writes_the_polling_loops_topology():
+    """meshenv_evaluate_queued with a topology buffer attached (meshenv_eval_set_topology) against MeshVecEnv.evaluate(
+    topology=True) on a twin env: the same rows in the same slots."""
+    import ctypes as C
+
+    import torch as t
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, _capi, boundary, random_domain
+    doms = [boundary(0), random_domain(8)]
+    n = N_TWO_GROUPS
+    targets = (1 + np.arange(n) % 2).astype(np.int32)
+    pol = _policy(3)
+    poll = MeshVecEnv(doms, n_envs=n, log_capacity=SMALL_LOG_CAP)
+    queue = MeshVecEnv(doms, n_envs=n, log_capacity=SMALL_LOG_CAP)
+    kw = dict(deterministic=False, seed=7, counter=500)
+    res = poll.evaluate(pol, episodes_per_env=targets, topology=True, max_steps=3000, check_every=1, **kw)
+    assert res.finished and len(res) == int(targets.sum())
+    offsets = np.zeros(n, np.int32)
+    offsets[1:] = np.cumsum(targets, dtype=np.int64)[:-1]
+    m = int(targets.sum())
+    i32, f64 = dict(dtype=t.int32, device=queue.device), dict(dtype=t.float64, device=queue.device)
+    buf = dict(target_dev=t.from_numpy(targets).to(queue.device), offset_dev=t.from_numpy(offsets).to(queue.device),
+               count_dev=t.empty(n, **i32), length_dev=t.empty(n, **i32), seen_dev=t.empty(n, **i32),
+               return_dev=t.empty(n, **f64), return_raw_dev=t.empty(n, **f64), short_dev=t.zeros(1, **i32),
+               ep_env_dev=t.zeros(m, **i32), ep_domain_dev=t.zeros(m, **i32), ep_step_dev=t.zeros(m, **i32),
+               ep_length_dev=t.zeros(m, **i32), ep_flags_dev=t.zeros(m, **i32), ep_n_elements_dev=t.zeros(m, **i32),
+               ep_archive_dev=t.zeros(m, **i32), ep_return_dev=t.zeros(m, **f64), ep_return_raw_dev=t.zeros(m, **f64),
+               ep_quality_dev=t.zeros((m, 8, 4), **f64))
+    buf.update(obs_dev=queue.obs, reward_dev=queue.reward, done_dev=queue.done, complete_dev=queue.complete)
+    B = _capi.MeshEvalBuffers()
+    B.struct_size = C.sizeof(_capi.MeshEvalBuffers)
+    for k, v in buf.items():
+        setattr(B, k, v.data_ptr())
+    ep_topology = t.full((m, 16), CANARY32, **i32)
+    queue._bind_stream()
+    pol._bind_stream()
+    queue._check(queue._L.meshenv_eval_set_topology(queue._handle, ep_topology.data_ptr()), "meshenv_eval_set_topology")
+    try:
+        rc = queue._L.meshenv_evaluate_queued(queue._handle, pol._h, None, 1, C.c_uint64(kw["seed"]), C.c_uint64(kw["counter"]),
+                                              int(res.steps), C.byref(B))
+    finally:
+        queue._L.meshenv_eval_set_topology(queue._handle, None)
+    queue._check(rc, "meshenv_evaluate_queued")
+    assert int(buf["short_dev"].item()) == 0 and np.array_equal(buf["count_dev"].cpu().numpy(), targets)
+    got = ep_topology.cpu().numpy()
+    slot_env, slot_step = buf["ep_env_dev"].cpu().numpy(), buf["ep_step_dev"].cpu().numpy()
+    order = np.lexsort((slot_env, slot_step))                  # EvalResult's order: by (step, env)
+    assert np.array_equal(slot_env[order], res.env) and np.array_equal(slot_step[order], res.step)
+    assert np.array_equal(got[order], res.topology)
+    assert not (got == CANARY32).any() and set(res.topology[:, 0].tolist()) == {0, 2}
+    print("queued rows", m, "ok", int((res.topology[:, 0] == 0).sum()), "overflowed", int((res.topology[:, 0] == 2).sum()),
+          "without elements", int((res.n_elements == 0).sum()))
+    pol.close(); poll.close(); queue.close()
