@@ -144,8 +144,8 @@ int meshenv_create_random_density(int device, int n_envs, uint64_t seed0, const 
  *   ints (the UI's event coordinates; then every value must be integral) -- the reference's arithmetic differs between
  *   int and float operands (exact int squares and an int 0 in atan2 against pow(x, 2.0) and -0.0),
  *   densities_host [total] nullable (1.0),
- *   count_host [n_polys] ring lengths, status_host [n_polys]: 0 ok, 1 the reference raises ZeroDivisionError, 2 more than
- *   2048 ring points, 3 fewer than 3 distinct pixels; xy_host [2*cap_points] nullable: the rings of the polygons with
+ *   count_host [n_polys] ring lengths, status_host [n_polys]: 0 ok, 1 the reference raises ZeroDivisionError (an edge of
+ *   0.5 - 1.5 spacings, or two adjacent vertices of density 0), 2 more than 2048 ring points, 3 fewer than 3 distinct pixels; xy_host [2*cap_points] nullable: the rings of the polygons with
  *   status 0, back to back in polygon order (MESHENV_E_RANGE if they do not fit).  3..256 vertices per polygon.
  */
 int meshenv_density_rings(int device, int n_polys, const int32_t *poly_offsets_host, const double *pixels_host, int integer_pixels,

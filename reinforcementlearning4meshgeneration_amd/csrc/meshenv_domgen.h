@@ -62,7 +62,7 @@ struct GenScratch {
 //   * the dict keyed by coordinates: a repeated pixel keeps its first position (and its LAST density);
 //   * edge i runs from vertex i - 1 to vertex i (edge 0 from the last vertex): A = density(prev) * base_length,
 //     B = density(i) * base_length, L = its length, x = round((2 L - A - B) / (A + B)) (Python round: half to even),
-//     e = (B - A) / x -- ZeroDivisionError for x == 0, reported per ring -- offsets A (j + 1) + e (j^2 + j) / 2 for j < x,
+//     e = (B - A) / x -- ZeroDivisionError for x == 0 and for A + B == 0, reported per ring -- offsets A (j + 1) + e (j^2 + j) / 2 for j < x,
 //     then L; points prev + offset * (cos, sin)(clockwise_angle(prev, i));
 //   * the last edge drops its middle point (index len // 2) when the total would be odd;
 //   * reversed unless the shoelace sum (builtin sum: left to right from 0) is negative; / 100.
@@ -97,7 +97,10 @@ __device__ __forceinline__ int density_ring(DensScratch *d, int m, double base_l
         const bool too_many = !(xr <= (double)kDensMaxPts);
         huge = huge || too_many;
         const int x = too_many ? kDensMaxPts : (xr < -(double)kDensMaxPts ? -kDensMaxPts : (int)xr);
-        zero = zero || x == 0;
+        // two adjacent vertices of density 0: the quotient's own division raises in the reference (A + B == 0) -- the same
+        // ZeroDivisionError as x == 0, not a ring that is too long (the quotient is +inf here and sets too_many as well;
+        // the raise is reported first below)
+        zero = zero || x == 0 || A + B == 0.0;
         d->A[i] = A; d->X[i] = x;
         d->E[i] = x != 0 ? (B - A) / xr : 0.0;
         d->cnt[i] = (x > 0 ? x : 0) + 1;                               // range(x) offsets, then L

@@ -3,7 +3,9 @@ orients, densifies and rounds one GenerateRandomPolygon-style ring per env from 
 its constants in HIP kernels.  Bar: the rings are BIT-IDENTICAL to the host restatement domains.random_domain(seed + k)
 (whose generator is pinned against the reference by tests/test_domains_cpu.py) for 8192 seeds; constants within 1e-12
 relative of the host's (BLAS dot / pow(x, 2) order effects); envs created this way step like envs created from the same
-rings through meshenv_create."""
+rings through meshenv_create.  The last section varies what the tests above keep fixed: density, fixed vertex counts in
+density mode, num_verts 5..7, an edge longer than every polygon edge, the constants of every short ring, and the refusal of
+seeds whose polygon the host regenerates."""
 import numpy as np
 import pytest
 
@@ -238,3 +240,139 @@ def test_random_density_probe_skips_seeds_the_device_cannot_generate():
     bad = seed0 + int(np.nonzero(rz == 2)[0][0])
     with pytest.raises(_capi.MeshEnvError, match=str(bad)):
         MeshVecEnv.from_random_density(2, 0, base_length=base_length, seeds=[int(env.seeds[0]), bad])
+
+
+# ------------------------------------------------------------------------------------------------ beyond the recorded parameters
+def _regenerates(seed, num_verts=None):
+    """True where domains.random_polygon_px draws a second polygon from the stream of ``seed`` (fewer than 5 distinct pixels
+    in the first): the device does not restate that and must refuse the seed."""
+    import random
+    from reinforcementlearning4meshgeneration_amd.domains import generate_polygon
+    rng = random.Random(seed)
+    nv = num_verts if num_verts is not None else rng.randint(8, 64)
+    pts = []
+    for p in generate_polygon(num_verts=nv, rng=rng):
+        if not pts or p != pts[-1]:
+            pts.append(p)
+    if len(pts) > 1 and pts[0] == pts[-1]:
+        pts.pop()
+    return len(pts) < 5
+
+
+def _assert_rings_and_constants(env, hosts):
+    """Every ring bit for bit, and the constants of EVERY ring within 1e-12 relative of domains.domain_constants (the bar
+    and its reason: test_device_rings_equal_host_restatement_8192_seeds)."""
+    from reinforcementlearning4meshgeneration_amd.domains import domain_constants
+    worst = 0.0
+    for k, host in enumerate(hosts):
+        ring, consts = env.get_domain(k)
+        want = np.asarray(host, np.float64)
+        assert ring.shape == want.shape and np.array_equal(ring, want), k
+        c = domain_constants(host)
+        ref = np.array([c.original_area, c.est_min_l ** 2, c.est_crit_l ** 2])
+        rel = np.abs(np.array(consts) - ref) / ref
+        worst = max(worst, float(rel.max()))
+        assert rel.max() <= 1e-12, (k, consts, ref)
+    return worst
+
+
+@pytest.mark.parametrize("num_verts,seed", [(5, 548), (6, 100), (7, 100)])
+@pytest.mark.parametrize("edge", [0.45, 10.0])
+def test_uniform_mode_at_the_smallest_vertex_counts(num_verts, seed, edge):
+    """num_verts 5, 6 and 7 (the least the C-ABI accepts), 64 consecutive seeds none of which regenerates; at edge 10.0 every
+    edge is one piece, the rings have 5 to 8 unequal edges, and which sorted edge srt[1] / srt[n - 2] is decides the constants."""
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    from reinforcementlearning4meshgeneration_amd.domains import random_domain
+    assert not any(_regenerates(seed + k, num_verts) for k in range(64))
+    hosts = [random_domain(seed + k, num_verts=num_verts, edge=edge) for k in range(64)]
+    if edge == 10.0:
+        assert max(map(len, hosts)) == num_verts + num_verts % 2          # one piece per edge, one more on an odd count
+    env = MeshVecEnv.from_random(64, seed, num_verts=num_verts, edge=edge)
+    worst = _assert_rings_and_constants(env, hosts)
+    print(f"num_verts {num_verts}, edge {edge}: 64 rings of {min(map(len, hosts))}..{max(map(len, hosts))} points, constants within {worst:.2e}")
+    env.close()
+
+
+def test_uniform_mode_one_piece_per_edge_bumped_and_unbumped():
+    """edge = 10.0 with the vertex count drawn per stream: every edge is one piece, so the even-count bump on the last lane
+    alone decides the ring length -- polygons of an odd count get one more point, those of an even count none."""
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv
+    from reinforcementlearning4meshgeneration_amd.domains import random_domain, random_polygon_px
+    n, seed = 256, 4000
+    assert not any(_regenerates(seed + k) for k in range(n))
+    raw = [len(random_polygon_px(seed + k)) for k in range(n)]
+    hosts = [random_domain(seed + k, edge=10.0) for k in range(n)]
+    assert all(len(h) == r + r % 2 for h, r in zip(hosts, raw))
+    bumped = sum(r % 2 for r in raw)
+    assert bumped >= 64 and n - bumped >= 64 and min(raw) <= 10 and max(raw) >= 60
+    env = MeshVecEnv.from_random(n, seed, edge=10.0)
+    worst = _assert_rings_and_constants(env, hosts)
+    assert env.max_ring == max(map(len, hosts))
+    print(f"edge 10.0: {n} rings of {min(raw)}..{max(raw)} edges, {bumped} bumped, constants within {worst:.2e}")
+    env.close()
+
+
+@pytest.mark.parametrize("num_verts,bad", [(5, 67), (5, 69), (5, 72), (6, 30), (7, 7758), (8, 2767)])
+def test_uniform_mode_refuses_a_seed_whose_polygon_regenerates(num_verts, bad):
+    """random_polygon_px draws a second polygon from the same stream on these seeds (found on the host); the device does
+    not restate that, so a batch containing one must fail loudly and return no environment -- never some other ring.  The
+    same call one seed later succeeds and equals the host, unless the host says another such seed is among its four."""
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, _capi
+    from reinforcementlearning4meshgeneration_amd.domains import random_domain
+    assert _regenerates(bad, num_verts)
+    for start in (bad, bad - 3):                      # the bad seed first and last among the four
+        with pytest.raises(_capi.MeshEnvError, match="could not be generated"):
+            MeshVecEnv.from_random(4, start, num_verts=num_verts)
+    nxt = bad + 1
+    if any(_regenerates(nxt + k, num_verts) for k in range(4)):
+        assert (num_verts, bad) in ((5, 67), (5, 69))         # 69 and 72 follow within four seeds
+        with pytest.raises(_capi.MeshEnvError, match="could not be generated"):
+            MeshVecEnv.from_random(4, nxt, num_verts=num_verts)
+        return
+    env = MeshVecEnv.from_random(4, nxt, num_verts=num_verts)
+    _assert_rings_and_constants(env, [random_domain(nxt + k, num_verts=num_verts) for k in range(4)])
+    env.close()
+
+
+@pytest.mark.parametrize("density,base_length,num_verts", [(0.5, 12.6, 0), (1.5, 4.1, 0), (0.5, 40.2, 5), (1.5, 13.4, 5),
+                                                           (0.5, 6.6, 64), (1.5, 2.2, 64)])
+def test_density_mode_at_other_densities_and_fixed_vertex_counts(density, base_length, num_verts):
+    """GenParams::density and fixed_verts together with density_mode: a block of 512 seeds at density 0.5 and 1.5, with
+    the vertex count drawn per stream, 5 and 64.  The base lengths were chosen on the host so that calculate_density is
+    defined on at least 64 seeds of the block and raises on others.  Raise flags equal the host's seed by seed wherever
+    the device generated the polygon (flag != 2); flag 2 only where the host regenerates or its ring exceeds 2048 points;
+    the rings of the defined seeds bit for bit."""
+    import ctypes as C
+    from reinforcementlearning4meshgeneration_amd import MeshVecEnv, _capi
+    from reinforcementlearning4meshgeneration_amd.domains import random_density_domain
+    L = _capi.load()
+    seed0, blk = 700_000, 512
+    nv = num_verts or None
+    host_flags = np.zeros(blk, np.uint8)
+    host_rings = {}
+    for k in range(blk):
+        try:
+            host_rings[k] = random_density_domain(seed0 + k, base_length, density, nv)
+        except ZeroDivisionError:
+            host_flags[k] = 1
+    usable = [k for k, r in host_rings.items() if len(r) <= 2048 and not _regenerates(seed0 + k, nv)]
+    assert len(usable) >= 64 and host_flags.sum() >= 3, (len(usable), int(host_flags.sum()))
+    rz = np.zeros(blk, np.uint8)
+    rc = L.meshenv_create_random_density(0, blk, C.c_uint64(seed0), None, num_verts, base_length, density, None, None, None, rz.ctypes.data)
+    assert rc in (0, _capi.E_STATE)
+    ok = rz != 2
+    assert np.array_equal(rz[ok], host_flags[ok]), (np.nonzero(ok & (rz != host_flags))[0][:8], rz[ok].sum(), host_flags[ok].sum())
+    for k in np.nonzero(~ok)[0]:
+        assert _regenerates(seed0 + int(k), nv) or (int(k) in host_rings and len(host_rings[int(k)]) > 2048), int(k)
+    defined = np.nonzero(rz == 0)[0]
+    assert set(defined.tolist()) == set(usable)
+    env = MeshVecEnv.from_random_density(len(defined), 0, base_length=base_length, density=density, num_verts=num_verts,
+                                         seeds=seed0 + defined)
+    for j, k in enumerate(defined):
+        ring, _ = env.get_domain(j)
+        host = np.asarray(host_rings[int(k)], np.float64)
+        assert ring.shape == host.shape and np.array_equal(ring, host), (int(k), ring.shape, host.shape)
+        assert len(host) % 2 == 0
+    print(f"density {density}, base_length {base_length}, num_verts {num_verts}: {len(defined)} rings identical, "
+          f"{int(host_flags.sum())} raise, {int((~ok).sum())} not generated")
+    env.close()
