@@ -12,7 +12,7 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
            "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
            "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback", "FusedOnPolicyLearn",
-           "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter"]
+           "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter", "FusedFNN", "FNNSpec", "FNNMeshResult"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -73,6 +73,9 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedOnPolicyLearn", "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter"):
         from . import onpolicy_learn
         return getattr(onpolicy_learn, name)
+    if name in ("FusedFNN", "FNNSpec", "FNNMeshResult"):
+        from . import fnn
+        return getattr(fnn, name)
     if name == "DeviceEvalCallback":
         from .eval_callback import DeviceEvalCallback
         return DeviceEvalCallback

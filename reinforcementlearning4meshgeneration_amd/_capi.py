@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -147,6 +147,14 @@ EXPORTS_TOPOLOGY = ["meshenv_mesh_topology", "meshenv_eval_set_topology", "meshe
 TOPOLOGY_DIM = 16
 TOPO_OK, TOPO_MASKED, TOPO_LOG_OVERFLOW, TOPO_DEGREE, TOPO_NOT_ARCHIVED = 0, 1, 2, 3, 4
 
+# every symbol include/meshenv_fnn.h declares: the forward of the supervised element-extraction network and the meshing loop
+# around meshenv_move
+EXPORTS_FNN = [
+    "meshenv_fnn_create", "meshenv_fnn_destroy", "meshenv_fnn_set_stream", "meshenv_fnn_last_error", "meshenv_fnn_pack",
+    "meshenv_fnn_load", "meshenv_fnn_forward", "meshenv_move_fnn_multi",
+]
+FNN_TENSORS, FNN_PACKED_FLOATS, MOVE_SKIPPED = 14, 21568, 255
+
 
 class MeshKeepEntry(C.Structure):
     """include/meshenv_eval_callback.h MeshKeepEntry: one tensor of a meshenv_keep_best call."""
@@ -265,7 +273,8 @@ def load():
                                           ("meshenv_ppo_grad", [], True), ("meshenv_rollout", [], True),
                                           ("meshenv_onpolicy_train", [], True), ("meshenv_onpolicy_learn", [], True),
                                           ("meshenv_offpolicy_train", [], True),
-                                          ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True)):
+                                          ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True),
+                                          ("meshenv_fnn", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -333,6 +342,12 @@ def load():
     L.meshenv_mesh_topology.argtypes, L.meshenv_mesh_topology.restype = [vp, C.c_int, vp, vp, vp], C.c_int
     L.meshenv_eval_set_topology.argtypes, L.meshenv_eval_set_topology.restype = [vp, vp], C.c_int
     L.meshenv_topology_selftest.argtypes, L.meshenv_topology_selftest.restype = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp], C.c_int
+    L.meshenv_fnn_pack.argtypes = [C.POINTER(vp), vp, vp]
+    L.meshenv_fnn_load.argtypes = [vp, C.POINTER(vp), vp]
+    L.meshenv_fnn_forward.argtypes = [vp, C.c_int] + [vp] * 6
+    L.meshenv_move_fnn_multi.argtypes = [vp, vp, C.c_int] + [vp] * 13
+    for name in ("meshenv_fnn_pack", "meshenv_fnn_load", "meshenv_fnn_forward", "meshenv_move_fnn_multi"):
+        getattr(L, name).restype = C.c_int
     for name in ("meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_uniform_actions", "meshenv_step_actions_multi",
                  "meshenv_episode_stats_update", "meshenv_evaluate_queued", "meshenv_eval_reduce", "meshenv_keep_best"):
         getattr(L, name).restype = C.c_int

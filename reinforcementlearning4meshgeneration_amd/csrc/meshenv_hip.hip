@@ -14,6 +14,7 @@
 #include "../../include/meshenv_offpolicy_learn.h"
 #include "../../include/meshenv_eval_callback.h"
 #include "../../include/meshenv_topology.h"
+#include "../../include/meshenv_fnn.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -49,6 +50,7 @@
 #include "meshenv_learn.h"
 #include "meshenv_eval_callback.h"
 #include "meshenv_topology.h"
+#include "meshenv_fnn.h"
 
 using namespace meshenv;
 
@@ -1144,13 +1146,17 @@ static int ensure_move_state(MeshEnv *h)
     if (!h->move_mask) rc = dev_alloc(h, &h->move_mask, (size_t)h->n_envs);
     if (rc != MESHENV_OK) return rc;
     if (move_lds_bytes(h->cap) > 64 * 1024)
+    {
         HIP_TRY(h, hipFuncSetAttribute((const void *)k_move, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(h, hipFuncSetAttribute((const void *)k_move_skip, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
     h->move_ready = true;   // only now (see ensure_smooth_state)
     return MESHENV_OK;
 }
 
-int meshenv_move(MeshEnv *h, const double *points_dev, const double *type_dev, float *obs_dev, uint8_t *done_dev,
-                 uint8_t *complete_dev, uint8_t *code_dev)
+// meshenv_move; skip_dev (meshenv_move_fnn_multi: the finished envs) is left out of k_move and, by its code, of the smoothing
+static int move_impl(MeshEnv *h, const double *points_dev, const double *type_dev, float *obs_dev, uint8_t *done_dev,
+                     uint8_t *complete_dev, uint8_t *code_dev, const uint8_t *skip_dev)
 {
     if (!h) return MESHENV_E_ARG;
     if (!points_dev || !type_dev || !obs_dev || !done_dev || !complete_dev || !code_dev) return fail_arg(h, "meshenv_move: null device pointer");
@@ -1159,8 +1165,13 @@ int meshenv_move(MeshEnv *h, const double *points_dev, const double *type_dev, f
     int rc = ensure_move_state(h);
     if (rc == MESHENV_OK) rc = ensure_libm_tables(h);   // before the first k_move: every move computes its observation alike
     if (rc != MESHENV_OK) return rc;
-    hipLaunchKernelGGL(k_move, dim3(h->n_envs), dim3(64), move_lds_bytes(h->cap), h->stream, h->S, h->cap, points_dev, type_dev,
-                       obs_dev, done_dev, complete_dev, code_dev, h->nv_xy, h->nv_count, h->nv_gid, libm_ref(h));
+    if (!skip_dev)
+        hipLaunchKernelGGL(k_move, dim3(h->n_envs), dim3(64), move_lds_bytes(h->cap), h->stream, h->S, h->cap, points_dev, type_dev,
+                           obs_dev, done_dev, complete_dev, code_dev, h->nv_xy, h->nv_count, h->nv_gid, libm_ref(h));
+    else
+        hipLaunchKernelGGL(k_move_skip, dim3(h->n_envs), dim3(64), move_lds_bytes(h->cap), h->stream, h->S, h->cap, points_dev,
+                           type_dev, obs_dev, done_dev, complete_dev, code_dev, h->nv_xy, h->nv_count, h->nv_gid, libm_ref(h),
+                           skip_dev);
     HIP_TRY(h, hipGetLastError());
     if (smoothing_fits(h, true)) {
         // B:405-426: the envs k_move left at "no selectable reference vertex" go through smooth_pave and select again
@@ -1180,6 +1191,12 @@ int meshenv_move(MeshEnv *h, const double *points_dev, const double *type_dev, f
         h->reselect_pending = false;
     }
     return MESHENV_OK;
+}
+
+int meshenv_move(MeshEnv *h, const double *points_dev, const double *type_dev, float *obs_dev, uint8_t *done_dev,
+                 uint8_t *complete_dev, uint8_t *code_dev)
+{
+    return move_impl(h, points_dev, type_dev, obs_dev, done_dev, complete_dev, code_dev, nullptr);
 }
 
 int meshenv_smooth(MeshEnv *h, int which, const uint8_t *mask_dev, int iteration, int interior, int is_static, int32_t *sweeps_dev,
@@ -4256,6 +4273,187 @@ int meshenv_keep_best(MeshEvalCallback *c, const MeshKeepEntry *entries_host, in
     return launch(c, guard, "meshenv_keep_best", [&] {
         hipLaunchKernelGGL(k_keep_best, dim3(chunks, n_entries), dim3(kKeepThreads), 0, c->stream, best_dev, improved_dev, T);
     });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the FNN mesher (include/meshenv_fnn.h)
+struct MeshFnn : HandleBase {
+    float *buf = nullptr;        // the packed weights, MESHENV_FNN_PACKED_FLOATS
+    bool loaded = false;
+    // meshenv_move_fnn_multi without histories: the points / types / code / done / complete of the step in flight
+    char *scratch = nullptr;
+    int scratch_envs = 0;
+};
+
+namespace {
+
+static_assert(kFnnPackedFloats == MESHENV_FNN_PACKED_FLOATS, "csrc/meshenv_fnn.h and include/meshenv_fnn.h disagree");
+static_assert(kMoveSkipped == MESHENV_MOVE_SKIPPED, "csrc/meshenv_kernels.h and include/meshenv_fnn.h disagree");
+
+const char *kFnnShapes = "supported network: fc1 [64][18], fc2 [128][64], fc3 [64][128], fc4 [32][64], fc5 [16][32], action_head "
+                         "[2][16], type_head [3][16], each with a bias of its rows (general/EBRD.py Policy)";
+
+// rows of the seven layers, in MESHENV_FNN_TENSORS' order; the two heads are layer 5's rows 0-1 and 2-4
+const int kFnnRows[7] = {64, 128, 64, 32, 16, kFnnAction, kFnnTypes};
+
+std::string fnn_pack(const float *const *tensors, const int32_t *shapes, float *out)
+{
+    if (!tensors || !shapes || !out) return "null pointer";
+    for (int i = 0; i < 7; i++) {
+        const int rows = kFnnRows[i], cols = fnn_in(i < 5 ? i : 5);
+        if (!tensors[2 * i] || !tensors[2 * i + 1]) return "null tensor pointer";
+        const int32_t *sw = shapes + 4 * i, *sb = sw + 2;
+        if (sw[0] != rows || sw[1] != cols || sb[0] != rows || sb[1] != 1)
+            return "tensor pair " + std::to_string(i) + " has shapes [" + std::to_string(sw[0]) + "][" + std::to_string(sw[1]) + "], [" +
+                   std::to_string(sb[0]) + "]; " + kFnnShapes;
+    }
+    std::memset(out, 0, sizeof(float) * (size_t)kFnnPackedFloats);
+    // torch [out][in] -> the per-lane MFMA B-operand order of meshenv_policy.h: [tile][K/16][lane][4]; `row0`: the tensor's first
+    // row in the layer's tiles (the type_head behind the action_head)
+    auto packed = [&](const float *w, const float *b, int l, int rows, int row0) {
+        const int in = fnn_in(l), groups = fnn_k(l) / 16;
+        float *wp = out + fnn_w_offset(l), *bp = out + fnn_b_offset(l);
+        for (int tile = 0; tile < fnn_tiles(l); tile++)
+            for (int g = 0; g < groups; g++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int j = 0; j < 4; j++) {
+                        const int k = 4 * (4 * g + j) + (lane >> 4), n = 16 * tile + (lane & 15) - row0;
+                        if (k < in && n >= 0 && n < rows) wp[(((size_t)tile * groups + g) * 64 + lane) * 4 + j] = w[(size_t)n * in + k];
+                    }
+        for (int n = 0; n < rows; n++) bp[row0 + n] = b[n];
+    };
+    for (int l = 0; l < 5; l++) packed(tensors[2 * l], tensors[2 * l + 1], l, kFnnRows[l], 0);
+    packed(tensors[10], tensors[11], 5, kFnnAction, 0);
+    packed(tensors[12], tensors[13], 5, kFnnTypes, kFnnAction);
+    return std::string();
+}
+
+int fnn_launch(MeshFnn *f, const char *fn, const FnnArgs &A)
+{
+    DeviceGuard guard(f->device);
+    return launch(f, guard, fn, [&] {
+        hipLaunchKernelGGL(k_fnn_forward, dim3((A.n + kFnnEnvs - 1) / kFnnEnvs), dim3(64 * kFnnWaves), 0, f->stream, A);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_fnn_create(int device, void *stream, MeshFnn **out) { return create_handle("meshenv_fnn_create", device, stream, out); }
+
+void meshenv_fnn_destroy(MeshFnn *f)
+{
+    if (f && f->scratch) {
+        DeviceGuard guard(f->device);
+        (void)hipStreamSynchronize(f->stream);
+        (void)hipFree(f->scratch);
+    }
+    destroy_handle(f, f ? f->buf : nullptr);
+}
+
+int meshenv_fnn_set_stream(MeshFnn *f, void *stream) { return set_stream(f, stream); }
+
+const char *meshenv_fnn_last_error(const MeshFnn *f) { return last_error(f); }
+
+int meshenv_fnn_pack(const float *const *tensors, const int32_t *shapes, float *out_host)
+{
+    const std::string refusal = fnn_pack(tensors, shapes, out_host);
+    if (refusal.empty()) return MESHENV_OK;
+    g_create_error = "meshenv_fnn_pack: " + refusal;
+    return MESHENV_E_ARG;
+}
+
+int meshenv_fnn_load(MeshFnn *f, const float *const *tensors, const int32_t *shapes)
+{
+    if (!f) return MESHENV_E_ARG;
+    std::vector<float> h((size_t)kFnnPackedFloats);
+    const std::string refusal = fnn_pack(tensors, shapes, h.data());
+    if (!refusal.empty()) return fail(f, MESHENV_E_ARG, "meshenv_fnn_load: " + refusal);
+    DeviceGuard guard(f->device);
+    if (guard.err != hipSuccess) return fail(f, MESHENV_E_HIP, "meshenv_fnn_load: hipSetDevice failed");
+    (void)hipStreamSynchronize(f->stream);   // the previous weights may still be in use
+    f->loaded = false;
+    if ((!f->buf && hipMalloc((void **)&f->buf, h.size() * sizeof(float)) != hipSuccess) ||
+        hipMemcpy(f->buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(f, MESHENV_E_HIP, "meshenv_fnn_load: upload failed");
+    f->loaded = true;
+    return MESHENV_OK;
+}
+
+int meshenv_fnn_forward(MeshFnn *f, int n, const float *obs_dev, const uint8_t *finished_dev, double *points_dev,
+                        double *types_dev, float *actions_dev, float *logits_dev)
+{
+    if (!f) return MESHENV_E_ARG;
+    if (!f->loaded) return fail(f, MESHENV_E_STATE, "meshenv_fnn_forward: no weights loaded");
+    if (n <= 0 || !obs_dev) return fail(f, MESHENV_E_ARG, "meshenv_fnn_forward: n > 0 and obs_dev are required");
+    if (!points_dev && !types_dev && !actions_dev && !logits_dev) return fail(f, MESHENV_E_ARG, "meshenv_fnn_forward: no output requested");
+    FnnArgs A{};
+    A.packed = f->buf; A.n = n; A.obs = obs_dev; A.finished = finished_dev;
+    A.points = points_dev; A.types = types_dev; A.actions = actions_dev; A.logits = logits_dev;
+    return fnn_launch(f, "meshenv_fnn_forward", A);
+}
+
+int meshenv_move_fnn_multi(MeshEnv *h, MeshFnn *f, int T, float *obs_dev, uint8_t *finished_dev, int32_t *steps_dev,
+                           uint8_t *done_dev, uint8_t *complete_dev, uint8_t *code_dev, int32_t *n_elements_dev,
+                           double *hist_points_dev, double *hist_types_dev, float *hist_obs_dev, uint8_t *hist_code_dev,
+                           uint8_t *hist_done_dev, uint8_t *hist_complete_dev)
+{
+    if (!h || !f) return MESHENV_E_ARG;
+    if (T <= 0 || !obs_dev || !finished_dev || !steps_dev || !done_dev || !complete_dev || !code_dev)
+        return fail_arg(h, "meshenv_move_fnn_multi: T > 0 and non-null obs, finished, steps, done, complete and code are required");
+    if (!f->loaded) {
+        h->err = "meshenv_move_fnn_multi: the network has no weights loaded";
+        return MESHENV_E_STATE;
+    }
+    if (f->device != h->device || f->stream != h->stream) {   // the forward and move launches are ordered by the stream alone
+        h->err = "meshenv_move_fnn_multi: env and network must be on the same device and stream (meshenv_set_stream / "
+                 "meshenv_fnn_set_stream)";
+        return MESHENV_E_STATE;
+    }
+    MESHENV_ON_DEVICE(h);
+    const size_t n = (size_t)h->n_envs;
+    if (f->scratch_envs < h->n_envs) {   // [n][2] + [n] doubles, 3 x [n] bytes
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (f->scratch) (void)hipFree(f->scratch);
+        f->scratch = nullptr;
+        f->scratch_envs = 0;
+        HIP_TRY(h, hipMalloc((void **)&f->scratch, n * (3 * sizeof(double) + 3)));
+        f->scratch_envs = h->n_envs;
+    }
+    double *s_points = (double *)f->scratch, *s_types = s_points + 2 * n;
+    uint8_t *s_code = (uint8_t *)(s_types + n), *s_done = s_code + n, *s_complete = s_done + n;
+    FnnArgs A{};
+    A.packed = f->buf; A.n = (int)n; A.obs = obs_dev; A.finished = finished_dev;
+    const int nb = (h->n_envs + 255) / 256;
+    for (int t = 0; t < T; t++) {
+        const size_t row = (size_t)t * n;
+        A.points = hist_points_dev ? hist_points_dev + 2 * row : s_points;
+        A.types = hist_types_dev ? hist_types_dev + row : s_types;
+        A.obs_copy = hist_obs_dev ? hist_obs_dev + row * kObsDim : nullptr;
+        uint8_t *code_t = hist_code_dev ? hist_code_dev + row : s_code;
+        uint8_t *done_t = hist_done_dev ? hist_done_dev + row : s_done;
+        uint8_t *complete_t = hist_complete_dev ? hist_complete_dev + row : s_complete;
+        const bool timed = h->timing == 1 && !h->ev.empty();
+        const size_t slot = (size_t)(h->ev_count % MESHENV_TIMING_POOL);
+        if (timed) HIP_TRY(h, hipEventRecord(h->ev[2 * slot], h->stream));
+        const int rf = fnn_launch(f, "meshenv_move_fnn_multi", A);
+        if (rf != MESHENV_OK) {
+            h->err = f->err;
+            return rf;
+        }
+        if (timed) {
+            HIP_TRY(h, hipEventRecord(h->ev[2 * slot + 1], h->stream));
+            h->ev_count += 1;
+        }
+        const int rm = move_impl(h, A.points, A.types, obs_dev, done_t, complete_t, code_t, finished_dev);
+        if (rm != MESHENV_OK) return rm;
+        hipLaunchKernelGGL(k_fnn_advance, dim3(nb), dim3(256), 0, h->stream, h->S, finished_dev, steps_dev, (const uint8_t *)done_t,
+                           (const uint8_t *)complete_t, (const uint8_t *)code_t, done_dev, complete_dev, code_dev, n_elements_dev);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return MESHENV_OK;
 }
 
 }  // extern "C"

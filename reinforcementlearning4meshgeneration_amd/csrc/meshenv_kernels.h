@@ -1980,11 +1980,12 @@ __host__ __device__ __forceinline__ size_t move_lds_bytes(int cap) { return lds_
 // kMoveRaises (ring <= 5 or no reference vertex on entry: the reference raises UnboundLocalError; nothing changes),
 // kMoveNeedsSmoothing (no selectable vertex left on a ring of more than 4: the reference runs smooth_pave -- not built
 // -- and retries; here done = 1, complete = 0 and the caller resets).
-__global__ void __launch_bounds__(64) k_move(DevState S, int cap, const double *__restrict__ points,
-                                              const double *__restrict__ types, float *__restrict__ obs_out,
-                                              uint8_t *__restrict__ done, uint8_t *__restrict__ complete,
-                                              uint8_t *__restrict__ code, double2 *__restrict__ nv_xy,
-                                              int32_t *__restrict__ nv_count, int32_t *__restrict__ nv_gid, const LibmRef lr)
+// (the body as a function: k_move is just this; k_move_skip, below, puts a skip mask in front of it)
+__device__ __forceinline__ void move_body(const DevState &S, int cap, const double *__restrict__ points,
+                                          const double *__restrict__ types, float *__restrict__ obs_out,
+                                          uint8_t *__restrict__ done, uint8_t *__restrict__ complete,
+                                          uint8_t *__restrict__ code, double2 *__restrict__ nv_xy,
+                                          int32_t *__restrict__ nv_count, int32_t *__restrict__ nv_gid, const LibmRef &lr)
 {
     extern __shared__ double2 smem[];
     Ctx c;
@@ -2046,6 +2047,35 @@ __global__ void __launch_bounds__(64) k_move(DevState S, int cap, const double *
         nv_count[env] = n_nv;
     }
     store_env(c, S, ring_unchanged);
+}
+
+__global__ void __launch_bounds__(64) k_move(DevState S, int cap, const double *__restrict__ points,
+                                              const double *__restrict__ types, float *__restrict__ obs_out,
+                                              uint8_t *__restrict__ done, uint8_t *__restrict__ complete,
+                                              uint8_t *__restrict__ code, double2 *__restrict__ nv_xy,
+                                              int32_t *__restrict__ nv_count, int32_t *__restrict__ nv_gid, const LibmRef lr)
+{
+    move_body(S, cap, points, types, obs_out, done, complete, code, nv_xy, nv_count, nv_gid, lr);
+}
+
+// k_move under a skip mask (meshenv_move_fnn_multi: the envs that have finished their episode).  An env with skip[e] != 0 is
+// not touched -- ring, record, logs, not_valid_points and its row of obs_out stay as they are; its code is kMoveSkipped (which
+// k_move_mask does not take for kMoveNeedsSmoothing, so the smoothing launches skip it too), done = complete = 0.
+enum { kMoveSkipped = 255 };
+
+__global__ void __launch_bounds__(64) k_move_skip(DevState S, int cap, const double *__restrict__ points,
+                                                   const double *__restrict__ types, float *__restrict__ obs_out,
+                                                   uint8_t *__restrict__ done, uint8_t *__restrict__ complete,
+                                                   uint8_t *__restrict__ code, double2 *__restrict__ nv_xy,
+                                                   int32_t *__restrict__ nv_count, int32_t *__restrict__ nv_gid, const LibmRef lr,
+                                                   const uint8_t *__restrict__ skip)
+{
+    const int env = blockIdx.x;
+    if (uniform_i32(skip[env]) != 0) {
+        if (lane_id() == 0) { done[env] = 0; complete[env] = 0; code[env] = (uint8_t)kMoveSkipped; }
+        return;
+    }
+    move_body(S, cap, points, types, obs_out, done, complete, code, nv_xy, nv_count, nv_gid, lr);
 }
 
 // ------------------------------------------------------------------------------------------ CU-group step kernel

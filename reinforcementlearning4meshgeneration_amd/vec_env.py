@@ -343,6 +343,14 @@ class MeshVecEnv:
             mptr = C.c_void_p(mask.data_ptr())
         self._check(self._L.meshenv_reset_static(self._handle, mptr, C.c_void_p(self.obs.data_ptr()), 1 if static else 0),
                     "meshenv_reset_static")
+        st = getattr(self, "_fnn_state", None)
+        if st is not None:      # a reset env is no longer a finished one of mesh_with
+            if mask is None:
+                self._fnn_state = None
+            else:
+                keep = mask == 0
+                st["finished"] *= keep
+                st["steps"] *= keep
         return self.obs
 
     reset = reset_tensor      # SB3MeshVecEnv overrides reset() / step() with the VecEnv (numpy) forms
@@ -365,6 +373,85 @@ class MeshVecEnv:
         self._check(rc, "meshenv_move")
         self._warn_if_libm_inexact()
         return self.obs, self.done, self.complete, self.move_code
+
+    def move_fnn(self, fnn, T: int, state: dict, record: bool = False) -> dict:
+        """T iterations of ``action, type = get_action(state, model); state, _, done, info = env.move(action, round(type, 2))``
+        (general/EBRD.py:541-548) for every env in ONE call (meshenv_move_fnn_multi): T forwards of ``fnn`` (a FusedFNN on this
+        device) on ``self.obs`` and T moves, enqueued with no host work in between.  ``state``: the uint8 / int32 CUDA tensors
+        finished, steps, done, complete, code, n_elements [n], updated in place; an env finishes at the move that returns done or
+        code >= MOVE_RAISES and is left exactly as it is from then on.  record=True returns the histories of these T steps
+        (points [T, n, 2], types [T, n], obs [T, n, 18], step_code / step_done / step_complete [T, n]).  ``mesh_with`` is the
+        loop around this."""
+        from .fnn import FusedFNN
+        t = self._torch
+        if not isinstance(fnn, FusedFNN):
+            raise TypeError(f"fnn must be a FusedFNN, got {type(fnn).__name__}")
+        if fnn.device != self.device:
+            raise ValueError(f"the network is on {fnn.device}, the envs on {self.device}")
+        if isinstance(T, bool) or int(T) != T or not 1 <= T < 2 ** 31:
+            raise ValueError(f"T must be an integer >= 1, got {T!r}")
+        n, T = self.num_envs, int(T)
+        hist = {}
+        if record:
+            u8 = dict(dtype=t.uint8, device=self.device)
+            hist = dict(points=t.empty((T, n, 2), dtype=t.float64, device=self.device),
+                        types=t.empty((T, n), dtype=t.float64, device=self.device),
+                        obs=t.empty((T, n, OBS_DIM), dtype=t.float32, device=self.device),
+                        step_code=t.empty((T, n), **u8), step_done=t.empty((T, n), **u8), step_complete=t.empty((T, n), **u8))
+        hp = lambda k: hist[k].data_ptr() if record else None    # noqa: E731
+        self._bind_stream()
+        fnn._bind_stream()
+        rc = self._L.meshenv_move_fnn_multi(self._handle, fnn._h, T, self.obs.data_ptr(), state["finished"].data_ptr(),
+                                            state["steps"].data_ptr(), state["done"].data_ptr(), state["complete"].data_ptr(),
+                                            state["code"].data_ptr(), state["n_elements"].data_ptr(), hp("points"), hp("types"),
+                                            hp("obs"), hp("step_code"), hp("step_done"), hp("step_complete"))
+        self._check(rc, "meshenv_move_fnn_multi")
+        self._warn_if_libm_inexact()
+        return hist
+
+    def _new_fnn_state(self) -> dict:
+        t = self._torch
+        z = lambda dt: t.zeros(self.num_envs, dtype=dt, device=self.device)   # noqa: E731
+        return dict(finished=z(t.uint8), steps=z(t.int32), done=z(t.uint8), complete=z(t.uint8), code=z(t.uint8),
+                    n_elements=z(t.int32))
+
+    def mesh_with(self, fnn, max_steps: int = 2000, check_every: int = 32, record: bool = False, reset: bool = True):
+        """Mesh every env's domain with the supervised network ``fnn`` (a FusedFNN): the loop of general/EBRD.py:525-548,
+        ``state = env.reset(static=True)``, then get_action + move until ``done``, on the device.  Runs chunks of check_every
+        moves (``move_fnn``) and reads ``finished.all()`` back once per chunk -- the polling idiom of ``evaluate`` -- until every
+        env has finished or max_steps moves were made.  reset=False continues the running episodes (and the finished flags of
+        the previous call; envs reset in between start over).  Needs auto_reset=False and log_capacity > 0 (ValueError
+        otherwise): the meshes stay in the running episode of the handle, where ``smooth(which="current")`` (EBRD.py:566),
+        ``element_quality``, ``mesh_topology``, ``extract_samples`` (all with which="current") and ``get_elements`` read them.
+        Returns an FNNMeshResult; record=True adds the per-step histories."""
+        from .fnn import FNNMeshResult
+        if self.auto_reset:
+            raise ValueError("mesh_with needs a MeshVecEnv created with auto_reset=False: move() has no auto-reset, and the "
+                             "finished meshes are read from the running episodes")
+        if self.log_capacity <= 0:
+            raise ValueError("mesh_with needs a MeshVecEnv created with log_capacity > 0: without an element log the "
+                             "smooth_pave inside move() cannot run and there is no mesh to read afterwards")
+        for name, v in (("max_steps", max_steps), ("check_every", check_every)):
+            if isinstance(v, bool) or int(v) != v or not 1 <= v < 2 ** 31:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        t = self._torch
+        if reset:
+            self.reset_tensor(static=True)
+        if reset or getattr(self, "_fnn_state", None) is None:
+            self._fnn_state = self._new_fnn_state()
+        st = self._fnn_state
+        chunks, total = [], 0
+        while total < max_steps:
+            T = min(int(check_every), int(max_steps) - total)
+            chunks.append(self.move_fnn(fnn, T, st, record=record))
+            total += T
+            if bool(st["finished"].all().item()):
+                break
+        res = FNNMeshResult(total_steps=total, **{k: v.clone() for k, v in st.items()})
+        if record:
+            for k in chunks[0]:
+                setattr(res, k, t.cat([c[k] for c in chunks], 0))
+        return res
 
     @property
     def step_kernel(self) -> str:
