@@ -8,7 +8,7 @@
  *         if done: break
  * for every environment of a handle as ONE call that enqueues T forwards and T moves with no host work and no synchronisation
  * in between (csrc/meshenv_fnn.h: k_fnn_forward, k_fnn_advance; csrc/meshenv_kernels.h: k_move_skip).
- * Inference only: the training of the network (EBRD.py train_ch3) is not here.  The conventions are those of meshenv.h (return
+ * The inference half: the training of the network (EBRD.py train_ch3) is meshenv_fnn_train.h's.  The conventions are those of meshenv.h (return
  * codes MESHENV_E_*, *_dev device pointers owned by the caller, one GPU and one stream per handle, no CPU fallback); the entry
  * points live in a header of their own, as those of meshenv_ppo_grad.h and meshenv_topology.h do: meshenv.h and
  * MESHENV_ABI_VERSION are unchanged.

@@ -12,7 +12,8 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "FusedPPOGrad", "PPOGradSpec", "DeviceRolloutBuffer", "RolloutBufferSamples", "FusedOnPolicyTrain", "OnPolicyTrainSpec",
            "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
            "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback", "FusedOnPolicyLearn",
-           "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter", "FusedFNN", "FNNSpec", "FNNMeshResult"]
+           "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter", "FusedFNN", "FNNSpec", "FNNMeshResult",
+           "FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -76,6 +77,9 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedFNN", "FNNSpec", "FNNMeshResult"):
         from . import fnn
         return getattr(fnn, name)
+    if name in ("FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog"):
+        from . import fnn_train
+        return getattr(fnn_train, name)
     if name == "DeviceEvalCallback":
         from .eval_callback import DeviceEvalCallback
         return DeviceEvalCallback

@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -155,6 +155,14 @@ EXPORTS_FNN = [
 ]
 FNN_TENSORS, FNN_PACKED_FLOATS, MOVE_SKIPPED = 14, 21568, 255
 
+# every symbol include/meshenv_fnn_train.h declares: the loss gradient of the supervised network (train_ch3) and the refresh of a
+# loaded FusedFNN from its live tensors
+EXPORTS_FNN_TRAIN = [
+    "meshenv_fnn_grad_create", "meshenv_fnn_grad_destroy", "meshenv_fnn_grad_set_stream", "meshenv_fnn_grad_last_error",
+    "meshenv_fnn_grad_bind", "meshenv_fnn_grad_backward", "meshenv_fnn_bind", "meshenv_fnn_refresh",
+]
+FNN_GRAD_FLOATS, FNN_GRAD_OUTPUTS, FNN_GRAD_MAX_GROUPS = 20544, 4, 128
+
 
 class MeshKeepEntry(C.Structure):
     """include/meshenv_eval_callback.h MeshKeepEntry: one tensor of a meshenv_keep_best call."""
@@ -274,7 +282,7 @@ def load():
                                           ("meshenv_onpolicy_train", [], True), ("meshenv_onpolicy_learn", [], True),
                                           ("meshenv_offpolicy_train", [], True),
                                           ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True),
-                                          ("meshenv_fnn", [], True)):
+                                          ("meshenv_fnn", [], True), ("meshenv_fnn_grad", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -346,7 +354,12 @@ def load():
     L.meshenv_fnn_load.argtypes = [vp, C.POINTER(vp), vp]
     L.meshenv_fnn_forward.argtypes = [vp, C.c_int] + [vp] * 6
     L.meshenv_move_fnn_multi.argtypes = [vp, vp, C.c_int] + [vp] * 13
-    for name in ("meshenv_fnn_pack", "meshenv_fnn_load", "meshenv_fnn_forward", "meshenv_move_fnn_multi"):
+    L.meshenv_fnn_grad_bind.argtypes = [vp, C.POINTER(vp), vp, C.c_int64]
+    L.meshenv_fnn_grad_backward.argtypes = [vp, C.c_int, C.c_int] + [vp] * 5
+    L.meshenv_fnn_bind.argtypes = [vp, C.POINTER(vp)]
+    L.meshenv_fnn_refresh.argtypes = [vp]
+    for name in ("meshenv_fnn_pack", "meshenv_fnn_load", "meshenv_fnn_forward", "meshenv_move_fnn_multi", "meshenv_fnn_grad_bind",
+                 "meshenv_fnn_grad_backward", "meshenv_fnn_bind", "meshenv_fnn_refresh"):
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_actor_bind", "meshenv_actor_refresh", "meshenv_uniform_actions", "meshenv_step_actions_multi",
                  "meshenv_episode_stats_update", "meshenv_evaluate_queued", "meshenv_eval_reduce", "meshenv_keep_best"):

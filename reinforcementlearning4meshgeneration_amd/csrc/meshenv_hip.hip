@@ -15,6 +15,7 @@
 #include "../../include/meshenv_eval_callback.h"
 #include "../../include/meshenv_topology.h"
 #include "../../include/meshenv_fnn.h"
+#include "../../include/meshenv_fnn_train.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -51,6 +52,7 @@
 #include "meshenv_eval_callback.h"
 #include "meshenv_topology.h"
 #include "meshenv_fnn.h"
+#include "meshenv_fnn_grad.h"
 
 using namespace meshenv;
 
@@ -4284,6 +4286,9 @@ struct MeshFnn : HandleBase {
     // meshenv_move_fnn_multi without histories: the points / types / code / done / complete of the step in flight
     char *scratch = nullptr;
     int scratch_envs = 0;
+    PackTable table{};           // meshenv_fnn_bind: the live tensors and where meshenv_fnn_refresh packs them
+    int n_copies = 0;
+    bool live = false;
 };
 
 namespace {
@@ -4454,6 +4459,123 @@ int meshenv_move_fnn_multi(MeshEnv *h, MeshFnn *f, int T, float *obs_dev, uint8_
         HIP_TRY(h, hipGetLastError());
     }
     return MESHENV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ training the FNN mesher (include/meshenv_fnn_train.h)
+static_assert(MESHENV_FNN_GRAD_FLOATS == FgLayout::stride && MESHENV_FNN_GRAD_OUTPUTS == kFgOut && MESHENV_FNN_GRAD_MAX_GROUPS == kCgMaxGroups,
+              "include/meshenv_fnn_train.h and csrc/meshenv_fnn_grad.h disagree");
+static_assert(2 * kFgLayers == MESHENV_FNN_TENSORS && MESHENV_FNN_TENSORS <= kTgtMaxCopies, "the copy table holds the 14 sources");
+
+struct MeshFnnGrad : HandleBase {
+    const float *w[kFgLayers]{}, *b[kFgLayers]{};
+    float *grad = nullptr;          // the caller's flat gradient buffer (FgLayout::stride floats)
+    float *partial = nullptr;       // kCgMaxGroups partial sets; zeroed once
+    bool bound = false;
+};
+
+extern "C" {
+
+int meshenv_fnn_grad_create(int device, void *stream, MeshFnnGrad **out)
+{
+    return create_handle("meshenv_fnn_grad_create", device, stream, out);
+}
+
+void meshenv_fnn_grad_destroy(MeshFnnGrad *g) { destroy_handle(g, g ? g->partial : nullptr); }
+
+const char *meshenv_fnn_grad_last_error(const MeshFnnGrad *g) { return last_error(g); }
+
+int meshenv_fnn_grad_set_stream(MeshFnnGrad *g, void *stream) { return set_stream(g, stream); }
+
+int meshenv_fnn_grad_bind(MeshFnnGrad *g, const float *const *tensors_dev, float *grad_dev, int64_t n_grad)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!tensors_dev) return fail(g, MESHENV_E_ARG, std::string("meshenv_fnn_grad_bind: takes 14 tensors; ") + kFnnShapes);
+    if (!grad_dev || n_grad != FgLayout::stride)
+        return fail(g, MESHENV_E_ARG, "meshenv_fnn_grad_bind: the gradient buffer has " + std::to_string(FgLayout::stride) + " floats, got " +
+                       std::to_string((long long)n_grad));
+    for (int i = 0; i < MESHENV_FNN_TENSORS; i++) {
+        if (!tensors_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_fnn_grad_bind: null tensor");
+        // the weights behind fc1 are read 16 bytes at a time
+        if (i % 2 == 0 && i >= 2 && ((uintptr_t)tensors_dev[i] & 15))
+            return fail(g, MESHENV_E_ARG, "meshenv_fnn_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_fnn_grad_bind: hipSetDevice failed");
+    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * FgLayout::set))
+        return fail(g, MESHENV_E_HIP, "meshenv_fnn_grad_bind: allocation failed");
+    for (int l = 0; l < kFgLayers; l++) {
+        g->w[l] = tensors_dev[2 * l];
+        g->b[l] = tensors_dev[2 * l + 1];
+    }
+    g->grad = grad_dev;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_fnn_grad_backward(MeshFnnGrad *g, int n, int N, const float *x_dev, const float *y_dev, const int32_t *rows_dev,
+                              float *out_dev, float *accum_dev)
+{
+    if (!g) return MESHENV_E_ARG;
+    const char *fn = "meshenv_fnn_grad_backward";
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_fnn_grad_bind)");
+    if (n <= 0 || N <= 0 || N > (1 << 24) || n > (1 << 24) || !x_dev || !y_dev || !out_dev || (!rows_dev && n > N))
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": 0 < n, N <= 2^24, n <= N without rows_dev, and x, y and out are required");
+    FgArgs A{};
+    A.n = n; A.N = N;
+    const int tiles = (n + kCgRows - 1) / kCgRows;
+    A.nwg = tiles < kCgMaxGroups ? tiles : kCgMaxGroups;
+    A.x = x_dev; A.y = y_dev; A.rows = rows_dev;
+    for (int l = 0; l < kFgLayers; l++) {
+        A.w[l] = g->w[l];
+        A.b[l] = g->b[l];
+    }
+    A.partial = g->partial;
+    DeviceGuard guard(g->device);
+    const int rc = launch(g, guard, fn, [&] { hipLaunchKernelGGL(k_fnn_grad, dim3(A.nwg), dim3(kFgThreads), 0, g->stream, A); });
+    if (rc != MESHENV_OK) return rc;
+    return launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(k_fnn_grad_reduce, dim3((FgLayout::params + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial,
+                           A.nwg, g->grad, out_dev, accum_dev);
+    }, "reduction launch");
+}
+
+// ---- live weights into a loaded FusedFNN (the twin of meshenv_policy_bind / meshenv_policy_refresh)
+int meshenv_fnn_bind(MeshFnn *f, const float *const *tensors_dev)
+{
+    if (!f) return MESHENV_E_ARG;
+    if (!f->loaded) return fail(f, MESHENV_E_STATE, "meshenv_fnn_bind: no weights loaded (meshenv_fnn_load lays the buffer out)");
+    if (!tensors_dev) return fail(f, MESHENV_E_ARG, std::string("meshenv_fnn_bind: takes 14 tensors; ") + kFnnShapes);
+    for (int i = 0; i < MESHENV_FNN_TENSORS; i++)
+        if (!tensors_dev[i]) return fail(f, MESHENV_E_ARG, "meshenv_fnn_bind: null tensor");
+    f->n_copies = 0;
+    // fnn_pack's layout: layer l's weight tiles at fnn_w_offset(l), its bias behind them; `row0`: the tensor's first row in
+    // the layer's tiles (the type_head behind the action_head)
+    auto add = [&](const float *w, const float *b, int l, int rows, int row0) {
+        PackCopy &cw = f->table.c[f->n_copies++];
+        cw.src = w; cw.dst = f->buf + fnn_w_offset(l); cw.out = rows; cw.in = fnn_in(l); cw.groups = fnn_k(l) / 16; cw.tiles = fnn_tiles(l);
+        cw.n_off = row0; cw.kind = kPackMatrix;
+        PackCopy &cb = f->table.c[f->n_copies++];
+        cb.src = b; cb.dst = f->buf + fnn_b_offset(l); cb.out = rows; cb.in = 0; cb.groups = 0; cb.tiles = 0; cb.n_off = row0; cb.kind = kPackVector;
+    };
+    for (int l = 0; l < 5; l++) add(tensors_dev[2 * l], tensors_dev[2 * l + 1], l, kFnnRows[l], 0);
+    add(tensors_dev[10], tensors_dev[11], 5, kFnnAction, 0);
+    add(tensors_dev[12], tensors_dev[13], 5, kFnnTypes, kFnnAction);
+    f->live = true;
+    return MESHENV_OK;
+}
+
+int meshenv_fnn_refresh(MeshFnn *f)
+{
+    if (!f) return MESHENV_E_ARG;
+    if (!f->loaded || !f->live) return fail(f, MESHENV_E_STATE, "meshenv_fnn_refresh: no tensors bound (meshenv_fnn_bind)");
+    DeviceGuard guard(f->device);
+    // k_target_pack (meshenv_target.h) is the pack kernel; what it does not write (the padding of K and of the head tile)
+    // meshenv_fnn_load left zero.  The largest copies (fc2, fc3) have 32 groups of 256 floats: 32 blocks cover them in one pass.
+    return launch(f, guard, "meshenv_fnn_refresh", [&] {
+        hipLaunchKernelGGL(k_target_pack, dim3(32, f->n_copies), dim3(256), 0, f->stream, f->table);
+    });
 }
 
 }  // extern "C"

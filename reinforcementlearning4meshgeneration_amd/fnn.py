@@ -1,8 +1,9 @@
 """The supervised element-extraction network of the reference ("FNN mesher", general/EBRD.py: ``Policy`` :85-126,
 ``get_action`` :174-177) on the GPU (include/meshenv_fnn.h, csrc/meshenv_fnn.h): observation -> (new point, rule type) in
 one launch, and -- through ``MeshVecEnv.mesh_with`` -- the meshing loop of EBRD.py:525-548 for every env of a batch without a
-host round trip per move.  Inference only: the network is trained elsewhere (EBRD.py ``train_ch3``), and no trained weights
-ship with this package because the reference holds no weights file.
+host round trip per move.  This module is the inference half; the training of the network (EBRD.py ``train_ch3``) is
+``fnn_train.FusedFNNTrain``, whose stepped parameters reach a loaded ``FusedFNN`` through ``bind_live`` + ``refresh`` without
+leaving the device.  No trained weights ship with this package because the reference holds no weights file.
 
 ``FNNSpec`` is the host half (the fourteen tensors as float32 arrays, their packed form; no device needed); ``FusedFNN``
 loads one on a GPU."""
@@ -23,6 +24,25 @@ LAYERS = (("fc1", 64, 18), ("fc2", 128, 64), ("fc3", 64, 128), ("fc4", 32, 64), 
 SUPPORTED = ("fc1 [64, 18], fc2 [128, 64], fc3 [64, 128], fc4 [32, 64], fc5 [16, 32], action_head [2, 16], type_head [3, 16], "
              "each with a bias, ReLU between them (general/EBRD.py Policy)")
 PACKED_FLOATS = 21568
+
+
+def live_parameters(module):
+    """The fourteen LIVE parameter tensors of a Policy-shaped torch module, in MESHENV_FNN_TENSORS' order: float32, contiguous,
+    of exactly the shapes of LAYERS.  ValueError names what is wrong and what is supported."""
+    import torch
+    params = []
+    for name, rows, cols in LAYERS:
+        layer = getattr(module, name, None)
+        if layer is None or getattr(layer, "weight", None) is None or getattr(layer, "bias", None) is None:
+            raise ValueError(f"the module has no layer {name!r} with a weight and a bias; supported: {SUPPORTED}")
+        for part, p, shape in (("weight", layer.weight, (rows, cols)), ("bias", layer.bias, (rows,))):
+            if not torch.is_tensor(p) or tuple(p.shape) != shape:
+                raise ValueError(f"{name}.{part} has shape {tuple(getattr(p, 'shape', ()))}, expected {shape}; supported: {SUPPORTED}")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError(f"{name}.{part} is {str(p.dtype).replace('torch.', '')}{'' if p.is_contiguous() else ', not contiguous'}; "
+                                 "the live tensors must be float32 and contiguous")
+            params.append(p)
+    return params
 
 
 def _np(x, what):
@@ -126,6 +146,24 @@ class FusedFNN(Handle):
     @classmethod
     def from_state_dict(cls, sd, device: int = 0):
         return cls(FNNSpec.from_state_dict(sd), device)
+
+    def bind_live(self, policy_module) -> None:
+        """Record the LIVE parameters of ``policy_module`` (the module an optimiser steps, on this device) so that refresh() can
+        carry them into this object's packed weights.  Again after anything that reallocates the parameters (``.to()``)."""
+        from .sb3_nets import check_device
+        params = live_parameters(policy_module)
+        check_device(params, self.device, "FusedFNN.bind_live")
+        self._check(self._L.meshenv_fnn_bind(self._h, self._ptrs(params)), "meshenv_fnn_bind")
+        self._live = params      # keeps the storages alive
+
+    def refresh(self) -> None:
+        """The bound parameters, as they are now, into the packed weights, in exactly the layout ``FNNSpec.packed`` builds on the
+        host: one launch on the current stream, no host copy, no synchronisation.  Launches that follow on the same stream
+        (forward, mesh_with) see the new weights."""
+        if getattr(self, "_live", None) is None:
+            raise ValueError("refresh() needs bind_live(policy) first")
+        self._bind_stream()
+        self._check(self._L.meshenv_fnn_refresh(self._h), "meshenv_fnn_refresh")
 
     def forward(self, obs, finished=None, raw: bool = False):
         """obs float32 CUDA [n, 18] (the static observation; a row of zeros is the reference's None).  Returns (points [n, 2]
