@@ -330,6 +330,23 @@ int launch(H *h, const DeviceGuard &guard, const char *fn, F &&enqueue, const ch
     return MESHENV_OK;
 }
 
+// The kernels' pointers into `buf`, from consecutive slots of the network's PackLayout (meshenv_pack.h).
+void point(const float *buf, const PackSlot *s, std::initializer_list<const float **> ptrs)
+{
+    for (const float **p : ptrs) *p = buf + (s++)->off;
+}
+
+// The launch of every *_refresh: one k_target_pack over the live tensors that the handle's *_bind put into its table by the
+// network's PackLayout, the description its buffer was packed by.
+template <typename H>
+int pack_refresh(H *h, const char *fn)
+{
+    DeviceGuard guard(h->device);
+    return launch(h, guard, fn, [&] {
+        hipLaunchKernelGGL(k_target_pack, dim3(pack_blocks(h->table, h->n_copies), h->n_copies), dim3(256), 0, h->stream, h->table);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1846,12 +1863,21 @@ struct MeshActor : HandleBase {
     bool live = false;
 };
 
+// The SAC actor's buffer, in the tensor order of meshenv_actor_bind: w1 b1 w2 b2 w3 b3, then mu at column 0 and log_std at
+// column kActOut of one head tile.
+static PackLayout actor_layout()
+{
+    PackLayout L;
+    L.tower(kActHid, 3, kActIn, kActInPad / 16, kActOut, true);
+    return L;
+}
+
 int meshenv_actor_create(int device, void *stream, MeshActor **out)
 {
     const int rc = create_handle("meshenv_actor_create", device, stream, out);
     if (rc != MESHENV_OK) return rc;
     MeshActor *a = *out;
-    a->nfloat = (size_t)kActInPad * kActHid + kActHid + 2 * ((size_t)kActHid * kActHid + kActHid) + (size_t)kActHid * 16 + 16;
+    a->nfloat = actor_layout().floats;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess || hipMalloc((void **)&a->buf, a->nfloat * sizeof(float)) != hipSuccess) {
         g_create_error = "meshenv_actor_create: hipMalloc failed";
@@ -1873,48 +1899,10 @@ int meshenv_actor_load(MeshActor *a, const float *w1, const float *b1, const flo
 {
     if (!a || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w_mu || !b_mu || !w_log_std || !b_log_std || !low || !high)
         return MESHENV_E_ARG;
-    std::vector<float> h;
-    // torch [out][in] -> the per-lane MFMA B-operand order of meshenv_actor.h: [16-neuron tile = 2 wv + tile][K/16][lane][4]
-    auto packed = [&](const float *w, int out, int in, int k_pad, int waves) {
-        const size_t off = h.size();
-        const int groups = k_pad / 16;
-        h.resize(off + (size_t)waves * 2 * groups * 64 * 4, 0.0f);
-        for (int wv = 0; wv < waves; wv++)
-            for (int tile = 0; tile < 2; tile++)
-                for (int g = 0; g < groups; g++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int j = 0; j < 4; j++) {
-                            const int k = 4 * (4 * g + j) + (lane >> 4), n = 32 * wv + 16 * tile + (lane & 15);
-                            if (k < in && n < out)
-                                h[off + ((((size_t)wv * 2 + tile) * groups + g) * 64 + lane) * 4 + j] = w[(size_t)n * in + k];
-                        }
-        return off;
-    };
-    auto plain = [&](const float *b, int n, int pad) {
-        const size_t off = h.size();
-        h.resize(off + pad, 0.0f);
-        for (int i = 0; i < n; i++) h[off + i] = b[i];
-        return off;
-    };
-    const size_t o_w1 = packed(w1, kActHid, kActIn, kActInPad, 4), o_b1 = plain(b1, kActHid, kActHid);
-    const size_t o_w2 = packed(w2, kActHid, kActHid, kActHid, 4), o_b2 = plain(b2, kActHid, kActHid);
-    const size_t o_w3 = packed(w3, kActHid, kActHid, kActHid, 4), o_b3 = plain(b3, kActHid, kActHid);
-    // heads: one 16-wide tile, columns mu0..2, log_std0..2, zeros: [8][64][4]
-    std::vector<float> wh((size_t)16 * kActHid, 0.0f);  // [n 16][k 128]
-    for (int o = 0; o < 3; o++)
-        for (int k = 0; k < kActHid; k++) {
-            wh[(size_t)o * kActHid + k] = w_mu[(size_t)o * kActHid + k];
-            wh[(size_t)(3 + o) * kActHid + k] = w_log_std[(size_t)o * kActHid + k];
-        }
-    const size_t o_wh = h.size();
-    h.resize(o_wh + (size_t)8 * 64 * 4, 0.0f);
-    for (int g = 0; g < 8; g++)
-        for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 4; j++)
-                h[o_wh + ((size_t)g * 64 + lane) * 4 + j] = wh[(size_t)(lane & 15) * kActHid + 4 * (4 * g + j) + (lane >> 4)];
-    const size_t o_bh = h.size();
-    h.resize(o_bh + 16, 0.0f);
-    for (int o = 0; o < 3; o++) { h[o_bh + o] = b_mu[o]; h[o_bh + 3 + o] = b_log_std[o]; }
+    const PackLayout L = actor_layout();
+    const float *const src[10] = {w1, b1, w2, b2, w3, b3, w_mu, b_mu, w_log_std, b_log_std};
+    std::vector<float> h(L.floats, 0.0f);
+    pack_host(L, src, h.data());
     if (h.size() > a->nfloat) {
         a->err = "meshenv_actor_load: internal size mismatch";
         return MESHENV_E_STATE;
@@ -1925,10 +1913,7 @@ int meshenv_actor_load(MeshActor *a, const float *w1, const float *b1, const flo
         a->err = "meshenv_actor_load: upload failed";
         return MESHENV_E_HIP;
     }
-    a->W.w1p = a->buf + o_w1; a->W.b1 = a->buf + o_b1;
-    a->W.w2p = a->buf + o_w2; a->W.b2 = a->buf + o_b2;
-    a->W.w3p = a->buf + o_w3; a->W.b3 = a->buf + o_b3;
-    a->W.whp = a->buf + o_wh; a->W.bh = a->buf + o_bh;
+    point(a->buf, L.s, {&a->W.w1p, &a->W.b1, &a->W.w2p, &a->W.b2, &a->W.w3p, &a->W.b3, &a->W.whp, &a->W.bh});
     for (int i = 0; i < 3; i++) { a->W.low[i] = low[i]; a->W.high[i] = high[i]; }
     a->loaded = true;
     return MESHENV_OK;
@@ -2113,6 +2098,18 @@ PolicyKernel policy_kernel(int kind, int hidden, int activation)
 const char *kPolicyShapes = "supported policies: kind 0 (actor-critic: pi and vf towers) or 1 (deterministic tanh actor), two hidden "
                             "layers of width 64, 128 or 256, activation 0 (ReLU) or 1 (Tanh), 18 inputs, 3 actions";
 
+// A policy's buffer, in the tensor order of meshenv_policy_bind: the pi tower (w1 b1 w2 b2 wh bh), the actor-critic kind's vf
+// tower, then the 16-float aux block.  Its slot, the last, is log_std or sigma; low and high follow at aux + 3 and aux + 6
+// (meshenv_policy_load).  The deterministic kind's bind stops before it.
+PackLayout policy_layout(int kind, int H)
+{
+    PackLayout L;
+    L.tower(H, 2, kObsDim, kPolInPad / 16, 3, false);
+    if (kind == kPolicyActorCritic) L.tower(H, 2, kObsDim, kPolInPad / 16, 1, false);
+    L.vector(3, 16);
+    return L;
+}
+
 // One launch of k_policy_forward.  The pi workgroups run when an action output is asked for, the vf workgroups when a value
 // (or a bootstrap terminal value) is.  Arguments are checked by the callers.
 int policy_launch(MeshPolicy *p, const char *fn, const PolicyArgs &A)
@@ -2161,43 +2158,16 @@ int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, con
         return fail(p, MESHENV_E_ARG, "meshenv_policy_load: the actor-critic kind needs the vf tower and value_net");
     if (!ac && (vf_w1 || vf_b1 || vf_w2 || vf_b2 || value_w || value_b))
         return fail(p, MESHENV_E_ARG, "meshenv_policy_load: the deterministic kind has no vf tower (pass NULL)");
-    const int H = hidden;
-    std::vector<float> h;
-    // torch [out][in] -> the per-lane MFMA B-operand order of meshenv_policy.h: [tile][K/16][lane][4]
-    auto packed = [&](const float *w, int out, int in, int k_pad, int tiles) {
-        const size_t off = h.size();
-        const int groups = k_pad / 16;
-        h.resize(off + (size_t)tiles * groups * 64 * 4, 0.0f);
-        for (int tile = 0; tile < tiles; tile++)
-            for (int g = 0; g < groups; g++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 4; j++) {
-                        const int k = 4 * (4 * g + j) + (lane >> 4), n = 16 * tile + (lane & 15);
-                        if (k < in && n < out) h[off + (((size_t)tile * groups + g) * 64 + lane) * 4 + j] = w[(size_t)n * in + k];
-                    }
-        return off;
-    };
-    auto plain = [&](const float *b, int n, int pad) {
-        const size_t off = h.size();
-        h.resize(off + pad, 0.0f);
-        for (int i = 0; i < n; i++) h[off + i] = b[i];
-        return off;
-    };
-    struct Offs { size_t w1, b1, w2, b2, wh, bh; };
-    auto tower = [&](const float *w1, const float *b1, const float *w2, const float *b2, const float *wh, const float *bh, int n_out) {
-        Offs o;
-        o.w1 = packed(w1, H, kObsDim, kPolInPad, H / 16); o.b1 = plain(b1, H, H);
-        o.w2 = packed(w2, H, H, H, H / 16); o.b2 = plain(b2, H, H);
-        o.wh = packed(wh, n_out, H, H, 1); o.bh = plain(bh, n_out, 16);
-        return o;
-    };
-    const Offs pi = tower(pi_w1, pi_b1, pi_w2, pi_b2, head_w, head_b, 3);
-    Offs vf{};
-    if (ac) vf = tower(vf_w1, vf_b1, vf_w2, vf_b2, value_w, value_b, 1);
-    const size_t o_aux = h.size();
-    h.resize(o_aux + 16, 0.0f);
+    const PackLayout L = policy_layout(kind, hidden);
+    const float *src[kPgTensors] = {pi_w1, pi_b1, pi_w2, pi_b2, head_w, head_b};
+    int n = 6;
+    if (ac)
+        for (const float *t : {vf_w1, vf_b1, vf_w2, vf_b2, value_w, value_b}) src[n++] = t;
+    src[n++] = log_std_or_sigma;   // NULL (a deterministic policy without sigma) leaves the slot zero
+    const size_t o_aux = L.s[L.n - 1].off;
+    std::vector<float> h(L.floats, 0.0f);
+    pack_host(L, src, h.data());
     for (int i = 0; i < 3; i++) {
-        h[o_aux + i] = log_std_or_sigma ? log_std_or_sigma[i] : 0.0f;
         h[o_aux + 3 + i] = low[i];
         h[o_aux + 6 + i] = high[i];
     }
@@ -2211,14 +2181,10 @@ int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, con
     if (hipMalloc((void **)&p->buf, h.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(p->buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(p, MESHENV_E_HIP, "meshenv_policy_load: upload failed");
-    auto bind = [&](PolicyTower &T, const Offs &o) {
-        T.w1p = p->buf + o.w1; T.b1 = p->buf + o.b1;
-        T.w2p = p->buf + o.w2; T.b2 = p->buf + o.b2;
-        T.whp = p->buf + o.wh; T.bh = p->buf + o.bh;
-    };
-    bind(p->W.pi, pi);
-    if (ac) bind(p->W.vf, vf);
-    else p->W.vf = p->W.pi;   // never read
+    PolicyTower &pi = p->W.pi, &vf = p->W.vf;
+    point(p->buf, L.s, {&pi.w1p, &pi.b1, &pi.w2p, &pi.b2, &pi.whp, &pi.bh});
+    if (ac) point(p->buf, L.s + 6, {&vf.w1p, &vf.b1, &vf.w2p, &vf.b2, &vf.whp, &vf.bh});
+    else vf = pi;   // never read
     p->W.aux = p->buf + o_aux;
     p->kind = kind; p->hidden = hidden; p->activation = activation;
     p->loaded = true;
@@ -2658,6 +2624,20 @@ namespace {
 const char *kTargetKinds = "supported kinds: 0 (SAC: ReLU [128, 128, 128] actor with mu / log_std heads and twin ReLU [128, 128, 128] "
                            "critics) or 1 (TD3: ReLU [256, 256] tanh actor and twin ReLU [256, 256] critics); 18 observations, 3 actions";
 
+// The target's buffer, in the tensor order of meshenv_target_bind: the towers actor (SAC: mu at column 0 and log_std at column 3
+// of its head tile), q1 and q2, each w1 b1 w2 b2 [w3 b3] wh bh, then log_ent_coef.  Its slot, the last, is there for both
+// kinds; a bind without log_ent_coef stops before it.
+PackLayout target_layout(int kind)
+{
+    const bool sac = kind == kTargetSAC;
+    const int H = sac ? 128 : 256, NL = sac ? 3 : 2;
+    PackLayout L;
+    L.tower(H, NL, kObsDim, kPolInPad / 16, 3, sac);
+    for (int q = 0; q < 2; q++) L.tower(H, NL, kTgtIn, kPolInPad / 16, 1, false);
+    L.vector(1, 4);
+    return L;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2689,7 +2669,7 @@ int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_acto
 {
     if (!t) return MESHENV_E_ARG;
     const bool sac = t->kind == kTargetSAC;
-    const int H = sac ? 128 : 256, NL = sac ? 3 : 2, G = H / 16;
+    const int NL = sac ? 3 : 2;
     const int want_actor = 2 * NL + (sac ? 4 : 2), want_critic = 2 * NL + 2;
     if (!actor_dev || !q1_dev || !q2_dev || n_actor != want_actor || n_critic != want_critic)
         return fail(t, MESHENV_E_ARG, "meshenv_target_bind: kind " + std::to_string(t->kind) + " takes " +
@@ -2701,45 +2681,24 @@ int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_acto
     if (!sac && log_ent_coef_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: TD3 has no entropy coefficient (pass NULL)");
     DeviceGuard guard(t->device);
     if (guard.err != hipSuccess) return fail(t, MESHENV_E_HIP, "meshenv_target_bind: hipSetDevice failed");
-    // layout of the buffer: per tower w1p b1 w2p b2 [w3p b3] whp bh, then log_ent_coef
-    const size_t tower_floats = (size_t)G * 2 * 256 + H + (size_t)(NL - 1) * ((size_t)G * G * 256 + H) + (size_t)G * 256 + 16;
-    const size_t total = 3 * tower_floats + 4;
-    if (!zeroed_once(t, &t->buf, total)) return fail(t, MESHENV_E_HIP, "meshenv_target_bind: allocation failed");
-    t->n_copies = 0;
-    auto add = [&](const float *src, float *dst, int out, int in, int groups, int tiles, int n_off, int kind) {
-        PackCopy &c = t->table.c[t->n_copies++];
-        c.src = src; c.dst = dst; c.out = out; c.in = in; c.groups = groups; c.tiles = tiles; c.n_off = n_off; c.kind = kind;
-    };
-    auto tower = [&](TargetTower &T, float *base, const float *const *p, int in1, bool actor) {
-        float *at = base;
-        int i = 0;
-        T.w1p = at; add(p[i++], at, H, in1, 2, G, 0, kPackMatrix); at += (size_t)G * 2 * 256;
-        T.b1 = at; add(p[i++], at, H, 0, 0, 0, 0, kPackVector); at += H;
-        T.w2p = at; add(p[i++], at, H, H, G, G, 0, kPackMatrix); at += (size_t)G * G * 256;
-        T.b2 = at; add(p[i++], at, H, 0, 0, 0, 0, kPackVector); at += H;
-        T.w3p = T.b3 = nullptr;
-        if (NL == 3) {
-            T.w3p = at; add(p[i++], at, H, H, G, G, 0, kPackMatrix); at += (size_t)G * G * 256;
-            T.b3 = at; add(p[i++], at, H, 0, 0, 0, 0, kPackVector); at += H;
-        }
-        float *wh = at, *bh = at + (size_t)G * 256;
-        T.whp = wh; T.bh = bh;
-        const int n_out = actor ? 3 : 1;
-        add(p[i], wh, n_out, H, G, 1, 0, kPackMatrix); add(p[i + 1], bh, n_out, 0, 0, 0, 0, kPackVector);
-        if (actor && sac) {   // log_std head: columns 3..5 of the same tile
-            add(p[i + 2], wh, 3, H, G, 1, 3, kPackMatrix); add(p[i + 3], bh, 3, 0, 0, 0, 3, kPackVector);
-        }
-    };
-    tower(t->W.actor, t->buf, actor_dev, kObsDim, true);
-    tower(t->W.q1, t->buf + tower_floats, q1_dev, kTgtIn, false);
-    tower(t->W.q2, t->buf + 2 * tower_floats, q2_dev, kTgtIn, false);
-    t->W.log_ent_coef = nullptr;
-    if (log_ent_coef_dev) {
-        float *dst = t->buf + 3 * tower_floats;
-        add(log_ent_coef_dev, dst, 1, 0, 0, 0, 0, kPackVector);
-        t->W.log_ent_coef = dst;
-    }
+    const PackLayout L = target_layout(t->kind);
     static_assert(10 + 2 * 8 + 1 <= kTgtMaxCopies, "the copy table holds SAC's 27 sources");
+    if (!zeroed_once(t, &t->buf, L.floats)) return fail(t, MESHENV_E_HIP, "meshenv_target_bind: allocation failed");
+    const float *src[kTgtMaxCopies];
+    int n = 0;
+    for (int i = 0; i < n_actor; i++) src[n++] = actor_dev[i];
+    for (int i = 0; i < n_critic; i++) src[n++] = q1_dev[i];
+    for (int i = 0; i < n_critic; i++) src[n++] = q2_dev[i];
+    if (log_ent_coef_dev) src[n++] = log_ent_coef_dev;
+    t->n_copies = pack_table(L, src, n, t->buf, t->table);
+    int at = 0;
+    for (TargetTower *T : {&t->W.actor, &t->W.q1, &t->W.q2}) {
+        T->w3p = T->b3 = nullptr;
+        if (NL == 3) point(t->buf, L.s + at, {&T->w1p, &T->b1, &T->w2p, &T->b2, &T->w3p, &T->b3, &T->whp, &T->bh});
+        else point(t->buf, L.s + at, {&T->w1p, &T->b1, &T->w2p, &T->b2, &T->whp, &T->bh});
+        at += T == &t->W.actor ? want_actor : want_critic;
+    }
+    t->W.log_ent_coef = log_ent_coef_dev ? t->buf + L.s[at].off : nullptr;
     t->bound = true;
     t->packed = false;
     return MESHENV_OK;
@@ -2749,12 +2708,7 @@ int meshenv_target_refresh(MeshTarget *t)
 {
     if (!t) return MESHENV_E_ARG;
     if (!t->bound) return fail(t, MESHENV_E_STATE, "meshenv_target_refresh: no tensors bound (meshenv_target_bind)");
-    // the largest copy is an H x H matrix: H * H / 256 blocks cover it in one pass
-    const int H = t->kind == kTargetSAC ? 128 : 256;
-    DeviceGuard guard(t->device);
-    const int rc = launch(t, guard, "meshenv_target_refresh", [&] {
-        hipLaunchKernelGGL(k_target_pack, dim3(H * H / 256, t->n_copies), dim3(256), 0, t->stream, t->table);
-    });
+    const int rc = pack_refresh(t, "meshenv_target_refresh");
     if (rc == MESHENV_OK) t->packed = true;
     return rc;
 }
@@ -3284,23 +3238,8 @@ int meshenv_policy_bind(MeshPolicy *p, const float *const *tensors_dev, int n_te
                        std::to_string(want) + " tensors (pi w1 b1 w2 b2 wh bh" + (ac ? ", vf likewise, log_std)" : ")"));
     for (int i = 0; i < want; i++)
         if (!tensors_dev[i]) return fail(p, MESHENV_E_ARG, "meshenv_policy_bind: null tensor");
-    const int H = p->hidden, G = H / 16;
-    p->n_copies = 0;
-    auto add = [&](const float *src, const float *dst, int out, int in, int groups, int tiles, int kind) {
-        PackCopy &c = p->table.c[p->n_copies++];
-        c.src = src; c.dst = const_cast<float *>(dst); c.out = out; c.in = in; c.groups = groups; c.tiles = tiles; c.n_off = 0; c.kind = kind;
-    };
-    auto tower = [&](const PolicyTower &T, const float *const *t, int n_out) {
-        add(t[0], T.w1p, H, kObsDim, kPolInPad / 16, G, kPackMatrix); add(t[1], T.b1, H, 0, 0, 0, kPackVector);
-        add(t[2], T.w2p, H, H, G, G, kPackMatrix); add(t[3], T.b2, H, 0, 0, 0, kPackVector);
-        add(t[4], T.whp, n_out, H, G, 1, kPackMatrix); add(t[5], T.bh, n_out, 0, 0, 0, kPackVector);
-    };
-    tower(p->W.pi, tensors_dev, 3);
-    if (ac) {
-        tower(p->W.vf, tensors_dev + 6, 1);
-        add(tensors_dev[12], p->W.aux, 3, 0, 0, 0, kPackVector);
-    }
     static_assert(kPgTensors <= kTgtMaxCopies, "the copy table holds the 13 sources");
+    p->n_copies = pack_table(policy_layout(p->kind, p->hidden), tensors_dev, want, p->buf, p->table);
     p->live = true;
     return MESHENV_OK;
 }
@@ -3309,13 +3248,7 @@ int meshenv_policy_refresh(MeshPolicy *p)
 {
     if (!p) return MESHENV_E_ARG;
     if (!p->loaded || !p->live) return fail(p, MESHENV_E_STATE, "meshenv_policy_refresh: no tensors bound (meshenv_policy_bind)");
-    const int H = p->hidden;   // the largest copy is an H x H matrix: H * H / 256 blocks cover it in one pass
-    DeviceGuard guard(p->device);
-    // k_target_pack (meshenv_target.h) is the pack kernel: the table of meshenv_policy_bind has every n_off = 0, and what it
-    // does not write (the padding of K and of the head tile) meshenv_policy_load left zero
-    return launch(p, guard, "meshenv_policy_refresh", [&] {
-        hipLaunchKernelGGL(k_target_pack, dim3(H * H / 256, p->n_copies), dim3(256), 0, p->stream, p->table);
-    });
+    return pack_refresh(p, "meshenv_policy_refresh");
 }
 
 }  // extern "C"
@@ -4040,21 +3973,7 @@ int meshenv_actor_bind(MeshActor *a, const float *const *tensors_dev, int n)
         return fail(a, MESHENV_E_ARG, "meshenv_actor_bind: the SAC actor takes 10 tensors (w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w log_std_b)");
     for (int i = 0; i < n; i++)
         if (!tensors_dev[i]) return fail(a, MESHENV_E_ARG, "meshenv_actor_bind: null tensor");
-    constexpr int H = kActHid, G = kActHid / 16;
-    a->n_copies = 0;
-    auto add = [&](const float *src, const float *dst, int out, int in, int groups, int tiles, int n_off, int kind) {
-        PackCopy &c = a->table.c[a->n_copies++];
-        c.src = src; c.dst = const_cast<float *>(dst); c.out = out; c.in = in; c.groups = groups; c.tiles = tiles; c.n_off = n_off; c.kind = kind;
-    };
-    const float *const *t = tensors_dev;
-    // the layout of meshenv_actor_load: [tile 8][K / 16][lane 64][4] per hidden layer, one 16-wide head tile (mu at column 0,
-    // log_std at column 3), which is what k_target_pack writes
-    add(t[0], a->W.w1p, H, kActIn, kActInPad / 16, G, 0, kPackMatrix); add(t[1], a->W.b1, H, 0, 0, 0, 0, kPackVector);
-    add(t[2], a->W.w2p, H, H, G, G, 0, kPackMatrix); add(t[3], a->W.b2, H, 0, 0, 0, 0, kPackVector);
-    add(t[4], a->W.w3p, H, H, G, G, 0, kPackMatrix); add(t[5], a->W.b3, H, 0, 0, 0, 0, kPackVector);
-    add(t[6], a->W.whp, kActOut, H, G, 1, 0, kPackMatrix); add(t[7], a->W.bh, kActOut, 0, 0, 0, 0, kPackVector);
-    add(t[8], a->W.whp, kActOut, H, G, 1, kActOut, kPackMatrix); add(t[9], a->W.bh, kActOut, 0, 0, 0, kActOut, kPackVector);
-    static_assert(10 <= kTgtMaxCopies, "the copy table holds the 10 sources");
+    a->n_copies = pack_table(actor_layout(), tensors_dev, n, a->buf, a->table);
     a->live = true;
     return MESHENV_OK;
 }
@@ -4063,11 +3982,7 @@ int meshenv_actor_refresh(MeshActor *a)
 {
     if (!a) return MESHENV_E_ARG;
     if (!a->loaded || !a->live) return fail(a, MESHENV_E_STATE, "meshenv_actor_refresh: no tensors bound (meshenv_actor_bind)");
-    DeviceGuard guard(a->device);
-    // the largest copy is a 128 x 128 matrix: 64 blocks of 256 threads cover it in one pass
-    return launch(a, guard, "meshenv_actor_refresh", [&] {
-        hipLaunchKernelGGL(k_target_pack, dim3(kActHid * kActHid / 256, a->n_copies), dim3(256), 0, a->stream, a->table);
-    });
+    return pack_refresh(a, "meshenv_actor_refresh");
 }
 
 const char *meshenv_actor_last_error(const MeshActor *a) { return last_error(a); }
@@ -4302,6 +4217,20 @@ const char *kFnnShapes = "supported network: fc1 [64][18], fc2 [128][64], fc3 [6
 // rows of the seven layers, in MESHENV_FNN_TENSORS' order; the two heads are layer 5's rows 0-1 and 2-4
 const int kFnnRows[7] = {64, 128, 64, 32, 16, kFnnAction, kFnnTypes};
 
+// The FNN's buffer (MESHENV_FNN_PACKED_FLOATS), in MESHENV_FNN_TENSORS' order: layer l's weight tiles at fnn_w_offset(l), its bias
+// behind them; the type_head sits behind the action_head in layer 5's tile.
+PackLayout fnn_layout()
+{
+    PackLayout L;
+    for (int i = 0; i < 7; i++) {
+        const int l = i < 5 ? i : 5, row0 = i == 6 ? kFnnAction : 0;
+        L.add(fnn_w_offset(l), kFnnRows[i], fnn_in(l), fnn_k(l) / 16, fnn_tiles(l), row0, kPackMatrix);
+        L.add(fnn_b_offset(l), kFnnRows[i], 0, 0, 0, row0, kPackVector);
+    }
+    L.floats = kFnnPackedFloats;
+    return L;
+}
+
 std::string fnn_pack(const float *const *tensors, const int32_t *shapes, float *out)
 {
     if (!tensors || !shapes || !out) return "null pointer";
@@ -4314,23 +4243,7 @@ std::string fnn_pack(const float *const *tensors, const int32_t *shapes, float *
                    std::to_string(sb[0]) + "]; " + kFnnShapes;
     }
     std::memset(out, 0, sizeof(float) * (size_t)kFnnPackedFloats);
-    // torch [out][in] -> the per-lane MFMA B-operand order of meshenv_policy.h: [tile][K/16][lane][4]; `row0`: the tensor's first
-    // row in the layer's tiles (the type_head behind the action_head)
-    auto packed = [&](const float *w, const float *b, int l, int rows, int row0) {
-        const int in = fnn_in(l), groups = fnn_k(l) / 16;
-        float *wp = out + fnn_w_offset(l), *bp = out + fnn_b_offset(l);
-        for (int tile = 0; tile < fnn_tiles(l); tile++)
-            for (int g = 0; g < groups; g++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 4; j++) {
-                        const int k = 4 * (4 * g + j) + (lane >> 4), n = 16 * tile + (lane & 15) - row0;
-                        if (k < in && n >= 0 && n < rows) wp[(((size_t)tile * groups + g) * 64 + lane) * 4 + j] = w[(size_t)n * in + k];
-                    }
-        for (int n = 0; n < rows; n++) bp[row0 + n] = b[n];
-    };
-    for (int l = 0; l < 5; l++) packed(tensors[2 * l], tensors[2 * l + 1], l, kFnnRows[l], 0);
-    packed(tensors[10], tensors[11], 5, kFnnAction, 0);
-    packed(tensors[12], tensors[13], 5, kFnnTypes, kFnnAction);
+    pack_host(fnn_layout(), tensors, out);
     return std::string();
 }
 
@@ -4549,19 +4462,7 @@ int meshenv_fnn_bind(MeshFnn *f, const float *const *tensors_dev)
     if (!tensors_dev) return fail(f, MESHENV_E_ARG, std::string("meshenv_fnn_bind: takes 14 tensors; ") + kFnnShapes);
     for (int i = 0; i < MESHENV_FNN_TENSORS; i++)
         if (!tensors_dev[i]) return fail(f, MESHENV_E_ARG, "meshenv_fnn_bind: null tensor");
-    f->n_copies = 0;
-    // fnn_pack's layout: layer l's weight tiles at fnn_w_offset(l), its bias behind them; `row0`: the tensor's first row in
-    // the layer's tiles (the type_head behind the action_head)
-    auto add = [&](const float *w, const float *b, int l, int rows, int row0) {
-        PackCopy &cw = f->table.c[f->n_copies++];
-        cw.src = w; cw.dst = f->buf + fnn_w_offset(l); cw.out = rows; cw.in = fnn_in(l); cw.groups = fnn_k(l) / 16; cw.tiles = fnn_tiles(l);
-        cw.n_off = row0; cw.kind = kPackMatrix;
-        PackCopy &cb = f->table.c[f->n_copies++];
-        cb.src = b; cb.dst = f->buf + fnn_b_offset(l); cb.out = rows; cb.in = 0; cb.groups = 0; cb.tiles = 0; cb.n_off = row0; cb.kind = kPackVector;
-    };
-    for (int l = 0; l < 5; l++) add(tensors_dev[2 * l], tensors_dev[2 * l + 1], l, kFnnRows[l], 0);
-    add(tensors_dev[10], tensors_dev[11], 5, kFnnAction, 0);
-    add(tensors_dev[12], tensors_dev[13], 5, kFnnTypes, kFnnAction);
+    f->n_copies = pack_table(fnn_layout(), tensors_dev, MESHENV_FNN_TENSORS, f->buf, f->table);
     f->live = true;
     return MESHENV_OK;
 }
@@ -4570,12 +4471,7 @@ int meshenv_fnn_refresh(MeshFnn *f)
 {
     if (!f) return MESHENV_E_ARG;
     if (!f->loaded || !f->live) return fail(f, MESHENV_E_STATE, "meshenv_fnn_refresh: no tensors bound (meshenv_fnn_bind)");
-    DeviceGuard guard(f->device);
-    // k_target_pack (meshenv_target.h) is the pack kernel; what it does not write (the padding of K and of the head tile)
-    // meshenv_fnn_load left zero.  The largest copies (fc2, fc3) have 32 groups of 256 floats: 32 blocks cover them in one pass.
-    return launch(f, guard, "meshenv_fnn_refresh", [&] {
-        hipLaunchKernelGGL(k_target_pack, dim3(32, f->n_copies), dim3(256), 0, f->stream, f->table);
-    });
+    return pack_refresh(f, "meshenv_fnn_refresh");
 }
 
 }  // extern "C"

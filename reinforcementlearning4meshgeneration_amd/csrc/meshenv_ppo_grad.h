@@ -10,7 +10,7 @@
 //
 // for the actor-critic MLP policies the reference trains with: rl/baselines/RL_Mesh.py:113-177, PPO ReLU [128, 128] x 2, and
 // SB3's default A2C Tanh [64, 64]).  (The live tensors reach a loaded FusedPolicy's packed buffer through k_target_pack of
-// meshenv_target.h: meshenv_policy_bind fills its PackTable, meshenv_policy_refresh launches it.)
+// meshenv_pack.h: meshenv_policy_bind fills its PackTable, meshenv_policy_refresh launches it.)
 // At most four launches: k_ppo_adv_stats (when normalising), k_ppo_grad<H, ACT>, k_ppo_grad_reduce, k_ppo_grad_clip (with a
 // max_grad_norm).
 //

@@ -22,11 +22,11 @@
 // lo, counter hi, 2).  Tag 2 is this kernel's own: the rollout noise (meshenv_actor.h) uses 0, the replay draw
 // (meshenv_replay.h) 1, so the same (seed, counter) given to all three does not reuse a stream.
 //
-// k_target_pack: the weights come from LIVE device tensors in torch.nn.Linear layout ([out][in] row-major, [out] bias).  One
-// launch copies all of them (and log_ent_coef) into the handle's buffer in the kernel's layout; the table of copies is the
-// kernel's argument.  blockIdx.y selects the copy.
+// k_target_pack (meshenv_pack.h): the weights come from LIVE device tensors in torch.nn.Linear layout.  One launch copies all
+// of them (and log_ent_coef) into the handle's buffer in the kernel's layout.
 #pragma once
 
+#include "meshenv_pack.h"
 #include "meshenv_policy.h"
 
 namespace meshenv {
@@ -183,42 +183,6 @@ k_td_target(TargetWeights W, TargetArgs A)
         float nq = fminf(qa[reg], qb[reg]);
         if (KIND == kTargetSAC) nq = nq - ent * lp[reg];
         A.target[r] = A.rewards[r] + ((1.0f - A.dones[r]) * A.gamma) * nq;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ weights from live tensors
-enum { kPackMatrix = 0, kPackVector = 1 };
-constexpr int kTgtMaxCopies = 32;
-
-struct PackCopy {
-    const float *src;  // [out][in] row-major (matrix) or [out] (vector)
-    float *dst;        // packed [tiles][groups][64][4] (element j of lane l in group g = W[n = 16 tile + (l & 15) - n_off][k = 4 (4 g + j) + (l >> 4)]) or a plain vector
-    int out, in, groups, tiles;
-    int n_off;         // first neuron (matrix) / first element (vector) of dst this source occupies
-    int kind;
-};
-
-struct PackTable {
-    PackCopy c[kTgtMaxCopies];
-};
-
-// Elements of dst outside the source (k >= in, neurons of another source or of the padding) are not written: the buffer is
-// zeroed once when it is allocated.
-__global__ void __launch_bounds__(256)
-k_target_pack(PackTable P)
-{
-    const PackCopy &c = P.c[blockIdx.y];
-    const int stride = gridDim.x * 256, i0 = blockIdx.x * 256 + threadIdx.x;
-    if (c.kind == kPackVector) {
-        for (int i = i0; i < c.out; i += stride) c.dst[c.n_off + i] = c.src[i];
-        return;
-    }
-    const int total = c.tiles * c.groups * 256;
-    for (int i = i0; i < total; i += stride) {
-        const int j = i & 3, lane = (i >> 2) & 63, tg = i >> 8;
-        const int g = tg % c.groups, tile = tg / c.groups;
-        const int k = 4 * (4 * g + j) + (lane >> 4), n = 16 * tile + (lane & 15) - c.n_off;
-        if (k < c.in && n >= 0 && n < c.out) c.dst[i] = c.src[(size_t)n * c.in + k];
     }
 }
 
