@@ -13,7 +13,7 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
            "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback", "FusedOnPolicyLearn",
            "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter", "FusedFNN", "FNNSpec", "FNNMeshResult",
-           "FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog"]
+           "FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog", "DeviceMeshAugmentation", "AugmentScore"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -80,6 +80,9 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog"):
         from . import fnn_train
         return getattr(fnn_train, name)
+    if name in ("DeviceMeshAugmentation", "AugmentScore"):
+        from . import augmentation
+        return getattr(augmentation, name)
     if name == "DeviceEvalCallback":
         from .eval_callback import DeviceEvalCallback
         return DeviceEvalCallback

@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h, meshenv_augment.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -163,6 +163,14 @@ EXPORTS_FNN_TRAIN = [
 ]
 FNN_GRAD_FLOATS, FNN_GRAD_OUTPUTS, FNN_GRAD_MAX_GROUPS = 20544, 4, 128
 
+# every symbol include/meshenv_augment.h declares: the synthetic training samples of the supervised network (MeshAugmentation.sampling)
+EXPORTS_AUGMENT = [
+    "meshenv_augment_create", "meshenv_augment_destroy", "meshenv_augment_set_stream", "meshenv_augment_last_error",
+    "meshenv_augment_score", "meshenv_augment_propose", "meshenv_augment_sample",
+]
+AUGMENT_PHILOX_TAG, AUGMENT_BINS, AUGMENT_TYPES, AUGMENT_MAX_ACTIONS, AUGMENT_UNIFORMS = 5, 11, 3, 20, 57
+AUGMENT_MAX_POOL, AUGMENT_MAX_ROUND, AUGMENT_MAX_ROUNDS, AUGMENT_STATS = 1024, 2 ** 20, 4095, 4
+
 
 class MeshKeepEntry(C.Structure):
     """include/meshenv_eval_callback.h MeshKeepEntry: one tensor of a meshenv_keep_best call."""
@@ -282,7 +290,8 @@ def load():
                                           ("meshenv_onpolicy_train", [], True), ("meshenv_onpolicy_learn", [], True),
                                           ("meshenv_offpolicy_train", [], True),
                                           ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True),
-                                          ("meshenv_fnn", [], True), ("meshenv_fnn_grad", [], True)):
+                                          ("meshenv_fnn", [], True), ("meshenv_fnn_grad", [], True),
+                                          ("meshenv_augment", [], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -358,6 +367,10 @@ def load():
     L.meshenv_fnn_grad_backward.argtypes = [vp, C.c_int, C.c_int] + [vp] * 5
     L.meshenv_fnn_bind.argtypes = [vp, C.POINTER(vp)]
     L.meshenv_fnn_refresh.argtypes = [vp]
+    L.meshenv_augment_score.argtypes = [vp, C.c_int, vp, vp, C.c_double, vp, vp, vp, vp]
+    L.meshenv_augment_propose.argtypes = [vp, C.c_int] + [vp] * 9
+    L.meshenv_augment_sample.argtypes = [vp, C.c_int64, C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.meshenv_augment_score.restype = L.meshenv_augment_propose.restype = L.meshenv_augment_sample.restype = C.c_int
     for name in ("meshenv_fnn_pack", "meshenv_fnn_load", "meshenv_fnn_forward", "meshenv_move_fnn_multi", "meshenv_fnn_grad_bind",
                  "meshenv_fnn_grad_backward", "meshenv_fnn_bind", "meshenv_fnn_refresh"):
         getattr(L, name).restype = C.c_int

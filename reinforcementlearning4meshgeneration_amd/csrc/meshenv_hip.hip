@@ -16,6 +16,7 @@
 #include "../../include/meshenv_topology.h"
 #include "../../include/meshenv_fnn.h"
 #include "../../include/meshenv_fnn_train.h"
+#include "../../include/meshenv_augment.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -53,6 +54,7 @@
 #include "meshenv_topology.h"
 #include "meshenv_fnn.h"
 #include "meshenv_fnn_grad.h"
+#include "meshenv_augment.h"
 
 using namespace meshenv;
 
@@ -4472,6 +4474,238 @@ int meshenv_fnn_refresh(MeshFnn *f)
     if (!f) return MESHENV_E_ARG;
     if (!f->loaded || !f->live) return fail(f, MESHENV_E_STATE, "meshenv_fnn_refresh: no tensors bound (meshenv_fnn_bind)");
     return pack_refresh(f, "meshenv_fnn_refresh");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ synthetic training samples
+static_assert(MESHENV_AUGMENT_PHILOX_TAG == kAugPhiloxTag && MESHENV_AUGMENT_BINS == kAugBins && MESHENV_AUGMENT_TYPES == kAugTypes &&
+                  MESHENV_AUGMENT_MAX_ACTIONS == kAugMaxActions && MESHENV_AUGMENT_UNIFORMS == kAugMaxUniforms &&
+                  (uint64_t)MESHENV_AUGMENT_MAX_ROUNDS * MESHENV_AUGMENT_MAX_ROUND < ((uint64_t)1 << 32),
+              "include/meshenv_augment.h and csrc/meshenv_augment.h disagree");
+
+struct MeshAugment : HandleBase {
+    char *buf = nullptr;   // the per-bin tables, then flag / surv / acc of one round
+    size_t cap = 0;
+};
+
+namespace {
+
+size_t aug_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// rows a bin of type t owes: Q - 1 with Q = ceil(frac_t * (n / pool) / 11), data_augmentation.py:116, :137-139, :276-278, :963
+int64_t aug_rows_per_bin(int64_t n, int pool, int t)
+{
+    const double per_worker = (double)n / (double)pool;
+    const double q = std::ceil((t == 0 ? 0.5 : 0.25) * per_worker / 11);
+    return q >= 1.0 ? (int64_t)q - 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meshenv_augment_create(int device, void *stream, MeshAugment **out)
+{
+    const int rc = create_handle("meshenv_augment_create", device, stream, out);
+    if (rc != MESHENV_OK) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess || upload_atan_state() != hipSuccess) {  // the tie-breaker of every quantised angle (atan2_x_nc)
+        delete *out;
+        *out = nullptr;
+        g_create_error = "meshenv_augment_create: the atan2 state could not be uploaded";
+        return MESHENV_E_HIP;
+    }
+    return MESHENV_OK;
+}
+
+void meshenv_augment_destroy(MeshAugment *a) { destroy_handle(a, a ? a->buf : nullptr); }
+
+const char *meshenv_augment_last_error(const MeshAugment *a) { return last_error(a); }
+
+int meshenv_augment_set_stream(MeshAugment *a, void *stream) { return set_stream(a, stream); }
+
+int meshenv_augment_score(MeshAugment *a, int n, const double *obs_dev, const double *act_dev, double threshold,
+                          uint8_t *rejected_dev, uint8_t *valid_dev, double *q_dev, uint8_t *accept_dev)
+{
+    if (!a) return MESHENV_E_ARG;
+    const char *fn = "meshenv_augment_score";
+    if (n < 0 || n > (1 << 24) || !obs_dev || !act_dev || !rejected_dev || !valid_dev || !q_dev)
+        return fail(a, MESHENV_E_ARG, std::string(fn) + ": 0 <= n <= 2^24, and obs, act, rejected, valid and q are required");
+    if (accept_dev && !(threshold > 0.0 && threshold <= 1.0))
+        return fail(a, MESHENV_E_ARG, std::string(fn) + ": threshold outside (0, 1]");
+    if (n == 0) return MESHENV_OK;
+    DeviceGuard guard(a->device);
+    return launch(a, guard, fn, [&] {
+        hipLaunchKernelGGL(k_aug_score_rows, dim3((n + kAugThreads - 1) / kAugThreads), dim3(kAugThreads), 0, a->stream, n, obs_dev,
+                           act_dev, threshold, rejected_dev, valid_dev, q_dev, accept_dev);
+    });
+}
+
+int meshenv_augment_propose(MeshAugment *a, int n, const double *uniforms_dev, const int32_t *t_dev, const int32_t *b_dev,
+                            const int32_t *t_host, const int32_t *b_host, double *angle_dev, double *obs_dev, double *act_dev,
+                            uint8_t *rejected_dev)
+{
+    if (!a) return MESHENV_E_ARG;
+    const char *fn = "meshenv_augment_propose";
+    if (n < 0 || n > (1 << 24) || !uniforms_dev || !t_dev || !b_dev || !t_host || !b_host || !angle_dev || !obs_dev || !act_dev ||
+        !rejected_dev)
+        return fail(a, MESHENV_E_ARG, std::string(fn) + ": 0 <= n <= 2^24 and every pointer is required");
+    for (int i = 0; i < n; i++)
+        if (t_host[i] < 0 || t_host[i] >= kAugTypes || b_host[i] < 0 || b_host[i] >= kAugBins)
+            return fail(a, MESHENV_E_ARG, std::string(fn) + ": row " + std::to_string(i) + ": type index outside 0..2 or bin outside 0..10");
+    if (n == 0) return MESHENV_OK;
+    DeviceGuard guard(a->device);
+    return launch(a, guard, fn, [&] {
+        hipLaunchKernelGGL(k_aug_propose_recorded, dim3((n + kAugThreads - 1) / kAugThreads), dim3(kAugThreads), 0, a->stream, n,
+                           uniforms_dev, t_dev, b_dev, angle_dev, obs_dev, act_dev, rejected_dev);
+    });
+}
+
+int meshenv_augment_sample(MeshAugment *a, int64_t n, double threshold, uint64_t seed, int pool, int round_size, int max_rounds,
+                           int64_t rows, double *x64_dev, double *y64_dev, float *x32_dev, float *y32_dev, int32_t *counts_host,
+                           uint64_t *stats_host)
+{
+    if (!a) return MESHENV_E_ARG;
+    const std::string fn = "meshenv_augment_sample";
+    if (n < 0 || n > ((int64_t)1 << 40) || pool < 1 || pool > MESHENV_AUGMENT_MAX_POOL)
+        return fail(a, MESHENV_E_ARG, fn + ": 0 <= n <= 2^40 and 1 <= pool <= 1024");
+    if (!(threshold > 0.0 && threshold <= 1.0)) return fail(a, MESHENV_E_ARG, fn + ": threshold outside (0, 1]");
+    if (round_size < 64 || round_size > MESHENV_AUGMENT_MAX_ROUND || round_size % 64 || max_rounds < 1 || max_rounds > MESHENV_AUGMENT_MAX_ROUNDS)
+        return fail(a, MESHENV_E_ARG, fn + ": 64 <= round_size <= 2^20 in multiples of 64, 1 <= max_rounds <= 4095");
+    if ((!x64_dev) != (!y64_dev) || (!x32_dev) != (!y32_dev) || (!x64_dev && !x32_dev))
+        return fail(a, MESHENV_E_ARG, fn + ": x and y come in pairs, and the float64 or the float32 pair is required");
+    const int G = pool * kAugTypes * kAugBins;
+    std::vector<int32_t> owed(G);
+    std::vector<int64_t> row0(G);
+    int64_t total = 0, acc_cap = 0;
+    for (int g = 0; g < G; g++) {
+        const int t = (g / kAugBins) % kAugTypes;
+        const int64_t r = aug_rows_per_bin(n, pool, t);
+        if (r > INT32_MAX || total + r > ((int64_t)1 << 40)) return fail(a, MESHENV_E_ARG, fn + ": too many rows");
+        owed[g] = (int32_t)r;
+        row0[g] = total;
+        total += r;
+        acc_cap += (int64_t)round_size * (t == 0 ? kAugMaxActions : 1);
+    }
+    if (rows != total)
+        return fail(a, MESHENV_E_ARG, fn + ": these arguments give " + std::to_string((long long)total) + " rows, the buffers have " +
+                       std::to_string((long long)rows));
+    if (stats_host) std::memset(stats_host, 0, sizeof(uint64_t) * MESHENV_AUGMENT_STATS);
+    if (counts_host) std::memset(counts_host, 0, sizeof(int32_t) * (size_t)G);
+    if (total == 0) return MESHENV_OK;
+
+    // one allocation: rows, row0 | count, next_p, n_surv, tally | active, acc_at of the round | flag, surv, acc of the round.
+    // A round has lanes = G * round_size proposals and acc_cap candidates, however many bins share them.
+    const int64_t lanes = (int64_t)G * round_size;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = aug_align(at + bytes); return o; };
+    const size_t o_rows = take(sizeof(int32_t) * G), o_row0 = take(sizeof(int64_t) * G);
+    const size_t tables_end = at;
+    const size_t o_count = take(sizeof(int32_t) * G), o_next = take(sizeof(uint32_t) * G), o_nsurv = take(sizeof(int32_t) * G);
+    const size_t o_tally = take(sizeof(unsigned long long) * 2 * G);
+    const size_t zero_end = at;
+    const size_t o_active = take(sizeof(int32_t) * G), o_acc_at = take(sizeof(int64_t) * ((size_t)G + 1));
+    const size_t o_flag = take((size_t)lanes), o_surv = take(sizeof(int32_t) * (size_t)lanes);
+    const size_t o_acc = take((size_t)acc_cap);
+    if (at > ((size_t)8 << 30)) return fail(a, MESHENV_E_ARG, fn + ": pool * round_size needs more than 8 GiB of scratch");
+    DeviceGuard guard(a->device);
+    if (guard.err != hipSuccess) return fail(a, MESHENV_E_HIP, fn + ": hipSetDevice failed");
+    if (at > a->cap) {
+        if (hipStreamSynchronize(a->stream) != hipSuccess) return fail(a, MESHENV_E_HIP, fn + ": hipStreamSynchronize failed");
+        if (a->buf) (void)hipFree(a->buf);
+        a->buf = nullptr;
+        a->cap = 0;
+        if (hipMalloc((void **)&a->buf, at) != hipSuccess) return fail(a, MESHENV_E_HIP, fn + ": allocation failed");
+        a->cap = at;
+    }
+    std::vector<char> tables(tables_end);
+    std::memcpy(tables.data() + o_rows, owed.data(), sizeof(int32_t) * G);
+    std::memcpy(tables.data() + o_row0, row0.data(), sizeof(int64_t) * G);
+    if (hipMemcpyAsync(a->buf, tables.data(), tables_end, hipMemcpyHostToDevice, a->stream) != hipSuccess ||
+        hipMemsetAsync(a->buf + tables_end, 0, zero_end - tables_end, a->stream) != hipSuccess ||
+        hipStreamSynchronize(a->stream) != hipSuccess)
+        return fail(a, MESHENV_E_HIP, fn + ": upload failed");
+
+    AugRound A{};
+    A.seed = seed;
+    A.threshold = threshold;
+    A.rows = (const int32_t *)(a->buf + o_rows);
+    A.row0 = (const int64_t *)(a->buf + o_row0);
+    A.count = (int32_t *)(a->buf + o_count);
+    A.next_p = (uint32_t *)(a->buf + o_next);
+    A.n_surv = (int32_t *)(a->buf + o_nsurv);
+    A.tally = (unsigned long long *)(a->buf + o_tally);
+    A.active = (const int32_t *)(a->buf + o_active);
+    A.acc_at = (const int64_t *)(a->buf + o_acc_at);
+    A.flag = (uint8_t *)(a->buf + o_flag);
+    A.surv = (int32_t *)(a->buf + o_surv);
+    A.acc = (uint8_t *)(a->buf + o_acc);
+    A.x64 = x64_dev; A.y64 = y64_dev; A.x32 = x32_dev; A.y32 = y32_dev;
+
+    std::vector<int32_t> count(G, 0), active(G);
+    std::vector<int64_t> acc_at((size_t)G + 1);
+    int rounds = 0;
+    bool done = false;
+    while (!done && rounds < max_rounds) {
+        // the unfinished bins share the round's lanes and candidates: P = what fits, a multiple of 64, at most 2^20
+        int n_active = 0;
+        int64_t actions = 0;
+        for (int g = 0; g < G; g++)
+            if (count[g] < owed[g]) {
+                active[n_active++] = g;
+                actions += (g / kAugBins) % kAugTypes == 0 ? kAugMaxActions : 1;
+            }
+        int64_t P = std::min<int64_t>(lanes / n_active, acc_cap / actions);
+        P = std::min<int64_t>(P / kAugThreads * kAugThreads, MESHENV_AUGMENT_MAX_ROUND);   // >= round_size: every subset fits
+        int64_t acc_total = 0;
+        for (int i = 0; i < n_active; i++) {
+            acc_at[i] = acc_total;
+            acc_total += P * ((active[i] / kAugBins) % kAugTypes == 0 ? kAugMaxActions : 1);
+        }
+        acc_at[n_active] = acc_total;
+        A.n_active = n_active;
+        A.P = (int)P;
+        // (pageable memory: the two vectors are not written again before the synchronise that ends the round)
+        if (hipMemcpyAsync(a->buf + o_active, active.data(), sizeof(int32_t) * n_active, hipMemcpyHostToDevice, a->stream) != hipSuccess ||
+            hipMemcpyAsync(a->buf + o_acc_at, acc_at.data(), sizeof(int64_t) * ((size_t)n_active + 1), hipMemcpyHostToDevice, a->stream) != hipSuccess)
+            return fail(a, MESHENV_E_HIP, fn + ": uploading the round's slots failed");
+        const dim3 grid_p((unsigned)(P / kAugThreads), n_active);
+        const dim3 grid_s((unsigned)(acc_total / kAugThreads));
+        int rc = launch(a, guard, fn.c_str(), [&] { hipLaunchKernelGGL(k_aug_propose, grid_p, dim3(kAugThreads), 0, a->stream, A); }, "proposal launch");
+        if (rc == MESHENV_OK)
+            rc = launch(a, guard, fn.c_str(), [&] { hipLaunchKernelGGL(k_aug_compact, dim3(n_active), dim3(kAugScanThreads), 0, a->stream, A); }, "compaction launch");
+        if (rc == MESHENV_OK)
+            rc = launch(a, guard, fn.c_str(), [&] { hipLaunchKernelGGL(k_aug_score, grid_s, dim3(kAugThreads), 0, a->stream, A); }, "scoring launch");
+        if (rc == MESHENV_OK)
+            rc = launch(a, guard, fn.c_str(), [&] { hipLaunchKernelGGL(k_aug_select, dim3(n_active), dim3(kAugScanThreads), 0, a->stream, A); }, "selection launch");
+        if (rc != MESHENV_OK) return rc;
+        rounds++;
+        if (hipMemcpyAsync(count.data(), A.count, sizeof(int32_t) * G, hipMemcpyDeviceToHost, a->stream) != hipSuccess ||
+            hipStreamSynchronize(a->stream) != hipSuccess)
+            return fail(a, MESHENV_E_HIP, fn + ": reading the counts failed");
+        done = true;
+        for (int g = 0; g < G; g++) done = done && count[g] >= owed[g];
+    }
+    if (counts_host) std::memcpy(counts_host, count.data(), sizeof(int32_t) * (size_t)G);
+    if (stats_host) {
+        std::vector<unsigned long long> tally(2 * (size_t)G);
+        if (hipMemcpy(tally.data(), A.tally, sizeof(unsigned long long) * tally.size(), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(a, MESHENV_E_HIP, fn + ": reading the tallies failed");
+        for (int g = 0; g < G; g++) {
+            stats_host[0] += tally[2 * (size_t)g];
+            stats_host[1] += tally[2 * (size_t)g + 1];
+            stats_host[2] += (uint64_t)count[g];
+        }
+        stats_host[3] = (uint64_t)rounds;
+    }
+    if (!done) {
+        int shortfall = 0;
+        for (int g = 0; g < G; g++) shortfall += count[g] < owed[g];
+        return fail(a, MESHENV_E_RANGE, fn + ": " + std::to_string(shortfall) + " of " + std::to_string(G) + " bins are short after " +
+                       std::to_string(rounds) + " rounds of " + std::to_string((long long)lanes) + " proposals");
+    }
+    return MESHENV_OK;
 }
 
 }  // extern "C"
