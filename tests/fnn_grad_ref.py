@@ -1,4 +1,5 @@
-"""Host side of the FNN-training tests (tests/test_fnn_grad_cpu.py, tests/test_gpu_fnn_grad.py): the statement of
+"""Host side of the FNN-training tests (tests/test_fnn_grad_cpu.py, tests/test_gpu_fnn_grad.py,
+tests/test_gpu_fnn_grad_range.py): the statement of
 general/EBRD.py's train_ch3 (:272-320) for one minibatch,
 
     action, logits = model(x)
@@ -18,7 +19,20 @@ NAMES = tuple(f"{name}.{part}" for name, _, _ in R.LAYERS for part in ("weight",
 LOSSES = ("loss", "classification_loss", "regression_loss")
 TEACHER = (12, 40.0)            # fnn_ref.forward_policy: its fp64 argmax is 1 or 2 on every row
 STUDENTS = (11, 6)              # fnn_ref.make_policy seeds
+# A student KEY names the net and the rows every helper below works on (policy, rows_of):
+#   seed                 fnn_ref.make_policy(seed) on data(): near-uniform softmax, logits in [-0.153, 0.099]
+#   (seed, type_scale)   fnn_ref.forward_policy(seed, type_scale) on data(): the same trunk, type_head.weight scaled
+#   ("dead", seed)       make_policy(seed) with crafted units in fc1 .. fc5 (dead_policy) on data()
+#   ("sampler", seed)    make_policy(seed) on sampler_rows()
+# CONFIDENT: logits in [-25, 39] with a spread up to 63.5 (the fp64 argmax is class 0 on every row), and in [-194, 121] with a
+# spread up to 313 (classes 1 / 2 on 332 / 3769 rows): a softmax without the row maximum overflows float32 on the second
+# (exp(121)) and not on the first, and exp(l - m) underflows to 0 on the second (exp(-313)).
+# forward_policy(12, s) is no student: it shares the teacher's trunk, its regression loss is 3e-17 and the yardstick collapses.
+CONFIDENT = ((11, 400.0), (6, 4000.0))
+DEAD = ("dead", 11)
+SAMPLER = (("sampler", 11), ("sampler", 6))
 POOL = 4101                     # rows of the shared data
+DEEP_B = 6145                   # 385 tiles on 128 workgroups: workgroup 0 walks four, the others three; the last tile has one row
 GPU_BS = (1, 15, 16, 17, 33, 128, 2065)   # 2065: 130 tiles on at most 128 workgroups, so two of them walk two tiles; the last tile has one row
 UNDECIDED_CAP = 0.01
 LR = 1e-3
@@ -107,14 +121,79 @@ def eager(policy, x, y, double=False, device="cpu"):
     return g
 
 
-# ------------------------------------------------------------------------------------------------------------ the ReLU condition
-@functools.lru_cache(maxsize=None)
-def undecided(seed, n=POOL):
-    """bool [n]: rows of data(n) on which some hidden pre-activation of make_policy(seed) has |z64| <= 8 max |z32 - z64| of its
-    layer: float32 and float64 may disagree about its ReLU mask, and a gradient compared across them says nothing there."""
+# ------------------------------------------------------------------------------------------------------------ students, conditions
+def crafted_units(out):
+    """Per hidden layer of `out` units: (units with a zero weight row and bias -1, the unit with a zero weight row and bias 0)."""
+    return (0, out - 1), 1
+
+
+def dead_policy(seed):
+    """make_policy(seed) in which, for each of fc1 .. fc5, units 0 and out - 1 have a zero weight row and bias -1 (dead on every
+    row) and unit 1 a zero weight row and bias 0: its pre-activation is exactly 0, where relu' is 0 in torch."""
     import torch
-    x, _ = data(n)
-    pol = R.make_policy(seed)
+    p = R.make_policy(seed)
+    with torch.no_grad():
+        for name, out, _ in R.LAYERS[:5]:
+            fc, (minus, zero) = getattr(p, name), crafted_units(out)
+            for u in (*minus, zero):
+                fc.weight[u].zero_()
+                fc.bias[u] = 0.0 if u == zero else -1.0
+    return p
+
+
+def dead_zero_blocks():
+    """[(gradient name, index)] of what dead_policy's crafted units make exactly zero: their weight rows and bias entries
+    (relu' is 0 at -1 and at 0) and, their activation being 0, the matching columns of the next layer's weight gradient --
+    fc5's in both heads."""
+    blocks = []
+    for i, (name, out, _) in enumerate(R.LAYERS[:5]):
+        minus, zero = crafted_units(out)
+        units = [*minus, zero]
+        blocks += [(f"{name}.weight", (units, slice(None))), (f"{name}.bias", (units,))]
+        for nxt in ([R.LAYERS[i + 1][0]] if i < 4 else ["action_head", "type_head"]):
+            blocks.append((f"{nxt}.weight", (slice(None), units)))
+    return blocks
+
+
+def policy(key):
+    """The eager module of a student key (STUDENTS' comment)."""
+    if isinstance(key, tuple) and key[0] == "dead":
+        return dead_policy(key[1])
+    if isinstance(key, tuple) and key[0] == "sampler":
+        return R.make_policy(key[1])
+    if isinstance(key, tuple):
+        return R.forward_policy(*key)
+    return R.make_policy(key)
+
+
+@functools.lru_cache(maxsize=None)
+def sampler_rows():
+    """(x [90, 18], y [90, 3]) float32: the data the trainer exists for.  Of the reference's recorded candidates
+    (tests/golden/quality_augment_scores.npz) the rows accepted at threshold 0.7 and the extra_* rows: 30 per type, x in
+    [-1.57, 4.51], targets in [0.04, 1.82]."""
+    import os
+    z = np.load(os.path.join(R.GOLDEN_DIR, "quality_augment_scores.npz"))
+    at = int(np.flatnonzero(z["thresholds"] == 0.7)[0])
+    keep = z["accept"][:, at]
+    x = np.concatenate([z["prop_obs"][z["prop"]][keep], z["extra_obs"]]).astype(np.float32)
+    y = np.concatenate([z["act"][keep], z["extra_act"]]).astype(np.float32)
+    return np.ascontiguousarray(x), np.ascontiguousarray(y)
+
+
+def rows_of(key, n=POOL):
+    """(x, y) a student key works on."""
+    return sampler_rows() if isinstance(key, tuple) and key[0] == "sampler" else data(n)
+
+
+@functools.lru_cache(maxsize=None)
+def relu_undecided(key, n=POOL):
+    """bool [rows]: rows of rows_of(key, n) on which some hidden pre-activation of policy(key) has |z64| <= 8 max |z32 - z64| of
+    its layer: float32 and float64 may disagree about its ReLU mask, and a gradient compared across them says nothing there.
+    A unit whose pre-activation is identical in float32 and float64 on every row (dead_policy's) is decided whatever its value:
+    it is left out, or the unit at exactly 0 would flag every row."""
+    import torch
+    x, _ = rows_of(key, n)
+    pol = policy(key)
     P64 = params64(pol)
     z64, _ = pre_activations(P64, x.astype(np.float64))
     with torch.no_grad():
@@ -123,39 +202,69 @@ def undecided(seed, n=POOL):
             z = getattr(pol, name)(h)
             z32.append(z.numpy().astype(np.float64))
             h = torch.relu(z)
-    bad = np.zeros(n, bool)
+    bad = np.zeros(len(x), bool)
     for a, b in zip(z32, z64):
-        bad |= (np.abs(b) <= 8 * np.abs(a - b).max()).any(axis=1)
+        exact = (a == b).all(axis=0)
+        bad |= ((np.abs(b) <= 8 * np.abs(a - b).max()) & ~exact).any(axis=1)
     return bad
 
 
 @functools.lru_cache(maxsize=None)
-def decided_pool(seed):
-    """(x, y) of data() without the undecided rows of make_policy(seed): what every batch of that student is cut from."""
-    x, y = data()
-    keep = ~undecided(seed)
+def margin_undecided(key, n=POOL):
+    """bool [rows]: rows whose fp64 top-two logit margin is <= 8 max |l32 - l64|: float32 and float64 may disagree about the
+    argmax, and `hits` compared across them says nothing there."""
+    x, _ = rows_of(key, n)
+    pol = policy(key)
+    _, l32 = R.eager(pol, x)
+    _, l64 = R.eager(pol, x, double=True)
+    top = np.sort(l64, axis=1)
+    return top[:, 2] - top[:, 1] <= 8 * float(np.abs(l32 - l64).max())
+
+
+def undecided(key, n=POOL):
+    """bool [rows]: the rows left out of every batch of student `key`.  The ReLU condition; for the keyed students (tuples) the
+    hits condition as well.  The plain seeds keep the rows they had: their hits are pinned batch by batch
+    (tests/test_fnn_grad_cpu.py)."""
+    bad = relu_undecided(key, n)
+    return bad | margin_undecided(key, n) if isinstance(key, tuple) else bad
+
+
+@functools.lru_cache(maxsize=None)
+def decided_pool(key):
+    """(x, y) of rows_of(key) without the undecided rows of policy(key): what every batch of that student is cut from."""
+    x, y = rows_of(key)
+    keep = ~undecided(key)
     return np.ascontiguousarray(x[keep]), np.ascontiguousarray(y[keep])
 
 
-def batch(seed, B, gather=False):
-    """(x, y, rows) for student `seed`: the first B decided rows (rows None), or the whole decided pool with rows = B distinct
-    shuffled indices into it."""
-    x, y = decided_pool(seed)
-    assert B <= len(x)
+def batch(key, B, gather=False):
+    """(x, y, rows) for student `key`: the first B decided rows (rows None), or the whole decided pool with rows = B distinct
+    shuffled indices into it.  B past the pool (DEEP_B): the pool cycled to B rows, or rows a shuffled order of the pool cycled
+    to B entries -- indices that repeat, into the un-cycled pool."""
+    x, y = decided_pool(key)
     if not gather:
+        if B > len(x):
+            return np.resize(x, (B, x.shape[1])), np.resize(y, (B, y.shape[1])), None
         return x[:B].copy(), y[:B].copy(), None
-    rows = np.random.default_rng(1000 + B).permutation(len(x))[:B].astype(np.int32)
+    perm = np.random.default_rng(1000 + B).permutation(len(x))
+    rows = (np.resize(perm, B) if B > len(x) else perm[:B]).astype(np.int32)
     return x, y, rows
 
 
 @functools.lru_cache(maxsize=None)
-def references(seed, B, gather=False):
-    """(fp64 restatement, eager float32, eager float64) of student `seed` on batch(seed, B, gather): computed once."""
-    x, y, rows = batch(seed, B, gather)
+def references(key, B, gather=False):
+    """(fp64 restatement, eager float32, eager float64) of student `key` on batch(key, B, gather): computed once."""
+    x, y, rows = batch(key, B, gather)
     if rows is not None:
         x, y = x[rows], y[rows]
-    pol = R.make_policy(seed)
+    pol = policy(key)
     return restated(params64(pol), x, y), eager(pol, x, y), eager(pol, x, y, double=True)
+
+
+def exact_zeros(g32, g64):
+    """Per gradient name the bool mask of the elements that are exactly 0 in eager float32 AND in eager float64 (a unit dead on
+    the whole batch, a column fed by one): there the device's value must be exactly 0 too, whatever the tensor's bound."""
+    return {k: (np.asarray(g32[k]) == 0) & (np.asarray(g64[k]) == 0) for k in NAMES}
 
 
 def bounds(g32, g64):
@@ -163,6 +272,12 @@ def bounds(g32, g64):
     floor, the floor scaled by the tensor because a summed loss grows with B)."""
     return {k: 4 * float(np.abs(np.asarray(g32[k]) - np.asarray(g64[k])).max()) + 1e-6 * float(np.abs(np.asarray(g64[k])).max())
             for k in (*NAMES, *LOSSES)}
+
+
+def zero_violations(got, g32, g64):
+    """{name: count} of the elements exact_zeros() names at which `got` is not exactly 0 (-0 counts as 0); empty when none."""
+    bad = {k: int((np.asarray(got[k])[m] != 0).sum()) for k, m in exact_zeros(g32, g64).items()}
+    return {k: v for k, v in bad.items() if v}
 
 
 def ratios(got, g64, bound):

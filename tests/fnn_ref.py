@@ -193,6 +193,37 @@ def closed_loop_counts(loop, max_steps=MAX_STEPS):
                 finished_early=int((finished & (steps < max_steps)).sum()), unfinished=int((~finished).sum()))
 
 
+# ---- the early-stop net: all weights zero, type_head.bias (1, 0, 0), action_head.bias EARLY_STOP_POINT.  The logits are the bias
+# exactly, so every forward returns type 0 and that point, and the oracle alone says where each of EARLY_STOP_ENVS envs
+# (two forward tiles, the second ragged) ends: every env with done = 1, complete = 0, code 0, after EARLY_STOP_STEPS moves,
+# each through smooth_pave at least once.
+EARLY_STOP_POINT = (0.375, -1.25)
+EARLY_STOP_TYPE_BIAS = (1.0, 0.0, 0.0)
+EARLY_STOP_ENVS = 21
+EARLY_STOP_STEPS = (10, 8, 10, 162, 108, 26, 12, 179, 137, 10, 192, 151, 39, 185, 116, 68, 10, 8, 10, 162, 108)
+
+
+def early_stop_state_dict():
+    import torch
+    sd = {k: torch.zeros_like(v) for k, v in make_policy(0).state_dict().items()}
+    sd["type_head.bias"] = torch.tensor(EARLY_STOP_TYPE_BIAS, dtype=torch.float32)
+    sd["action_head.bias"] = torch.tensor(EARLY_STOP_POINT, dtype=torch.float32)
+    return sd
+
+
+def early_stop_cpu(max_steps=500):
+    """The oracle alone under the early-stop net's constant action: the OracleLoop after at most max_steps vector steps, and
+    the number of vector steps made."""
+    loop = OracleLoop(make_refs(closed_loop_domains(), EARLY_STOP_ENVS))
+    points = np.tile(np.float64(np.float32(EARLY_STOP_POINT)), (EARLY_STOP_ENVS, 1))
+    types = np.zeros(EARLY_STOP_ENVS)
+    total = 0
+    while total < max_steps and not loop.finished.all():
+        loop.step(points, types)
+        total += 1
+    return loop, total
+
+
 def forward_observations(n):
     """n observation rows for the forward tests: the static observations the closed loop of CLOSED_LOOP_SEED visited (its
     reset(static=True) rows first), cycled, with every 17th row zero (the reference's None)."""

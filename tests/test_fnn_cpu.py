@@ -117,6 +117,32 @@ def test_seed_hunt_closed_loop_net_meets_the_conditions_of_the_gpu_test():
     assert (loop.steps[~loop.finished] == R.MAX_STEPS).all() and (loop.steps[loop.finished] < R.MAX_STEPS).all()
 
 
+def test_early_stop_net_finishes_every_env_where_the_oracle_says():
+    """The crafted net of the GPU early-stop tests returns type 0 and EARLY_STOP_POINT whatever it reads; the oracle alone then
+    gives the step count of each of the 21 envs (16 domains, the first five twice).  Pinned as observed here."""
+    import torch
+    sd = R.early_stop_state_dict()
+    net = R.make_policy(0)
+    net.load_state_dict(sd)
+    pts, typ = R.get_action(net, R.forward_observations(33))
+    assert np.array_equal(pts, np.tile(np.float64(np.float32(R.EARLY_STOP_POINT)), (33, 1))) and not typ.any()
+    assert int(torch.argmax(torch.tensor(R.EARLY_STOP_TYPE_BIAS))) == 0
+    loop, total = R.early_stop_cpu()
+    print("early-stop net: vector steps", total, "steps", loop.steps.tolist(), "smooth_pave passes", loop.smoothed.tolist(),
+          "accepted moves", loop.accepted.tolist())
+    assert R.EARLY_STOP_ENVS == 21 > 16 and R.EARLY_STOP_ENVS % 16 != 0
+    assert total == max(R.EARLY_STOP_STEPS) == 192 and loop.finished.all()
+    assert loop.steps.tolist() == list(R.EARLY_STOP_STEPS)
+    assert (loop.done == 1).all() and (loop.complete == 0).all() and (loop.code == 0).all()
+    assert (loop.smoothed >= 1).all()
+    # what the GPU tests cut out of these counts: chunks of 50 stop at 200; 195 = 50 + 50 + 50 + 45 covers the longest env; a
+    # budget of 9 = 4 + 4 + 1 finishes exactly the envs that need 8
+    assert -(-192 // 50) * 50 == 200 and 192 <= 195 and sorted(set(R.EARLY_STOP_STEPS))[:2] == [8, 10]
+    assert R.EARLY_STOP_STEPS.count(8) == 2
+    # the domains repeat with period 16
+    assert R.EARLY_STOP_STEPS[16:] == R.EARLY_STOP_STEPS[:5]
+
+
 @pytest.mark.parametrize("seed,type_scale", R.FORWARD_NETS)
 def test_seed_hunt_forward_nets_keep_the_margin_cap(seed, type_scale):
     """Eager torch float32 against float64 alone, on the observations the GPU forward test uses: at most 1 % of the rows may

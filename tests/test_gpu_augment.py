@@ -173,6 +173,66 @@ def test_invariants_at_440(aug):
     assert st["rows"] == 407 and st["proposals"] % 64 == 0 and st["proposals"] >= 33 * 8192 and 0 < st["candidates"] < 20 * st["proposals"]
 
 
+def _per_bin(x, y, n):
+    """{(type index, bin): (x rows, y rows)} of sampling(n, ...) with pool = 1, from the order type / bin / acceptance."""
+    from reinforcementlearning4meshgeneration_amd.augmentation import rows_per_bin
+    out, at = {}, 0
+    for t, quota in enumerate(rows_per_bin(n)):
+        for b in range(11):
+            out[t, b] = (x[at:at + quota], y[at:at + quota])
+            at += quota
+    assert at == len(x) == len(y)
+    return out
+
+
+def _assert_prefix(small, n_small, large, n_large):
+    """Per (type, bin) the rows of sampling(n_small) are the first rows of that bin in sampling(n_large), bit for bit."""
+    import torch
+    a, b = _per_bin(*small, n_small), _per_bin(*large, n_large)
+    for key, (xs, ys) in a.items():
+        xl, yl = b[key]
+        assert 0 < len(xs) < len(xl), key
+        assert torch.equal(xs, xl[:len(xs)]) and torch.equal(ys, yl[:len(ys)]), key
+        assert bool((ys[:, 0] == A.TYPES[key[0]]).all()) and bool((yl[:, 0] == A.TYPES[key[0]]).all()), key
+
+
+def test_rows_of_a_bin_are_a_prefix_of_its_stream_whatever_n(aug):
+    """The sampler's claim across n: a bin's rows are the first accepted candidates of its stream, so the 3 / 1 / 1 rows a bin
+    owes at n = 88 are the first of the 19 / 9 / 9 it owes at n = 440."""
+    import torch
+    from reinforcementlearning4meshgeneration_amd.augmentation import rows_per_bin
+    assert rows_per_bin(88) == (3, 1, 1) and rows_per_bin(440) == (19, 9, 9)
+    small = aug.sampling(88, 0.7, seed=9, dtype=torch.float64)
+    large = aug.sampling(440, 0.7, seed=9, dtype=torch.float64)
+    assert tuple(small[0].shape) == (55, 18) and tuple(large[0].shape) == (407, 18)
+    _assert_prefix(small, 88, large, 440)
+
+
+def test_sparse_bins_at_threshold_08(aug):
+    """Threshold 0.8: few candidates are accepted, bins fill over many rounds and the lanes of finished bins are shared among
+    the short ones.  The rows are the same whatever the round size, each is accepted when scored again, and they are a per-bin
+    prefix of a larger n."""
+    import torch
+    from reinforcementlearning4meshgeneration_amd.augmentation import rows_per_bin
+    x, y = aug.sampling(88, 0.8, seed=1, dtype=torch.float64, round_size=2048)
+    small_rounds = dict(aug.last_stats)
+    x2, y2 = aug.sampling(88, 0.8, seed=1, dtype=torch.float64, round_size=8192)
+    large_rounds = dict(aug.last_stats)
+    print(f"  threshold 0.8, n 88: round_size 2048 {small_rounds}; round_size 8192 {large_rounds}")
+    assert tuple(x.shape) == (55, 18) and tuple(y.shape) == (55, 3)
+    assert torch.equal(x, x2) and torch.equal(y, y2)
+    assert small_rounds["rounds"] != large_rounds["rounds"] and small_rounds["rows"] == large_rounds["rows"] == 55
+    assert (aug.last_counts == np.array([3, 1, 1])[None, :, None]).all()
+    s = aug.score(x, y, 0.8)
+    assert s.accept.all() and s.valid.all() and not s.obs_rejected.any()
+    assert rows_per_bin(176) == (7, 3, 3)
+    large = aug.sampling(176, 0.8, seed=1, dtype=torch.float64)
+    print(f"  threshold 0.8, n 176: {aug.last_stats}")
+    _assert_prefix((x, y), 88, large, 176)
+    s = aug.score(*large, 0.8)
+    assert s.accept.all() and s.valid.all() and not s.obs_rejected.any()
+
+
 def test_obs_rejection_rate_is_the_references(aug):
     import torch
     z = _npz("quality_augment_scores.npz")

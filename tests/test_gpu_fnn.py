@@ -2,7 +2,9 @@
   (a) the forward against the same net in float64, with a tolerance measured from eager torch float32 against float64;
       points / types exactly what EBRD.get_action makes of the device's own float32 outputs; crafted heads for ties and NaN;
   (b) mesh_with in lockstep with the oracle's move() on 48 envs over 16 domains, the freeze of finished envs (the skip
-      mask), record=False against record=True, and the log_capacity = 0 path.
+      mask), record=False against record=True, and the log_capacity = 0 path;
+  (c) the early stops of mesh_with on a crafted net and 21 envs: the finished.all() break, a last chunk shorter than
+      check_every, a call on a batch that has finished, a budget shorter than most episodes.
 tests/fnn_ref.py holds the nets, the observations and the counts tests/test_fnn_cpu.py pinned for them on the CPU."""
 import functools
 
@@ -90,10 +92,10 @@ def test_argmax_ties_take_the_lowest_index_and_the_first_nan_wins(bias, want):
 
 
 # --------------------------------------------------------------------------------------------------------- closed loop
-def _make_env(log_capacity=512):
+def _make_env(log_capacity=512, n=R.N_ENVS):
     from reinforcementlearning4meshgeneration_amd import MeshVecEnv
     doms = R.closed_loop_domains()
-    env_domain = (np.arange(R.N_ENVS) % len(doms)).astype(np.int32)
+    env_domain = (np.arange(n) % len(doms)).astype(np.int32)
     return MeshVecEnv(doms, env_domain=env_domain, auto_reset=False, log_capacity=log_capacity)
 
 
@@ -113,6 +115,22 @@ def _same(a, b):
 EXTRA_STEPS = 16
 
 
+FINAL = ("steps", "done", "complete", "code", "finished", "n_elements")
+
+
+def _leg(env, loop, res):
+    """What a recorded mesh_with call left, with the oracle loop stepped through the same moves -- fed the device's own recorded
+    points and types."""
+    hist = {k: getattr(res, k).cpu().numpy() for k in ("points", "types", "obs", "step_code", "step_done", "step_complete")}
+    final = {k: getattr(res, k).cpu().numpy() for k in FINAL}
+    trace = []
+    for t in range(res.total_steps):
+        before = (loop.finished.copy(), loop.obs.copy())
+        trace.append(before + loop.step(hist["points"][t], hist["types"][t]))
+    return dict(total_steps=res.total_steps, hist=hist, final=final, trace=trace, oracle=loop.summary(),
+                snaps=[_snapshot(env, k) for k in range(env.num_envs)], obs_end=env.obs.cpu().numpy().copy())
+
+
 @pytest.fixture(scope="module")
 def run():
     """Once for the tests below: mesh_with(record=True) of the seeded closed-loop net, then EXTRA_STEPS more moves through
@@ -123,18 +141,8 @@ def run():
     env = _make_env()
     loop = R.OracleLoop(R.make_refs(R.closed_loop_domains(), R.N_ENVS))
 
-    def leg(res):
-        hist = {k: getattr(res, k).cpu().numpy() for k in ("points", "types", "obs", "step_code", "step_done", "step_complete")}
-        final = {k: getattr(res, k).cpu().numpy() for k in ("steps", "done", "complete", "code", "finished", "n_elements")}
-        trace = []
-        for t in range(res.total_steps):
-            before = (loop.finished.copy(), loop.obs.copy())
-            trace.append(before + loop.step(hist["points"][t], hist["types"][t]))
-        return dict(total_steps=res.total_steps, hist=hist, final=final, trace=trace, oracle=loop.summary(),
-                    snaps=[_snapshot(env, k) for k in range(R.N_ENVS)], obs_end=env.obs.cpu().numpy().copy())
-
-    first = leg(env.mesh_with(fnn, max_steps=R.MAX_STEPS, check_every=8, record=True))
-    more = leg(env.mesh_with(fnn, max_steps=EXTRA_STEPS, check_every=8, record=True, reset=False))
+    first = _leg(env, loop, env.mesh_with(fnn, max_steps=R.MAX_STEPS, check_every=8, record=True))
+    more = _leg(env, loop, env.mesh_with(fnn, max_steps=EXTRA_STEPS, check_every=8, record=True, reset=False))
     return dict(policy=policy, fnn=fnn, env=env, first=first, more=more)
 
 
@@ -161,7 +169,7 @@ def _check_leg(leg):
     assert np.array_equal(final["done"], oracle["done"]) and np.array_equal(final["complete"], oracle["complete"])
     ok = oracle["code"] == 0
     assert np.abs(leg["obs_end"][ok].astype(np.float64) - oracle["obs"][ok]).max() <= 1e-5
-    for k in range(R.N_ENVS):
+    for k in range(len(leg["snaps"])):
         ids, xy = oracle["rings"][k]
         snap = leg["snaps"][k]
         assert np.array_equal(snap["ring_ids"], ids) and np.array_equal(snap["ring_xy"], xy), k
@@ -276,3 +284,95 @@ def test_move_fnn_refuses_what_it_cannot_run(run):
     with pytest.raises(MeshEnvError, match="no output"):
         fnn._check(fnn._L.meshenv_fnn_forward(fnn._h, 4, torch.zeros((4, 18), device="cuda").data_ptr(), None, None, None, None, None),
                    "meshenv_fnn_forward")
+
+
+# ---------------------------------------------------------------------------------------------------------- early stops
+def _early_env():
+    return _make_env(n=R.EARLY_STOP_ENVS)
+
+
+@pytest.fixture(scope="module")
+def early():
+    """Once for the tests below: the early-stop net of tests/fnn_ref.py (type 0 and one point whatever it reads) on 21 envs,
+    mesh_with(max_steps=500, check_every=50, record=True) with the oracle in lockstep, then eight more moves on the batch that
+    has finished.  tests/test_fnn_cpu.py pins the step counts with the oracle alone."""
+    from reinforcementlearning4meshgeneration_amd import FusedFNN
+    fnn = FusedFNN.from_state_dict(R.early_stop_state_dict())
+    env = _early_env()
+    loop = R.OracleLoop(R.make_refs(R.closed_loop_domains(), R.EARLY_STOP_ENVS))
+    first = _leg(env, loop, env.mesh_with(fnn, max_steps=500, check_every=50, record=True))
+    state = {k: v.clone() for k, v in env._fnn_state.items()}
+    again = env.mesh_with(fnn, max_steps=8, check_every=8, record=True, reset=False)
+    after = dict(total_steps=again.total_steps, final={k: getattr(again, k).cpu().numpy() for k in FINAL},
+                 hist={k: getattr(again, k).cpu().numpy() for k in ("points", "types", "obs", "step_code", "step_done", "step_complete")},
+                 snaps=[_snapshot(env, k) for k in range(R.EARLY_STOP_ENVS)], obs_end=env.obs.cpu().numpy().copy(),
+                 state_before=state, state_after={k: v.clone() for k, v in env._fnn_state.items()})
+    yield dict(fnn=fnn, first=first, after=after)
+    env.close()
+    fnn.close()
+
+
+def test_mesh_with_stops_at_the_chunk_in_which_the_last_env_finishes(early):
+    leg = early["first"]
+    hist, final = leg["hist"], leg["final"]
+    steps = np.array(R.EARLY_STOP_STEPS)
+    assert leg["total_steps"] == 200 and final["finished"].all() and hist["obs"].shape == (200, R.EARLY_STOP_ENVS, 18)
+    worst = _check_leg(leg)
+    print("early stop on the device: total_steps", leg["total_steps"], "steps", final["steps"].tolist(), "smooth_pave passes",
+          leg["oracle"]["smoothed"].tolist(), "max obs err", worst)
+    assert final["steps"].tolist() == list(R.EARLY_STOP_STEPS)
+    assert (final["done"] == 1).all() and (final["complete"] == 0).all() and (final["code"] == 0).all()
+    assert (leg["oracle"]["smoothed"] >= 1).all()
+    # every forward returned the crafted action: type 0 and the point, on live rows; rows after an env's last move 255 / zeros
+    live = np.arange(200)[:, None] < steps[None, :]
+    assert np.array_equal(hist["step_code"] != 255, live)
+    assert (hist["points"][live] == np.float64(np.float32(R.EARLY_STOP_POINT))).all() and not hist["types"][live].any()
+    for k in ("points", "types", "obs", "step_done", "step_complete"):
+        assert not hist[k][~live].any(), k
+    # done is raised at each env's last move and at no other
+    last = np.zeros_like(live)
+    last[steps - 1, np.arange(R.EARLY_STOP_ENVS)] = True
+    assert np.array_equal(hist["step_done"] != 0, last)
+
+
+def test_a_last_chunk_shorter_than_check_every(early):
+    fnn, first = early["fnn"], early["first"]
+    env = _early_env()
+    res = env.mesh_with(fnn, max_steps=195, check_every=50, record=True)
+    assert res.total_steps == 195 and tuple(res.step_code.shape) == (195, R.EARLY_STOP_ENVS) and bool(res.finished.all())
+    for k in FINAL:
+        assert np.array_equal(getattr(res, k).cpu().numpy(), first["final"][k]), k
+    assert all(_same(_snapshot(env, k), first["snaps"][k]) for k in range(R.EARLY_STOP_ENVS))
+    assert np.array_equal(env.obs.cpu().numpy(), first["obs_end"])
+    for k in ("points", "types", "obs", "step_code", "step_done", "step_complete"):
+        assert np.array_equal(getattr(res, k).cpu().numpy(), first["hist"][k][:195]), k
+    env.close()
+
+
+def test_a_finished_batch_is_left_byte_for_byte(early):
+    import torch
+    first, after = early["first"], early["after"]
+    assert after["total_steps"] == 8
+    assert all(_same(a, b) for a, b in zip(first["snaps"], after["snaps"]))
+    assert after["obs_end"].tobytes() == first["obs_end"].tobytes()
+    for k, v in after["state_before"].items():
+        assert torch.equal(v, after["state_after"][k]) and v.dtype == after["state_after"][k].dtype, k
+    for k in FINAL:
+        assert np.array_equal(after["final"][k], first["final"][k]), k
+    h = after["hist"]
+    assert h["step_code"].shape == (8, R.EARLY_STOP_ENVS) and (h["step_code"] == 255).all()
+    for k in ("points", "types", "obs", "step_done", "step_complete"):
+        assert not h[k].any(), k
+
+
+def test_a_budget_shorter_than_most_episodes(early):
+    fnn = early["fnn"]
+    steps = np.array(R.EARLY_STOP_STEPS)
+    env = _early_env()
+    res = env.mesh_with(fnn, max_steps=9, check_every=4)
+    assert res.total_steps == 9 and res.points is None
+    finished = res.finished.cpu().numpy() != 0
+    assert np.array_equal(finished, steps == 8) and finished.sum() == 2
+    assert np.array_equal(res.steps.cpu().numpy(), np.minimum(steps, 9)) and (res.steps.cpu().numpy()[~finished] == 9).all()
+    assert np.array_equal(res.done.cpu().numpy() != 0, finished)
+    env.close()

@@ -1,7 +1,9 @@
 """GPU: training the supervised FNN (include/meshenv_fnn_train.h; csrc/meshenv_fnn_grad.h: k_fnn_grad, k_fnn_grad_reduce;
 k_optim_step; k_target_pack through meshenv_fnn_refresh):
   (a) the fourteen gradients and the three losses against float64, within a bound made of eager torch float32 against float64
-      on the same rows (never of the kernel): 4 err_torch + 1e-6 max |g64| per tensor; determinism, rows past B, accum, hits;
+      on the same rows (never of the kernel): 4 err_torch + 1e-6 max |g64| per tensor, and exactly 0 wherever eager float32 and
+      float64 both give exactly 0; determinism, rows past B, accum, hits (tests/test_gpu_fnn_grad_range.py: confident and
+      dead-unit students, a deep tile walk, the sampler's rows, ties, ragged fit);
   (b) one backward + step against eager float32 + a stock Adam step, within twice the one-step bound of tests/ppo_grad_ref.py;
   (c) refresh() against a freshly packed FusedFNN, bit for bit;
   (d) fit against the hand loop (bits), against eager float64 (the measured float32 distance), and mesh_with afterwards.
@@ -71,6 +73,7 @@ def test_gradients_and_losses_against_float64(seed, gather):
             worst[k] = max(worst.get(k, 0.0), v)
         assert all(got[k].dtype == np.float32 and got[k].shape == np.shape(e64[k]) for k in G.NAMES)
         assert max(w.values()) <= 1.0, (B, {k: v for k, v in w.items() if v > 1.0})
+        assert not G.zero_violations(got, e32, e64), (B, G.zero_violations(got, e32, e64))   # exact zeros of eager stay exact zeros
         assert got["hits"] == e64["hits"] == want["hits"]
         kept = [p.grad.clone() for p in pol.parameters()]
         out2 = tr.backward(xd, yd, rows=rd)                                        # the same bits
@@ -120,6 +123,7 @@ def test_a_row_with_a_bad_label_adds_nothing_and_is_refused_when_validated():
     w = G.ratios(got, e64, G.bounds(e32, e64))
     print(f"\nfnn grad with a bad label at row 20 against fp64 without that row: {_fmt(w)}")
     assert max(w.values()) <= 1.0 and got["hits"] == want["hits"]
+    assert not G.zero_violations(got, e32, e64), G.zero_violations(got, e32, e64)
     # a rows entry outside [0, N) likewise, when validate=False lets it through: the kernel reads nothing there
     rows = np.arange(B, dtype=np.int32)
     rows[20] = 10 ** 6
