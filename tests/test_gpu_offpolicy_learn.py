@@ -11,15 +11,13 @@ after it (99 > 50)."""
 import numpy as np
 import pytest
 
-import offpolicy_learn_ref as LR
+import learn_twins as LT
 import offpolicy_train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 N, T, LS, GS, BATCH, SEED = 33, 3, 50, 2, 16, 6
-SIGMA = np.array([0.1, 0.2, 0.05], np.float32)
-LOW = np.array([-1.0, -1.5, 0.0], np.float32)
-HIGH = np.array([1.0, 1.5, 1.5], np.float32)
+SIGMA = LT.SIGMA
 
 
 def _env():
@@ -35,106 +33,14 @@ def _model(kind, **attrs):
     return TR.model(kind, **base)
 
 
-class Twin:
-    """SB3's loop by hand over step_tensor / step_actor_T / collect_rollout / add_rollout / the train composition."""
+class Twin(LT.OffPolicyTwin):
+    """tests/learn_twins.py's hand loop at this module's shape."""
 
     def __init__(self, model, kind):
-        from reinforcementlearning4meshgeneration_amd import DeviceReplayBuffer
-        self.m, self.kind = model, kind
-        self.env = _env()
-        self.buf = DeviceReplayBuffer(self.env, model.buffer_size)
-        self.comp = TR.Composition(model, self.buf)
-        self.monitor = LR.MonitorRef(N, 100)
-        self.steps = self.draws = 0
-        self.rebuilds = self.trains = self.uniform_calls = 0
-
-    def close(self):
-        self.comp.close()
-        self.env.close()
-
-    def _note(self, out):
-        self.monitor.update(out["reward"].cpu().numpy(), out["done"].cpu().numpy(), out["complete"].cpu().numpy())
-
-    def _warmup(self, W):
-        import torch
-        env = self.env
-        a, b = LR.uniform_actions(SEED, self.steps, W, N, LOW, HIGH)
-        actions, buffer_actions = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
-        obs = [env.obs.clone()]
-        hist = dict(reward=[], done=[], complete=[], terminal_obs=[])
-        for t in range(W):
-            o, r, d, c = env.step_tensor(actions[t])
-            obs.append(o.clone())
-            hist["reward"].append(r.clone()); hist["done"].append(d.clone()); hist["complete"].append(c.clone())
-            hist["terminal_obs"].append(torch.where(d[:, None] != 0, env.terminal_obs, torch.zeros_like(env.terminal_obs)))
-        out = {k: torch.stack(v) for k, v in hist.items()}
-        out.update(obs=torch.stack(obs[:W]), obs_after=torch.stack(obs[1:]), actions=actions, buffer_actions=buffer_actions)
-        self.buf.add_rollout(out)
-        self._note(out)
-        self.uniform_calls += 1
-
-    def _behave(self, P, counter):
-        from reinforcementlearning4meshgeneration_amd import FusedActor, FusedPolicy
-        env = self.env
-        self.rebuilds += 1
-        if self.kind == "sac":
-            actor = FusedActor.from_sb3(self.m)                          # through the host, every time
-            try:
-                obs0 = env.obs.clone()
-                first = actor.sample(obs0, SEED, counter)
-                out = env.step_actor_T(actor, first, P, seed=SEED, counter=counter + 1, want_terminal_obs=True)
-                self.buf.add_rollout(out, obs0=obs0)
-            finally:
-                actor.close()
-        else:
-            policy = FusedPolicy.from_sb3(self.m, sigma=SIGMA)
-            try:
-                out = env.collect_rollout(policy, P, seed=SEED, counter=counter)
-                self.buf.add_rollout(out)
-            finally:
-                policy.close()
-        self._note(out)
-
-    def learn(self, total_timesteps):
-        m = self.m
-        total = total_timesteps + m.num_timesteps
-        while m.num_timesteps < total:
-            flags = []
-            nt = m.num_timesteps
-            for _ in range(T):                                            # SB3 tests before each step's increment
-                flags.append(nt < m.learning_starts)
-                nt += N
-            W = sum(flags)
-            assert flags == [True] * W + [False] * (T - W)
-            if W:
-                self._warmup(W)
-            if T - W:
-                self._behave(T - W, self.steps + W)
-            self.steps += T
-            m.num_timesteps = nt
-            m._current_progress_remaining = 1.0 - float(nt) / float(total)
-            if nt > 0 and nt > m.learning_starts and m.gradient_steps != 0:
-                K = m.gradient_steps if m.gradient_steps > 0 else T
-                self.comp.train(K, seed=SEED, counter=self.draws)
-                self.draws += K
-                self.trains += 1
+        super().__init__(model, kind, n_envs=N, train_freq=T, seed=SEED)
 
 
-def _assert_equal(learn, twin, m, tw):
-    import torch
-    assert TR.differing(m, tw) == []                                      # parameters, moments, steps, targets, _n_updates
-    assert m.num_timesteps == tw.num_timesteps and m._current_progress_remaining == tw._current_progress_remaining
-    a, b = learn.buffer, twin.buf
-    assert (a.pos, a.full, a.size()) == (b.pos, b.full, b.size())
-    assert torch.equal(a.store.view(torch.int32), b.store.view(torch.int32))
-    assert torch.equal(learn.venv.obs.view(torch.int32), twin.env.obs.view(torch.int32))
-    assert torch.equal(learn.venv.done, twin.env.done)
-    stats, ref = learn.stats, twin.monitor
-    assert int(stats.count.cpu().numpy().view(np.uint64)[0]) == ref.count
-    assert np.array_equal(stats.ring.cpu().numpy().view(np.int64), ref.ring().view(np.int64))
-    cr, cl = ref.carries()
-    assert np.array_equal(stats.carry_return.cpu().numpy().view(np.int64), cr.view(np.int64))
-    assert np.array_equal(stats.carry_len.cpu().numpy(), cl)
+_assert_equal = LT.assert_offpolicy_equal
 
 
 @pytest.mark.parametrize("kind", ["sac", "td3"])
