@@ -610,7 +610,11 @@ int meshenv_replay_sample(MeshEnv *h, const float *store_dev, int rows, int size
  *     noise = actions.clone().normal_(0, target_policy_noise).clamp(-target_noise_clip, target_noise_clip)
  *     next_actions = (actor_target(next_observations) + noise).clamp(-1, 1)
  *     next_q_values = min(cat(critic_target(next_observations, next_actions), dim=1), dim=1)
- *   both: target_q_values = rewards + (1 - dones) * gamma * next_q_values          (float32, in that order)
+ *   kind 2, DDPG (csrc/meshenv_wide.h; the reference's DDPG('MlpPolicy', env), rl/baselines/RL_Mesh.py:113-228: SB3's TD3.train
+ *     with n_critics = 1, actor_target ReLU [400, 300] + tanh, ONE critic ReLU [400, 300]): the statements of kind 1 with
+ *     next_q_values = critic_target(next_observations, next_actions)[0]; SB3's DDPG passes target_policy_noise = 0.1 and
+ *     target_noise_clip = 0.0, which makes the noise term +-0 -- the formula is evaluated as written
+ *   all: target_q_values = rewards + (1 - dones) * gamma * next_q_values          (float32, in that order)
  * Any other kind fails with MESHENV_E_ARG and a message naming the supported ones.  gamma in [0, 1]; ent_coef is SB3's fixed
  * coefficient, used when meshenv_target_bind gets no log_ent_coef; policy_noise, noise_clip >= 0 (TD3).
  */
@@ -625,9 +629,11 @@ const char *meshenv_target_last_error(const MeshTarget *t);   /* message of the 
  * caller checks dtype, layout and device).  Nothing is read yet.
  *   actor_dev  kind 0: w1 b1 w2 b2 w3 b3 mu_w mu_b log_std_w log_std_b (n_actor 10); kind 1: w1 b1 w2 b2 mu_w mu_b (6)
  *   q1_dev, q2_dev  critic_target.q_networks[0], [1]: kind 0: w1 b1 w2 b2 w3 b3 w4 b4 (n_critic 8); kind 1: 6; w1 is [H][21]
+ *   kind 2: actor_dev w1 b1 w2 b2 mu_w mu_b (n_actor 6; w1 [400][18], w2 [300][400], mu_w [3][300]), q1_dev likewise
+ *       (n_critic 6; w1 [400][21], w4 [1][300]) and q2_dev = NULL (a q2_dev fails with MESHENV_E_ARG)
  *   log_ent_coef_dev  kind 0: SAC's learned log_ent_coef [1] (ent_coef = exp of it: th.exp(self.log_ent_coef.detach())) or NULL
  * SB3's optimisers and polyak_update write in place, so the pointers stay valid; bind again after anything that reallocates.
- * MESHENV_E_ARG for a wrong count, a NULL entry, or log_ent_coef_dev with kind 1.
+ * MESHENV_E_ARG for a wrong count, a NULL entry, or log_ent_coef_dev with kind 1 or 2.
  */
 int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_actor, const float *const *q1_dev,
                         const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev);
@@ -642,7 +648,7 @@ int meshenv_target_refresh(MeshTarget *t);
  * Outputs, each nullable and written only when given: target_dev [n] (needs rewards and dones), next_actions_dev [n][3] (in
  * [-1, 1], what the critics see), next_log_prob_dev [n] (kind 0), q1_dev, q2_dev [n], eps_out_dev [n][3] (needs noise).
  * MESHENV_E_STATE before the first refresh; MESHENV_E_ARG for n < 1, a missing input, noise and sample together,
- * next_log_prob_dev with kind 1, eps_out_dev without noise, or no output.
+ * next_log_prob_dev with kind 1 or 2, q2_dev with kind 2, eps_out_dev without noise, or no output.
  */
 int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, const float *rewards_dev, const float *dones_dev,
                            const float *noise_dev, int sample, uint64_t seed, uint64_t counter, float *target_dev,

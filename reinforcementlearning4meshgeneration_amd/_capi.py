@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h, meshenv_augment.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h, meshenv_augment.h, meshenv_ddpg.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -171,6 +171,9 @@ EXPORTS_AUGMENT = [
 AUGMENT_PHILOX_TAG, AUGMENT_BINS, AUGMENT_TYPES, AUGMENT_MAX_ACTIONS, AUGMENT_UNIFORMS = 5, 11, 3, 20, 57
 AUGMENT_MAX_POOL, AUGMENT_MAX_ROUND, AUGMENT_MAX_ROUNDS, AUGMENT_STATS = 1024, 2 ** 20, 4095, 4
 
+# every symbol include/meshenv_ddpg.h declares: the load of DDPG's [400, 300] actor into a MeshPolicy
+EXPORTS_DDPG = ["meshenv_policy_load_widths"]
+
 
 class MeshKeepEntry(C.Structure):
     """include/meshenv_eval_callback.h MeshKeepEntry: one tensor of a meshenv_keep_best call."""
@@ -302,6 +305,7 @@ def load():
     L.meshenv_actor_forward.argtypes = [vp, C.c_int, vp, vp, vp]
     L.meshenv_actor_sample.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp]
     L.meshenv_policy_load.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 15
+    L.meshenv_policy_load_widths.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 9
     L.meshenv_policy_forward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
     L.meshenv_step_policy_multi.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_uint64, C.c_uint64] + [vp] * 11 + [C.c_int]
     L.meshenv_gae.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
@@ -379,7 +383,7 @@ def load():
         getattr(L, name).restype = C.c_int
     for name in ("meshenv_replay_sample_batches", "meshenv_offpolicy_train_run", "meshenv_target_bind", "meshenv_target_refresh", "meshenv_target_forward", "meshenv_critic_grad_bind",
                  "meshenv_critic_grad_backward", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward", "meshenv_optim_bind",
-                 "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_forward", "meshenv_step_policy_multi",
+                 "meshenv_optim_step", "meshenv_policy_load", "meshenv_policy_load_widths", "meshenv_policy_forward", "meshenv_step_policy_multi",
                  "meshenv_actor_load", "meshenv_actor_forward", "meshenv_actor_sample", "meshenv_td3_actor_grad_bind",
                  "meshenv_td3_actor_grad_backward", "meshenv_ppo_grad_bind", "meshenv_ppo_grad_backward", "meshenv_policy_bind",
                  "meshenv_policy_refresh", "meshenv_rollout_gather", "meshenv_onpolicy_train_run"):

@@ -17,6 +17,7 @@
 #include "../../include/meshenv_fnn.h"
 #include "../../include/meshenv_fnn_train.h"
 #include "../../include/meshenv_augment.h"
+#include "../../include/meshenv_ddpg.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -41,6 +42,7 @@
 #include "meshenv_eval.h"
 #include "meshenv_replay.h"
 #include "meshenv_target.h"
+#include "meshenv_wide.h"
 #include "meshenv_critic_grad.h"
 #include "meshenv_actor_grad.h"
 #include "meshenv_td3_actor_grad.h"
@@ -2073,7 +2075,8 @@ int meshenv_step_actor_multi(MeshEnv *h, MeshActor *a, int T, float *actions_dev
 struct MeshPolicy : HandleBase {
     float *buf = nullptr;  // all weights of the loaded policy, one allocation
     PolicyWeights W{};
-    int kind = -1, hidden = 0, activation = 0;
+    WideNet wide{};        // the [400, 300] policy of meshenv_policy_load_widths (hidden2 != 0); its aux block is W.aux
+    int kind = -1, hidden = 0, hidden2 = 0, activation = 0;
     bool loaded = false;
     PackTable table{};     // meshenv_policy_bind: the live tensors and where meshenv_policy_refresh packs them
     int n_copies = 0;
@@ -2112,6 +2115,41 @@ PackLayout policy_layout(int kind, int H)
     return L;
 }
 
+const char *kWideShapes = "supported: kind 1 (deterministic tanh actor), activation 0 (ReLU), hidden widths (400, 300), 18 inputs, "
+                          "3 actions; meshenv_policy_load takes the uniform widths 64, 128 and 256";
+
+// One [400, 300] network of csrc/meshenv_wide.h over `in` inputs with n_out head columns, in bind order w1 b1 w2 b2 wh bh.
+// Layer 2 has 19 tiles for its 300 neurons and the head 19 K groups for its 300 inputs: the four neurons / inputs past 299
+// have no source and stay zero; the bias blocks are padded to the tile count.
+void wide_tower(PackLayout &L, int in, int n_out)
+{
+    L.matrix(kWideH1, in, kPolInPad / 16, kWideT1); L.vector(kWideH1, kWideH1);
+    L.matrix(kWideH2, kWideH1, kWideG2, kWideT2); L.vector(kWideH2, kWideH2Pad);
+    L.matrix(n_out, kWideH2, kWideGH, 1); L.vector(n_out, 16);
+}
+
+void point(const float *buf, const PackSlot *s, WideNet &N) { point(buf, s, {&N.w1p, &N.b1, &N.w2p, &N.b2, &N.whp, &N.bh}); }
+
+// The [400, 300] policy's buffer: the actor, then the aux block of policy_layout.
+PackLayout wide_policy_layout()
+{
+    PackLayout L;
+    wide_tower(L, kObsDim, 3);
+    L.vector(3, 16);
+    return L;
+}
+
+PackLayout policy_layout(const MeshPolicy *p) { return p->hidden2 ? wide_policy_layout() : policy_layout(p->kind, p->hidden); }
+
+// k_wide_policy / k_wide_target use more dynamic LDS than a launch gets by default when a workgroup has more than 16 rows
+template <typename K>
+void wide_lds_limit(K kernel)
+{
+    if (kWideLdsFloats * sizeof(float) > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(kWideLdsFloats * sizeof(float)));
+}
+
 // One launch of k_policy_forward.  The pi workgroups run when an action output is asked for, the vf workgroups when a value
 // (or a bootstrap terminal value) is.  Arguments are checked by the callers.
 int policy_launch(MeshPolicy *p, const char *fn, const PolicyArgs &A)
@@ -2123,6 +2161,12 @@ int policy_launch(MeshPolicy *p, const char *fn, const PolicyArgs &A)
     a.tower0 = pi ? 0 : 1;
     const dim3 grid((A.n + kPolEnvs - 1) / kPolEnvs, (pi ? 1 : 0) + (vf ? 1 : 0));
     DeviceGuard guard(p->device);
+    if (p->hidden2)
+        return launch(p, guard, fn, [&] {
+            wide_lds_limit(k_wide_policy);
+            hipLaunchKernelGGL(k_wide_policy, dim3((A.n + kWideRows - 1) / kWideRows), dim3(64 * kWideWaves),
+                               kWideLdsFloats * sizeof(float), p->stream, p->wide, p->W.aux, a);
+        });
     return launch(p, guard, fn, [&] {
         hipLaunchKernelGGL(policy_kernel(p->kind, p->hidden, p->activation), grid, dim3(4 * p->hidden), 0, p->stream, p->W, a);
     });
@@ -2188,7 +2232,42 @@ int meshenv_policy_load(MeshPolicy *p, int kind, int hidden, int activation, con
     if (ac) point(p->buf, L.s + 6, {&vf.w1p, &vf.b1, &vf.w2p, &vf.b2, &vf.whp, &vf.bh});
     else vf = pi;   // never read
     p->W.aux = p->buf + o_aux;
-    p->kind = kind; p->hidden = hidden; p->activation = activation;
+    p->kind = kind; p->hidden = hidden; p->hidden2 = 0; p->activation = activation;
+    p->loaded = true;
+    return MESHENV_OK;
+}
+
+int meshenv_policy_load_widths(MeshPolicy *p, int kind, int hidden1, int hidden2, int activation, const float *w1, const float *b1,
+                               const float *w2, const float *b2, const float *head_w, const float *head_b, const float *sigma,
+                               const float *low, const float *high)
+{
+    if (!p) return MESHENV_E_ARG;
+    if (kind != kPolicyDeterministic || activation != kPolicyReLU || hidden1 != kWideH1 || hidden2 != kWideH2)
+        return fail(p, MESHENV_E_ARG, std::string("meshenv_policy_load_widths: unsupported shape; ") + kWideShapes);
+    if (!w1 || !b1 || !w2 || !b2 || !head_w || !head_b || !low || !high)
+        return fail(p, MESHENV_E_ARG, "meshenv_policy_load_widths: null weight pointer");
+    const PackLayout L = wide_policy_layout();
+    const float *src[7] = {w1, b1, w2, b2, head_w, head_b, sigma};   // NULL sigma leaves the slot zero
+    const size_t o_aux = L.s[L.n - 1].off;
+    std::vector<float> h(L.floats, 0.0f);
+    pack_host(L, src, h.data());
+    for (int i = 0; i < 3; i++) {
+        h[o_aux + 3 + i] = low[i];
+        h[o_aux + 6 + i] = high[i];
+    }
+    DeviceGuard guard(p->device);
+    if (guard.err != hipSuccess) return fail(p, MESHENV_E_HIP, "meshenv_policy_load_widths: hipSetDevice failed");
+    (void)hipStreamSynchronize(p->stream);   // the previous weights may still be in use
+    if (p->buf) (void)hipFree(p->buf);
+    p->buf = nullptr;
+    p->loaded = false;
+    p->live = false;
+    if (hipMalloc((void **)&p->buf, h.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(p->buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(p, MESHENV_E_HIP, "meshenv_policy_load_widths: upload failed");
+    point(p->buf, L.s, p->wide);
+    p->W.aux = p->buf + o_aux;
+    p->kind = kind; p->hidden = hidden1; p->hidden2 = hidden2; p->activation = activation;
     p->loaded = true;
     return MESHENV_OK;
 }
@@ -2616,6 +2695,7 @@ struct MeshTarget : HandleBase {
     float gamma = 0.f, ent_coef = 0.f, policy_noise = 0.f, noise_clip = 0.f;
     float *buf = nullptr;      // every packed weight, one allocation, zeroed once
     TargetWeights W{};
+    WideNet wide_actor{}, wide_q{};   // kind 2
     PackTable table{};
     int n_copies = 0;
     bool bound = false, packed = false;
@@ -2624,13 +2704,20 @@ struct MeshTarget : HandleBase {
 namespace {
 
 const char *kTargetKinds = "supported kinds: 0 (SAC: ReLU [128, 128, 128] actor with mu / log_std heads and twin ReLU [128, 128, 128] "
-                           "critics) or 1 (TD3: ReLU [256, 256] tanh actor and twin ReLU [256, 256] critics); 18 observations, 3 actions";
+                           "critics), 1 (TD3: ReLU [256, 256] tanh actor and twin ReLU [256, 256] critics) or 2 (DDPG: ReLU [400, 300] "
+                           "tanh actor and one ReLU [400, 300] critic); 18 observations, 3 actions";
 
 // The target's buffer, in the tensor order of meshenv_target_bind: the towers actor (SAC: mu at column 0 and log_std at column 3
 // of its head tile), q1 and q2, each w1 b1 w2 b2 [w3 b3] wh bh, then log_ent_coef.  Its slot, the last, is there for both
 // kinds; a bind without log_ent_coef stops before it.
 PackLayout target_layout(int kind)
 {
+    if (kind == kTargetDDPG) {   // actor and the one critic (csrc/meshenv_wide.h), six tensors each
+        PackLayout L;
+        wide_tower(L, kObsDim, 3);
+        wide_tower(L, kTgtIn, 1);
+        return L;
+    }
     const bool sac = kind == kTargetSAC;
     const int H = sac ? 128 : 256, NL = sac ? 3 : 2;
     PackLayout L;
@@ -2648,7 +2735,7 @@ int meshenv_target_create(int device, void *stream, int kind, float gamma, float
                           MeshTarget **out)
 {
     std::string refusal;
-    if (kind != kTargetSAC && kind != kTargetTD3) refusal = std::string("unsupported kind; ") + kTargetKinds;
+    if (kind != kTargetSAC && kind != kTargetTD3 && kind != kTargetDDPG) refusal = std::string("unsupported kind; ") + kTargetKinds;
     else if (!(gamma >= 0.0f && gamma <= 1.0f) || !std::isfinite(ent_coef) || !(policy_noise >= 0.0f) || !(noise_clip >= 0.0f) ||
              !std::isfinite(policy_noise) || !std::isfinite(noise_clip))
         refusal = "gamma must lie in [0, 1], ent_coef be finite, policy_noise and noise_clip be finite and >= 0";
@@ -2670,17 +2757,19 @@ int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_acto
                         const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev)
 {
     if (!t) return MESHENV_E_ARG;
-    const bool sac = t->kind == kTargetSAC;
+    const bool sac = t->kind == kTargetSAC, ddpg = t->kind == kTargetDDPG;
     const int NL = sac ? 3 : 2;
     const int want_actor = 2 * NL + (sac ? 4 : 2), want_critic = 2 * NL + 2;
-    if (!actor_dev || !q1_dev || !q2_dev || n_actor != want_actor || n_critic != want_critic)
+    if (ddpg && q2_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: DDPG has one critic (pass q2_dev = NULL)");
+    if (!actor_dev || !q1_dev || (!ddpg && !q2_dev) || n_actor != want_actor || n_critic != want_critic)
         return fail(t, MESHENV_E_ARG, "meshenv_target_bind: kind " + std::to_string(t->kind) + " takes " +
                            std::to_string(want_actor) + " actor and " + std::to_string(want_critic) + " critic tensors; " + kTargetKinds);
     for (int i = 0; i < n_actor; i++)
         if (!actor_dev[i]) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: null actor tensor");
     for (int i = 0; i < n_critic; i++)
-        if (!q1_dev[i] || !q2_dev[i]) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: null critic tensor");
-    if (!sac && log_ent_coef_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: TD3 has no entropy coefficient (pass NULL)");
+        if (!q1_dev[i] || (!ddpg && !q2_dev[i])) return fail(t, MESHENV_E_ARG, "meshenv_target_bind: null critic tensor");
+    if (!sac && log_ent_coef_dev)
+        return fail(t, MESHENV_E_ARG, "meshenv_target_bind: TD3 / DDPG has no entropy coefficient (pass NULL)");
     DeviceGuard guard(t->device);
     if (guard.err != hipSuccess) return fail(t, MESHENV_E_HIP, "meshenv_target_bind: hipSetDevice failed");
     const PackLayout L = target_layout(t->kind);
@@ -2690,9 +2779,16 @@ int meshenv_target_bind(MeshTarget *t, const float *const *actor_dev, int n_acto
     int n = 0;
     for (int i = 0; i < n_actor; i++) src[n++] = actor_dev[i];
     for (int i = 0; i < n_critic; i++) src[n++] = q1_dev[i];
-    for (int i = 0; i < n_critic; i++) src[n++] = q2_dev[i];
+    for (int i = 0; !ddpg && i < n_critic; i++) src[n++] = q2_dev[i];
     if (log_ent_coef_dev) src[n++] = log_ent_coef_dev;
     t->n_copies = pack_table(L, src, n, t->buf, t->table);
+    if (ddpg) {
+        point(t->buf, L.s, t->wide_actor);
+        point(t->buf, L.s + want_actor, t->wide_q);
+        t->bound = true;
+        t->packed = false;
+        return MESHENV_OK;
+    }
     int at = 0;
     for (TargetTower *T : {&t->W.actor, &t->W.q1, &t->W.q2}) {
         T->w3p = T->b3 = nullptr;
@@ -2725,8 +2821,10 @@ int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, cons
     if (noise_dev && sample) return fail(t, MESHENV_E_ARG, "meshenv_target_forward: explicit noise and sample are exclusive");
     if (target_dev && (!rewards_dev || !dones_dev))
         return fail(t, MESHENV_E_ARG, "meshenv_target_forward: target_dev needs rewards_dev and dones_dev");
-    if (t->kind == kTargetTD3 && next_log_prob_dev)
-        return fail(t, MESHENV_E_ARG, "meshenv_target_forward: TD3 has no next_log_prob (pass NULL)");
+    if (t->kind != kTargetSAC && next_log_prob_dev)
+        return fail(t, MESHENV_E_ARG, "meshenv_target_forward: TD3 / DDPG has no next_log_prob (pass NULL)");
+    if (t->kind == kTargetDDPG && q2_dev)
+        return fail(t, MESHENV_E_ARG, "meshenv_target_forward: DDPG has no q2 (pass NULL)");
     if (eps_out_dev && !sample && !noise_dev) return fail(t, MESHENV_E_ARG, "meshenv_target_forward: eps_out_dev without noise");
     if (!target_dev && !next_actions_dev && !next_log_prob_dev && !q1_dev && !q2_dev && !eps_out_dev)
         return fail(t, MESHENV_E_ARG, "meshenv_target_forward: no output requested");
@@ -2738,6 +2836,18 @@ int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, cons
     A.eps_out = eps_out_dev;
     const dim3 grid((n + kTgtRows - 1) / kTgtRows);
     DeviceGuard guard(t->device);
+    if (t->kind == kTargetDDPG) {
+        WideTargetArgs a{};
+        a.n = n; a.next_obs = next_obs_dev; a.rewards = rewards_dev; a.dones = dones_dev; a.noise = noise_dev;
+        a.sample = A.sample; a.seed = seed; a.counter = counter;
+        a.gamma = t->gamma; a.policy_noise = t->policy_noise; a.noise_clip = t->noise_clip;
+        a.target = target_dev; a.next_actions = next_actions_dev; a.q1 = q1_dev; a.eps_out = eps_out_dev;
+        return launch(t, guard, "meshenv_target_forward", [&] {
+            wide_lds_limit(k_wide_target);
+            hipLaunchKernelGGL(k_wide_target, dim3((n + kWideRows - 1) / kWideRows), dim3(64 * kWideWaves),
+                               kWideLdsFloats * sizeof(float), t->stream, t->wide_actor, t->wide_q, a);
+        });
+    }
     return launch(t, guard, "meshenv_target_forward", [&] {
         if (t->kind == kTargetSAC) hipLaunchKernelGGL(k_td_target<kTargetSAC>, grid, dim3(512), 0, t->stream, t->W, A);
         else hipLaunchKernelGGL(k_td_target<kTargetTD3>, grid, dim3(1024), 0, t->stream, t->W, A);
@@ -3241,7 +3351,7 @@ int meshenv_policy_bind(MeshPolicy *p, const float *const *tensors_dev, int n_te
     for (int i = 0; i < want; i++)
         if (!tensors_dev[i]) return fail(p, MESHENV_E_ARG, "meshenv_policy_bind: null tensor");
     static_assert(kPgTensors <= kTgtMaxCopies, "the copy table holds the 13 sources");
-    p->n_copies = pack_table(policy_layout(p->kind, p->hidden), tensors_dev, want, p->buf, p->table);
+    p->n_copies = pack_table(policy_layout(p), tensors_dev, want, p->buf, p->table);
     p->live = true;
     return MESHENV_OK;
 }

@@ -31,7 +31,7 @@
 
 namespace meshenv {
 
-enum { kTargetSAC = 0, kTargetTD3 = 1 };
+enum { kTargetSAC = 0, kTargetTD3 = 1, kTargetDDPG = 2 };   // DDPG: k_wide_target, meshenv_wide.h
 
 constexpr int kTgtRows = 16;      // samples per workgroup = MFMA M
 constexpr int kTgtIn = 21;        // critic inputs: 18 observations ++ 3 actions (padded to kPolInPad = 32)

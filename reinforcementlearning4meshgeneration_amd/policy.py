@@ -1,5 +1,5 @@
-"""Fused PPO / A2C / TD3 policy forward on the GPU (include/meshenv.h: meshenv_policy_*, csrc/meshenv_policy.h): the
-policy side of the rollout loop for the reference's on-policy and deterministic-actor algorithms
+"""Fused PPO / A2C / TD3 / DDPG policy forward on the GPU (include/meshenv.h: meshenv_policy_*, csrc/meshenv_policy.h,
+csrc/meshenv_wide.h): the policy side of the rollout loop for the reference's on-policy and deterministic-actor algorithms
 (rl/baselines/RL_Mesh.py:113-228), so that observation -> action -> step stays on the device.
 
 Two kinds, two hidden layers of width 64, 128 or 256, ReLU or Tanh:
@@ -9,6 +9,11 @@ Two kinds, two hidden layers of width 64, 128 or 256, ReLU or Tanh:
   ``buffer_actions`` (the unclipped Gaussian sample that ``RolloutBuffer`` stores), ``log_prob`` and ``value``;
 * deterministic (SB3 ``TD3Policy``, ``actor.mu``; TD3 [256, 256] ReLU): ``buffer_actions`` = the tanh action in [-1, 1]
   (plus ``NormalActionNoise(0, sigma)``, clipped) that ``ReplayBuffer`` stores, ``actions`` = it rescaled to the Box.
+
+DDPG, which the reference builds as ``DDPG('MlpPolicy', env)``, has SB3's default ``net_arch`` [400, 300] with ReLU: the
+deterministic kind with two widths, a kernel family of its own (csrc/meshenv_wide.h).  It is asked for by name --
+``PolicySpec.ddpg`` / ``FusedPolicy.ddpg``, or ``from_sb3`` of a DDPG model (``actor.mu`` [400, 300] beside ONE [400, 300]
+critic) -- so that ``deterministic(...)`` and ``from_sb3`` of any other object keep refusing what they refused before.
 
 ``PolicySpec`` is the host half (shapes, kind, weights as float32 arrays; no device needed); ``FusedPolicy`` loads one on
 a GPU.  Layers are ``torch.nn.Linear``-like objects (``.weight [out][in]``, ``.bias``)."""
@@ -29,8 +34,11 @@ from .vec_env import ACTION_HIGH, ACTION_LOW
 KIND_ACTOR_CRITIC, KIND_DETERMINISTIC = 0, 1
 ACTIVATIONS = {"relu": 0, "tanh": 1}
 HIDDEN_WIDTHS = (64, 128, 256)
+DDPG_SUPPORTED = ("PolicySpec.ddpg, or from_sb3 of a DDPG model (one [400, 300] critic): DDPG's ReLU [400, 300] tanh actor, Linear(18, 400), "
+                  "Linear(400, 300), Linear(300, 3)")
 SUPPORTED = ("two hidden layers of width 64, 128 or 256 (the same width), ReLU or Tanh, 18 inputs, 3 actions: "
-             "actor-critic (pi and vf towers, action_net [3], value_net [1], log_std [3]) or deterministic (tanh actor)")
+             "actor-critic (pi and vf towers, action_net [3], value_net [1], log_std [3]) or deterministic (tanh actor); or, by "
+             "name, " + DDPG_SUPPORTED)
 
 
 def _np(x, what):
@@ -59,10 +67,15 @@ class PolicySpec:
     weights: Dict[str, Optional[np.ndarray]] = field(default_factory=dict)
     low: np.ndarray = field(default_factory=lambda: ACTION_LOW.copy())
     high: np.ndarray = field(default_factory=lambda: ACTION_HIGH.copy())
+    hidden2: Optional[int] = None      # DDPG's second width (hidden is then the first); None: both layers are `hidden` wide
 
     @property
     def kind_name(self) -> str:
         return "actor_critic" if self.kind == KIND_ACTOR_CRITIC else "deterministic"
+
+    @property
+    def widths(self):
+        return (self.hidden, self.hidden if self.hidden2 is None else self.hidden2)
 
     # ---------------------------------------------------------------- constructors
     @staticmethod
@@ -100,21 +113,44 @@ class PolicySpec:
         H, pi = cls._tower(layers, mu, 3, "actor")
         w = {f"pi_{k}": v for k, v in zip(("w1", "b1", "w2", "b2", "wh", "bh"), pi)}
         w.update({f"vf_{k}": None for k in ("w1", "b1", "w2", "b2", "wh", "bh")})
-        if sigma is not None:
-            s = _np(sigma, "sigma")
-            s = np.broadcast_to(s, (3,)).astype(np.float32).copy() if s.size in (1, 3) else s
-            if s.shape != (3,) or (s < 0).any():
-                raise ValueError(f"sigma must be a non-negative scalar or [3] vector, got {sigma!r}")
-            w["log_std_or_sigma"] = s
-        else:
-            w["log_std_or_sigma"] = None
+        w["log_std_or_sigma"] = cls._sigma(sigma)
         return cls(KIND_DETERMINISTIC, H, _activation(activation), w, _np(low, "low"), _np(high, "high"))
+
+    @staticmethod
+    def _sigma(sigma):
+        """NormalActionNoise's sigma as a [3] float32 vector, or None (no action noise)."""
+        if sigma is None:
+            return None
+        s = _np(sigma, "sigma")
+        s = np.broadcast_to(s, (3,)).astype(np.float32).copy() if s.size in (1, 3) else s
+        if s.shape != (3,) or (s < 0).any():
+            raise ValueError(f"sigma must be a non-negative scalar or [3] vector, got {sigma!r}")
+        return s
+
+    @classmethod
+    def ddpg(cls, layers, mu, sigma=None, low=ACTION_LOW, high=ACTION_HIGH) -> "PolicySpec":
+        """DDPG's actor: ReLU [400, 300], ``layers`` = [Linear(18, 400), Linear(400, 300)], ``mu`` = Linear(300, 3)."""
+        layers = list(layers)
+        what = "actor"
+        if len(layers) != 2:
+            raise ValueError(f"{what}: {len(layers)} hidden layers; supported: {DDPG_SUPPORTED}")
+        t = [_np(layers[0].weight, f"{what}[0].weight"), _np(layers[0].bias, f"{what}[0].bias"),
+             _np(layers[1].weight, f"{what}[1].weight"), _np(layers[1].bias, f"{what}[1].bias"),
+             _np(mu.weight, f"{what} head weight"), _np(mu.bias, f"{what} head bias")]
+        H1, H2 = N.DDPG_WIDTHS
+        if [a.shape for a in t] != [(H1, _capi.OBS_DIM), (H1,), (H2, H1), (H2,), (3, H2), (3,)]:
+            raise ValueError(f"{what}: unsupported shapes {[t[0].shape, t[2].shape, t[4].shape]}; supported: {DDPG_SUPPORTED}")
+        w = {f"pi_{k}": v for k, v in zip(("w1", "b1", "w2", "b2", "wh", "bh"), t)}
+        w.update({f"vf_{k}": None for k in ("w1", "b1", "w2", "b2", "wh", "bh")})
+        w["log_std_or_sigma"] = cls._sigma(sigma)
+        return cls(KIND_DETERMINISTIC, H1, "relu", w, _np(low, "low"), _np(high, "high"), hidden2=H2)
 
     @classmethod
     def from_sb3(cls, policy, sigma=None, low=ACTION_LOW, high=ACTION_HIGH) -> "PolicySpec":
         """Duck-typed on SB3 2.x: ``ActorCriticPolicy`` (mlp_extractor.policy_net / .value_net, action_net, value_net,
         log_std) or ``TD3Policy`` (actor.mu = Sequential(Linear, act, Linear, act, Linear, Tanh)).  An algorithm object
-        (``PPO(...)``) is unwrapped through its ``.policy``.  sigma: TD3's NormalActionNoise sigma (deterministic kind)."""
+        (``PPO(...)``) is unwrapped through its ``.policy``.  sigma: TD3's NormalActionNoise sigma (deterministic kind).
+        A DDPG model (``sb3_nets.is_ddpg``: actor.mu [400, 300] beside one [400, 300] critic) gives ``PolicySpec.ddpg``."""
         if not hasattr(policy, "mlp_extractor") and not hasattr(policy, "actor") and hasattr(policy, "policy"):
             policy = policy.policy
         for attr in ("features_extractor", "pi_features_extractor", "vf_features_extractor"):
@@ -139,11 +175,21 @@ class PolicySpec:
             linears, acts = _sequential(mods[:-1])
             if len(acts) != 1 or len(linears) != 3:
                 raise ValueError(f"actor.mu: {len(linears) - 1} hidden layers, activations {sorted(acts)}; supported: {SUPPORTED}")
+            if N.is_ddpg(policy, "actor", "critic"):
+                if acts != {"relu"}:
+                    raise ValueError(f"actor.mu: activations {sorted(acts)}; supported: {SUPPORTED}")
+                return cls.ddpg(linears[:2], linears[2], sigma=sigma, low=low, high=high)
             return cls.deterministic(linears[:2], linears[2], activation=acts.pop(), sigma=sigma, low=low, high=high)
         raise ValueError("not an SB3 ActorCriticPolicy (mlp_extractor) or TD3Policy (actor.mu)")
 
     def load_args(self):
-        """Host pointers in the order of meshenv_policy_load (the arrays stay referenced by self.weights)."""
+        """Host pointers in the order of meshenv_policy_load (the arrays stay referenced by self.weights); with two widths, of
+        meshenv_policy_load_widths."""
+        if self.hidden2 is not None:
+            w = self.weights
+            ptrs = [w[k].ctypes.data if w.get(k) is not None else None
+                    for k in ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_wh", "pi_bh", "log_std_or_sigma")]
+            return ptrs + [self.low.ctypes.data, self.high.ctypes.data]
         w = self.weights
         order = ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_wh", "pi_bh", "vf_w1", "vf_b1", "vf_w2", "vf_b2", "vf_wh", "vf_bh",
                  "log_std_or_sigma")
@@ -152,14 +198,14 @@ class PolicySpec:
 
 
 def live_deterministic(model):
-    """(hidden, activation, the six live tensors w1 b1 w2 b2 w3 b3) of the LIVE actor of an SB3 TD3 model, TD3Policy or Actor,
-    through ``sb3_nets.td3_live_actor`` (its refusals: a SAC model, no Tanh tail, other widths, non-float32 parameters)."""
+    """(first hidden width, activation, the six live tensors w1 b1 w2 b2 w3 b3) of the LIVE actor of an SB3 TD3 ([256, 256]) or
+    DDPG ([400, 300]) model, TD3Policy or Actor, through ``sb3_nets.td3_live_actor`` (its refusals: a SAC model, no Tanh tail,
+    other widths, non-float32 parameters)."""
     if not hasattr(model, "actor") and hasattr(model, "mu"):
         import types
         model = types.SimpleNamespace(actor=model)
-    layers, mu = N.td3_live_actor(model)
-    params = N.td3_actor_params(layers, mu)
-    return N.HIDDEN[N.KIND_TD3][0], "relu", params
+    widths, params = N.deterministic_live_params(model)
+    return widths[0], "relu", params
 
 
 class FusedPolicy(Handle):
@@ -170,6 +216,11 @@ class FusedPolicy(Handle):
     def __init__(self, spec: PolicySpec, device: int = 0):
         self.spec = spec
         super().__init__(device)
+        if spec.hidden2 is not None:
+            rc = self._L.meshenv_policy_load_widths(self._h, spec.kind, spec.hidden, spec.hidden2, ACTIVATIONS[spec.activation],
+                                                    *spec.load_args())
+            self._check(rc, "meshenv_policy_load_widths")
+            return
         rc = self._L.meshenv_policy_load(self._h, spec.kind, spec.hidden, ACTIVATIONS[spec.activation], *spec.load_args())
         self._check(rc, "meshenv_policy_load")
 
@@ -187,6 +238,10 @@ class FusedPolicy(Handle):
         return cls(PolicySpec.deterministic(layers, mu, activation, sigma, low, high), device)
 
     @classmethod
+    def ddpg(cls, layers, mu, sigma=None, device: int = 0, low=ACTION_LOW, high=ACTION_HIGH):
+        return cls(PolicySpec.ddpg(layers, mu, sigma, low, high), device)
+
+    @classmethod
     def from_sb3(cls, policy, sigma=None, device: int = 0, low=ACTION_LOW, high=ACTION_HIGH):
         return cls(PolicySpec.from_sb3(policy, sigma, low, high), device)
 
@@ -198,14 +253,16 @@ class FusedPolicy(Handle):
         ``policy.optimizer.step()`` has just written.  The shapes and the activation must be the loaded ones and the tensors
         on this device.  Again after anything that reallocates the parameters (``.to()``)."""
         if self.spec.kind != KIND_ACTOR_CRITIC:
-            # the deterministic kind: the live actor of an SB3 TD3 model (``model.actor``, ReLU [256, 256], six tensors); sigma,
-            # low and high stay as loaded
-            H, act, params = live_deterministic(policy)
+            # the deterministic kind: the live actor of an SB3 TD3 or DDPG model (``model.actor``, ReLU [256, 256] or
+            # [400, 300], six tensors); sigma, low and high stay as loaded
+            _, act, params = live_deterministic(policy)
+            widths = (int(params[0].shape[0]), int(params[2].shape[0]))
         else:
             H, act, params = N.actor_critic_live(policy, widths=HIDDEN_WIDTHS)
-        if H != self.spec.hidden or act != self.spec.activation:
-            raise ValueError(f"the live policy is {act} [{H}, {H}]; this FusedPolicy was loaded as {self.spec.activation} "
-                             f"[{self.spec.hidden}, {self.spec.hidden}]")
+            widths = (H, H)
+        if tuple(widths) != self.spec.widths or act != self.spec.activation:
+            raise ValueError(f"the live policy is {act} {list(widths)}; this FusedPolicy was loaded as {self.spec.activation} "
+                             f"{list(self.spec.widths)}")
         N.check_device(params, self.device, "FusedPolicy.bind_live")
         rc = self._L.meshenv_policy_bind(self._h, self._ptrs(params), len(params))
         self._check(rc, "meshenv_policy_bind")

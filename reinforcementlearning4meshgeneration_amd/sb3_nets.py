@@ -7,13 +7,16 @@ from __future__ import annotations
 
 from . import _capi
 
-KIND_SAC, KIND_TD3 = 0, 1
+KIND_SAC, KIND_TD3, KIND_DDPG = 0, 1, 2
 OBS_DIM, ACT_DIM = _capi.OBS_DIM, _capi.ACT_DIM
 Q_IN = OBS_DIM + ACT_DIM
 HIDDEN = {KIND_SAC: (128, 3), KIND_TD3: (256, 2)}     # width, hidden layers
 SUPPORTED = ("SAC: ReLU [128, 128, 128] actor (mu and log_std heads) with twin ReLU [128, 128, 128] critics and either the "
              "learned log_ent_coef tensor or a fixed ent_coef; TD3: ReLU [256, 256] tanh actor with twin ReLU [256, 256] "
-             "critics; 18 observations, 3 actions, critic input cat(obs, action) = 21; float32 contiguous parameters")
+             "critics; DDPG (the forward classes FusedPolicy and FusedTDTarget only): ReLU [400, 300] tanh actor with one ReLU "
+             "[400, 300] critic (n_critics = 1); 18 observations, 3 actions, critic input cat(obs, action) = 21; float32 "
+             "contiguous parameters")
+DDPG_WIDTHS = (400, 300)                              # SB3's TD3Policy default net_arch, what DDPG('MlpPolicy', env) builds
 
 
 def _refuse(what):
@@ -56,6 +59,55 @@ def _mlp(layers, head_layers, n_in, kind, what):
     for name, n_out, l in head_layers:
         out += [_param(l.weight, f"{what} {name}.weight", (n_out, H)), _param(l.bias, f"{what} {name}.bias", (n_out,))]
     return out
+
+
+def _widths(layers):
+    """The output widths of Linear-like layers (None where a weight has no shape)."""
+    return [(tuple(getattr(getattr(l, "weight", None), "shape", ())) or (None,))[0] for l in layers]
+
+
+def ddpg_mlp(layers, head, n_in, n_out, what):
+    """[w1, b1, w2, b2, head_w, head_b] of a [400, 300] MLP: DDPG's actor (18 -> 3) or critic (21 -> 1)."""
+    layers = list(layers)
+    if tuple(_widths(layers)) != DDPG_WIDTHS:
+        _refuse(f"{what}: hidden layers {_widths(layers)}")
+    H1, H2 = DDPG_WIDTHS
+    return [_param(layers[0].weight, f"{what}[0].weight", (H1, n_in)), _param(layers[0].bias, f"{what}[0].bias", (H1,)),
+            _param(layers[1].weight, f"{what}[1].weight", (H2, H1)), _param(layers[1].bias, f"{what}[1].bias", (H2,)),
+            _param(head.weight, f"{what} output.weight", (n_out, H2)), _param(head.bias, f"{what} output.bias", (n_out,))]
+
+
+def ddpg_actor_params(actor_layers, mu):
+    """The six tensors of DDPG's actor in bind order: w1 b1 w2 b2 mu_w mu_b."""
+    return ddpg_mlp(actor_layers, mu, OBS_DIM, ACT_DIM, "actor")
+
+
+def ddpg_critic_params(q, what="q_networks[0]"):
+    """The six tensors of DDPG's one q_network (an nn.Sequential(Linear, ReLU, Linear, ReLU, Linear) or its Linear layers)."""
+    linears = _relu_linears(q, what, 2)
+    return ddpg_mlp(linears[:-1], linears[-1], Q_IN, 1, what)
+
+
+def is_ddpg(model, actor_attr="actor_target", critic_attr="critic_target") -> bool:
+    """Whether ``model`` is a DDPG model as SB3 constructs it: ``<actor_attr>.mu`` and ONE q_network (``n_critics == 1``), both
+    of hidden widths [400, 300] (the activations are judged where the layers are read).  Every other single-critic model (a
+    TD3 or SAC model built with n_critics = 1 at its own widths) is not, and meets twin_critics' refusal."""
+    actor, critic = getattr(model, actor_attr, None), getattr(model, critic_attr, None)
+    if not hasattr(actor, "mu") or critic is None or not hasattr(critic, "q_networks"):
+        return False
+    qs = list(critic.q_networks)
+    if int(getattr(critic, "n_critics", len(qs))) != 1 or len(qs) != 1:
+        return False
+    mu = [m for m in actor.mu if type(m).__name__ == "Linear"]
+    q = [m for m in qs[0] if type(m).__name__ == "Linear"]
+    return tuple(_widths(mu[:-1])) == DDPG_WIDTHS and tuple(_widths(q[:-1])) == DDPG_WIDTHS
+
+
+def ddpg_target_nets(model):
+    """(actor_target's hidden layers, its mu, critic_target.q_networks[0]) of a model is_ddpg() took."""
+    _flatten_only(model.critic_target, "critic_target", shared=bool(getattr(model.critic_target, "share_features_extractor", False)))
+    layers, mu = td3_actor(model.actor_target)
+    return layers, mu, list(model.critic_target.q_networks)[0]
 
 
 def _relu_linears(seq, what, at_least=0):
@@ -140,6 +192,15 @@ def td3_live_actor(model):
     if tail != "Tanh":
         _refuse(f"actor.mu ends in {tail}; SB3's TD3 actor ends in Tanh")
     return td3_actor(actor, "actor")
+
+
+def deterministic_live_params(model):
+    """((width 1, width 2), the six live tensors) of the live actor of a TD3 ([256, 256]) or DDPG ([400, 300]) model."""
+    layers, mu = td3_live_actor(model)
+    if tuple(_widths(layers)) == DDPG_WIDTHS:
+        return DDPG_WIDTHS, ddpg_actor_params(layers, mu)
+    H = HIDDEN[KIND_TD3][0]
+    return (H, H), td3_actor_params(layers, mu)
 
 
 def td3_actor_params(actor_layers, mu):

@@ -1,11 +1,14 @@
-"""TD targets of SAC and TD3 on the GPU (include/meshenv.h: meshenv_target_*, csrc/meshenv_target.h): the
+"""TD targets of SAC, TD3 and DDPG on the GPU (include/meshenv.h: meshenv_target_*, csrc/meshenv_target.h, csrc/meshenv_wide.h): the
 ``with th.no_grad():`` block of SB3 2.x's ``SAC.train`` / ``TD3.train`` that turns a sampled batch into ``target_q_values``,
 one launch from the tensors ``DeviceReplayBuffer.sample`` returns.
 
-Two kinds, the networks the reference trains (rl/baselines/RL_Mesh.py:179-222):
+Three kinds, the networks the reference trains (rl/baselines/RL_Mesh.py:113-228):
 
 * SAC: actor ReLU [128, 128, 128] with ``mu`` / ``log_std`` heads, twin critics ReLU [128, 128, 128];
-* TD3: ``actor_target`` ReLU [256, 256] + tanh, twin critics ReLU [256, 256].
+* TD3: ``actor_target`` ReLU [256, 256] + tanh, twin critics ReLU [256, 256];
+* DDPG (``DDPG('MlpPolicy', env)``: SB3's defaults): ``actor_target`` ReLU [400, 300] + tanh, ONE critic ReLU [400, 300];
+  ``TD3.train``'s block with ``n_critics = 1``, so no twin minimum and no ``q2``.  SB3's DDPG sets
+  ``target_policy_noise = 0.1`` and ``target_noise_clip = 0.0``: the smoothing noise is clipped to +-0.
 
 The weights are the LIVE torch parameters on the device: ``FusedTDTarget`` records their pointers once and ``refresh()``
 copies them into the kernel's layout in one launch on the current stream (no host copy, no synchronisation), so a training
@@ -20,7 +23,7 @@ from typing import List, Optional
 
 from . import sb3_nets as N
 from ._handle import Handle
-from .sb3_nets import ACT_DIM, HIDDEN, KIND_SAC, KIND_TD3, OBS_DIM, SUPPORTED  # noqa: F401  (part of this module's interface)
+from .sb3_nets import ACT_DIM, HIDDEN, KIND_DDPG, KIND_SAC, KIND_TD3, OBS_DIM, SUPPORTED  # noqa: F401  (part of this module's interface)
 
 
 @dataclass
@@ -37,11 +40,12 @@ class TDTargetSpec:
 
     @property
     def kind_name(self) -> str:
-        return "sac" if self.kind == KIND_SAC else "td3"
+        return {KIND_SAC: "sac", KIND_TD3: "td3", KIND_DDPG: "ddpg"}[self.kind]
 
     @property
     def hidden(self) -> int:
-        return HIDDEN[self.kind][0]
+        """The hidden width (DDPG: the first of its two, sb3_nets.DDPG_WIDTHS)."""
+        return N.DDPG_WIDTHS[0] if self.kind == KIND_DDPG else HIDDEN[self.kind][0]
 
     def tensors(self):
         return list(self.actor) + list(self.q1) + list(self.q2) + ([self.log_ent_coef] if self.log_ent_coef is not None else [])
@@ -62,19 +66,35 @@ class TDTargetSpec:
 
     @classmethod
     def td3(cls, actor_layers, mu, q1, q2, gamma, policy_noise=0.2, noise_clip=0.5) -> "TDTargetSpec":
+        pn, nc = cls._noise(policy_noise, noise_clip)
+        actor = N._mlp(actor_layers, [("mu", ACT_DIM, mu)], OBS_DIM, KIND_TD3, "actor")
+        return cls(KIND_TD3, cls._gamma(gamma), actor, *N.twin_params(KIND_TD3, q1, q2), policy_noise=pn, noise_clip=nc)
+
+    @staticmethod
+    def _noise(policy_noise, noise_clip):
         pn, nc = float(policy_noise), float(noise_clip)
         if not (0.0 <= pn < float("inf")) or not (0.0 <= nc < float("inf")):
             raise ValueError(f"policy_noise and noise_clip must be finite and >= 0, got {policy_noise!r}, {noise_clip!r}")
-        actor = N._mlp(actor_layers, [("mu", ACT_DIM, mu)], OBS_DIM, KIND_TD3, "actor")
-        return cls(KIND_TD3, cls._gamma(gamma), actor, *N.twin_params(KIND_TD3, q1, q2), policy_noise=pn, noise_clip=nc)
+        return pn, nc
+
+    @classmethod
+    def ddpg(cls, actor_layers, mu, q1, gamma, policy_noise=0.1, noise_clip=0.0) -> "TDTargetSpec":
+        """actor_target's two hidden layers and mu, critic_target.q_networks[0]; the defaults are what SB3's DDPG passes."""
+        pn, nc = cls._noise(policy_noise, noise_clip)
+        return cls(KIND_DDPG, cls._gamma(gamma), N.ddpg_actor_params(actor_layers, mu), N.ddpg_critic_params(q1), [],
+                   policy_noise=pn, noise_clip=nc)
 
     @classmethod
     def from_sb3(cls, model) -> "TDTargetSpec":
         """Duck-typed on SB3 2.x's SAC (``actor.latent_pi / .mu / .log_std``, ``critic_target.q_networks``, ``gamma``,
         ``log_ent_coef`` or ``ent_coef_tensor``) and TD3 (``actor_target.mu``, ``critic_target.q_networks``, ``gamma``,
-        ``target_policy_noise``, ``target_noise_clip``)."""
+        ``target_policy_noise``, ``target_noise_clip``); DDPG is TD3's layout with ``critic_target.n_critics == 1`` and the
+        widths [400, 300] on both networks (``sb3_nets.is_ddpg``) -- every other single-critic model is refused."""
         is_sac = hasattr(getattr(model, "actor", None), "latent_pi")
         is_td3 = not is_sac and hasattr(getattr(model, "actor_target", None), "mu")
+        if is_td3 and N.is_ddpg(model):
+            layers, mu, q = N.ddpg_target_nets(model)
+            return cls.ddpg(layers, mu, q, model.gamma, model.target_policy_noise, model.target_noise_clip)
         qs = N.twin_critics(model, "critic_target", ddpg=is_td3)
         if is_sac:
             actor = model.actor
@@ -113,6 +133,10 @@ class FusedTDTarget(Handle):
         return cls(TDTargetSpec.td3(actor_layers, mu, q1, q2, gamma, policy_noise, noise_clip), device)
 
     @classmethod
+    def ddpg(cls, actor_layers, mu, q1, gamma, policy_noise=0.1, noise_clip=0.0, device: int = 0):
+        return cls(TDTargetSpec.ddpg(actor_layers, mu, q1, gamma, policy_noise, noise_clip), device)
+
+    @classmethod
     def from_sb3(cls, model, device: int = 0):
         return cls(TDTargetSpec.from_sb3(model), device)
 
@@ -123,7 +147,7 @@ class FusedTDTarget(Handle):
         s.check_device(self.device)
         arr = self._ptrs
         lec = s.log_ent_coef.data_ptr() if s.log_ent_coef is not None else None
-        rc = self._L.meshenv_target_bind(self._h, arr(s.actor), len(s.actor), arr(s.q1), arr(s.q2), len(s.q1), lec)
+        rc = self._L.meshenv_target_bind(self._h, arr(s.actor), len(s.actor), arr(s.q1), arr(s.q2) if s.q2 else None, len(s.q1), lec)
         self._check(rc, "meshenv_target_bind")
 
     def refresh(self) -> None:
@@ -138,7 +162,7 @@ class FusedTDTarget(Handle):
         """target_q_values [B, 1] of a batch: ``samples`` (a ReplayBufferSamples: next_observations, rewards, dones are
         read) or the three tensors by keyword.  eps is ``noise`` ([B, 3] of N(0, 1) draws), drawn in the kernel when ``seed``
         is given (Philox4x32-10 at (seed, counter, sample index), a stream of its own: pass a fresh counter every batch), or
-        0 with neither.  return_parts: also a dict of next_actions [B, 3] (in [-1, 1]), next_log_prob [B] (SAC), q1, q2 [B]
+        0 with neither.  return_parts: also a dict of next_actions [B, 3] (in [-1, 1]), next_log_prob [B] (SAC), q1, q2 [B] (DDPG: q1)
         and, with noise, eps [B, 3]; target(noise=parts["eps"]) reproduces a sampled call bit for bit."""
         t = self._torch
         if samples is not None:
@@ -161,7 +185,9 @@ class FusedTDTarget(Handle):
         y = t.empty((B, 1), **f32)
         parts = {}
         if return_parts:
-            parts = dict(next_actions=t.empty((B, ACT_DIM), **f32), q1=t.empty(B, **f32), q2=t.empty(B, **f32))
+            parts = dict(next_actions=t.empty((B, ACT_DIM), **f32), q1=t.empty(B, **f32))
+            if self.spec.kind != KIND_DDPG:
+                parts["q2"] = t.empty(B, **f32)
             if self.spec.kind == KIND_SAC:
                 parts["next_log_prob"] = t.empty(B, **f32)
             if noise is not None or seed is not None:

@@ -1,0 +1,179 @@
+"""CPU (-m "not gpu"): DDPG's forward half without a device.
+
+* The recogniser (sb3_nets.py) takes the DDPG stand-in of tests/ddpg_ref.py -- a PolicySpec of the deterministic kind at
+  400 / 300 and a TDTargetSpec of the DDPG kind, tensors in bind order -- keeps giving TD3 for rl_stubs.td3_model(), and refuses
+  every other single-critic or [400, 300]-ish model with a message naming the supported shapes.
+* The fp64 restatements of tests/ddpg_ref.py have teeth: their bound admits fp32 forwards summed in other orders (numpy float32,
+  one k at a time and pairwise) on policy_ref.input_rows(), and rejects each deliberate kernel mistake on at least one element."""
+import numpy as np
+import pytest
+import torch
+
+import ddpg_ref as D
+import policy_ref as R
+import rl_stubs
+import td_target_ref as T
+from reinforcementlearning4meshgeneration_amd import _capi
+from reinforcementlearning4meshgeneration_amd import sb3_nets as N
+from reinforcementlearning4meshgeneration_amd.policy import KIND_DETERMINISTIC, FusedPolicy, PolicySpec
+from reinforcementlearning4meshgeneration_amd.td_target import TDTargetSpec
+
+SEQ_ROWS = 600             # rows of the (slow) one-k-at-a-time forward
+
+
+@pytest.fixture(scope="module")
+def rows():
+    x = R.input_rows()
+    return x, R.noise_rows(len(x))
+
+
+# ------------------------------------------------------------------------------------------------------------ recogniser
+def test_the_stand_in_gives_a_policy_spec():
+    m = D.ddpg_model()
+    spec = PolicySpec.from_sb3(m, sigma=0.1)
+    assert (spec.kind, spec.kind_name, spec.hidden, spec.hidden2, spec.widths, spec.activation) == \
+        (KIND_DETERMINISTIC, "deterministic", 400, 300, (400, 300), "relu")
+    mu = m.actor.mu
+    for key, t in zip(("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_wh", "pi_bh"),
+                      (mu[0].weight, mu[0].bias, mu[2].weight, mu[2].bias, mu[4].weight, mu[4].bias)):
+        assert np.array_equal(spec.weights[key], t.detach().numpy()) and spec.weights[key].dtype == np.float32
+    assert np.allclose(spec.weights["log_std_or_sigma"], 0.1)
+    args = spec.load_args()                                     # meshenv_policy_load_widths: six tensors, sigma, low, high
+    assert len(args) == 9 and all(a is not None for a in args)
+    assert PolicySpec.from_sb3(m).load_args()[6] is None        # no action noise
+    lin = [mu[0], mu[2]]
+    by_name = PolicySpec.ddpg(lin, mu[4], sigma=0.1)
+    assert by_name.widths == (400, 300) and np.array_equal(by_name.weights["pi_w2"], spec.weights["pi_w2"])
+    # the existing kinds keep their meaning of `hidden`
+    td3 = PolicySpec.from_sb3(rl_stubs.td3_model())
+    assert (td3.hidden, td3.hidden2, td3.widths) == (256, None, (256, 256)) and len(td3.load_args()) == 15
+
+
+def test_the_stand_in_gives_a_td_target_spec():
+    m = D.ddpg_model()
+    spec = TDTargetSpec.from_sb3(m)
+    assert (spec.kind, spec.kind_name, spec.hidden) == (N.KIND_DDPG, "ddpg", 400)
+    assert (spec.gamma, spec.policy_noise, spec.noise_clip) == (0.99, 0.1, 0.0)
+    assert [tuple(t.shape) for t in spec.actor] == [(400, 18), (400,), (300, 400), (300,), (3, 300), (3,)]
+    assert [tuple(t.shape) for t in spec.q1] == [(400, 21), (400,), (300, 400), (300,), (1, 300), (1,)]
+    assert spec.q2 == [] and spec.log_ent_coef is None and len(spec.tensors()) == 12
+    mu, q = m.actor_target.mu, m.critic_target.q_networks[0]      # the TARGET networks, the live tensors themselves
+    assert spec.actor[0] is mu[0].weight and spec.actor[3] is mu[2].bias and spec.actor[4] is mu[4].weight
+    assert spec.q1[0] is q[0].weight and spec.q1[5] is q[4].bias
+    by_name = TDTargetSpec.ddpg([mu[0], mu[2]], mu[4], q, 0.99, policy_noise=0.2, noise_clip=0.5)
+    assert by_name.kind_name == "ddpg" and (by_name.policy_noise, by_name.noise_clip) == (0.2, 0.5) and by_name.q1[2] is q[2].weight
+    with pytest.raises(ValueError, match="policy_noise and noise_clip"):
+        TDTargetSpec.ddpg([mu[0], mu[2]], mu[4], q, 0.99, policy_noise=-1.0)
+    with pytest.raises(ValueError, match="is on cpu; FusedTDTarget binds"):
+        spec.check_device(torch.device("cuda", 0))
+
+
+def test_td3_stays_td3():
+    assert TDTargetSpec.from_sb3(rl_stubs.td3_model()).kind_name == "td3"
+    assert TDTargetSpec.from_sb3(rl_stubs.sac_model()).kind_name == "sac"
+    assert not N.is_ddpg(rl_stubs.td3_model()) and not N.is_ddpg(rl_stubs.td3_model(n_critics=1)) and N.is_ddpg(D.ddpg_model())
+
+
+REFUSED = [
+    ("td3_one_critic", lambda: rl_stubs.td3_model(n_critics=1), "n_critics = 1"),
+    ("sac_one_critic", lambda: rl_stubs.sac_model(n_critics=1), "n_critics = 1"),
+    ("widths_300_400", lambda: D.ddpg_model(widths=(300, 400)), "n_critics = 1"),
+    ("widths_400_400", lambda: D.ddpg_model(widths=(400, 400)), "n_critics = 1"),
+    ("three_hidden_layers", lambda: D.ddpg_model(widths=(400, 300, 300)), "n_critics = 1"),
+    ("tanh_hidden", lambda: D.ddpg_model(act=torch.nn.Tanh), "activations ['tanh']"),
+    ("two_critics_at_400_300", lambda: D.ddpg_model(n_critics=2), "hidden layers [400, 300]"),
+    ("actor_400_300_critic_256_256", lambda: D.ddpg_model(critic_widths=(256, 256)), "n_critics = 1"),
+]
+
+
+@pytest.mark.parametrize("name, make, names", REFUSED, ids=[r[0] for r in REFUSED])
+def test_every_other_model_is_refused_naming_the_supported_shapes(name, make, names):
+    with pytest.raises(ValueError) as e:
+        TDTargetSpec.from_sb3(make())
+    text = str(e.value)
+    assert names in text and N.SUPPORTED in text and "[400, 300]" in N.SUPPORTED and "[256, 256]" in N.SUPPORTED, text
+    if name.endswith("one_critic"):
+        return                                                   # (their actors are TD3's / SAC's own)
+    with pytest.raises(ValueError) as e:                         # the policy side refuses the same models
+        PolicySpec.from_sb3(make())
+    assert "[400, 300]" in str(e.value) and "64, 128 or 256" in str(e.value), str(e.value)
+
+
+def test_the_gradient_and_train_classes_keep_refusing_ddpg():
+    from reinforcementlearning4meshgeneration_amd.critic_grad import CriticGradSpec
+    from reinforcementlearning4meshgeneration_amd.td3_actor_grad import TD3ActorGradSpec
+    with pytest.raises(ValueError, match=r"n_critics = 1 \(DDPG: one critic, no twin minimum\)"):
+        CriticGradSpec.from_sb3(D.ddpg_model())
+    with pytest.raises(ValueError, match=r"hidden layers \[400, 300\]"):
+        TD3ActorGradSpec.from_sb3(D.ddpg_model())
+
+
+def test_bind_live_checks_the_widths_without_a_device():
+    ddpg, td3 = D.ddpg_model(), rl_stubs.td3_model()
+    for loaded, live, text in ((ddpg, td3, r"live policy is relu \[256, 256\].*loaded as relu \[400, 300\]"),
+                               (td3, ddpg, r"live policy is relu \[400, 300\].*loaded as relu \[256, 256\]")):
+        fp = FusedPolicy.__new__(FusedPolicy)                    # no device: the checks in front of the C call
+        fp.spec = PolicySpec.from_sb3(loaded, sigma=0.1)
+        fp.device = "cuda:0"
+        with pytest.raises(ValueError, match=text):
+            fp.bind_live(live)
+        with pytest.raises(ValueError, match=r"is on cpu; FusedPolicy.bind_live binds"):
+            fp.bind_live(loaded)
+
+
+def test_entry_point_is_declared_and_bound():
+    import os
+    import re
+    assert _capi.EXPORTS_DDPG == ["meshenv_policy_load_widths"]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "meshenv_ddpg.h")).read()
+    assert re.findall(r"^int (meshenv_\w+)\(", text, flags=re.M) == _capi.EXPORTS_DDPG and "rl/baselines/RL_Mesh.py" in text
+    L = _capi.load()
+    assert L.meshenv_policy_load_widths.restype is _capi.C.c_int and len(L.meshenv_policy_load_widths.argtypes) == 14
+
+
+# ------------------------------------------------------------------------------------------------------------ the bound
+def test_m_is_the_longest_path_of_the_kernels_order():
+    for m, k_pad in zip(D.M_LAYER, D.K_PAD):
+        groups = k_pad // 16
+        assert m == 4 * -(-groups // 2) + 1 + 1 and m <= k_pad + 2
+
+
+@pytest.mark.parametrize("head_scale", [1.0, 6.0])
+def test_bounds_admit_other_fp32_orders(head_scale, rows):
+    obs, eps = rows
+    m = D.ddpg_model(head_scale=head_scale)
+    actor, actor_t, critic = D.actor_layers(m), D.actor_layers(m, target=True), D.critic_layers(m)
+    rew, done = T.batch_rows(len(obs), reward_scale=1e3 if head_scale > 1 else 1.0)
+    worst = {}
+    for name, linear, n in (("pairwise", D.pair_linear, len(obs)), ("sequential", D.seq_linear, SEQ_ROWS)):
+        x, e = obs[:n], eps[:n]
+        for noise in (None, e):
+            D.assert_all_within(D.policy_f32(actor, x, noise, linear), D.policy_forward(actor, x, noise), f"{name} policy", worst)
+        for pn, nc in ((0.1, 0.0), (0.2, 0.5)):
+            got = D.target_f32(actor_t, critic, x, rew[:n], done[:n], e, linear, policy_noise=pn, noise_clip=nc)
+            ref = D.target(actor_t, critic, x, rew[:n], done[:n], e, policy_noise=pn, noise_clip=nc)
+            D.assert_all_within(got, ref, f"{name} target {pn} {nc}", worst)
+    print(f"\nddpg head x{head_scale}: other fp32 orders, max |fp32 - fp64| / bound:", {k: round(v, 4) for k, v in worst.items()})
+    assert 0 < max(worst.values()) < 1
+
+
+def _caught(ref, mut, keys):
+    return [k for k in keys if R.ratio(mut[k][0], ref[k])[1].any()]
+
+
+def test_bounds_reject_mutants(rows):
+    obs, eps = rows
+    m = D.ddpg_model()
+    actor, actor_t, critic = D.actor_layers(m), D.actor_layers(m, target=True), D.critic_layers(m)
+    rew, done = T.batch_rows(len(obs))
+    assert done.any()
+    pol = D.policy_forward(actor, obs, eps)
+    tgt = D.target(actor_t, critic, obs, rew, done, eps)                     # DDPG's constants: the noise is clipped to +-0
+    for mutant in D.NET_MUTANTS:
+        assert _caught(pol, D.policy_forward(actor, obs, eps, mutant=mutant), ["buffer_actions", "actions"]), f"policy: {mutant}"
+        assert _caught(tgt, D.target(actor_t, critic, obs, rew, done, eps, mutant=mutant), ["target", "q1"]), f"target: {mutant}"
+    for mutant in D.TARGET_MUTANTS:
+        keys = ["target"] if mutant == "drop_not_done" else ["target", "q1", "next_actions"]
+        assert _caught(tgt, D.target(actor_t, critic, obs, rew, done, eps, mutant=mutant), keys), f"target: {mutant}"
+    assert np.array_equal(tgt["next_actions"][0], D.target(actor_t, critic, obs, rew, done, None)["next_actions"][0])
