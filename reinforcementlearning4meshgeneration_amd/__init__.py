@@ -13,7 +13,7 @@ __all__ = ["MeshVecEnv", "SB3MeshVecEnv", "BoudaryEnv", "boundary", "read_polygo
            "TrainLogs", "FusedOffPolicyTrain", "OffPolicyTrainSpec", "OffPolicyTrainLogs", "FusedOffPolicyLearn",
            "OffPolicyLearnSpec", "OffPolicyLearnLogs", "EpisodeStats", "DeviceEvalCallback", "FusedOnPolicyLearn",
            "OnPolicyLearnSpec", "OnPolicyLearnLogs", "StepCounter", "FusedFNN", "FNNSpec", "FNNMeshResult",
-           "FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog", "DeviceMeshAugmentation", "AugmentScore"]
+           "FusedFNNTrain", "FNNTrainSpec", "FNNTrainLog", "DeviceMeshAugmentation", "AugmentScore", "FusedDDPGGrad", "DDPGGradSpec"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an environment is built
@@ -83,6 +83,9 @@ def __getattr__(name):  # torch / the HIP library are only needed once an enviro
     if name in ("DeviceMeshAugmentation", "AugmentScore"):
         from . import augmentation
         return getattr(augmentation, name)
+    if name in ("FusedDDPGGrad", "DDPGGradSpec"):
+        from . import ddpg_grad
+        return getattr(ddpg_grad, name)
     if name == "DeviceEvalCallback":
         from .eval_callback import DeviceEvalCallback
         return DeviceEvalCallback

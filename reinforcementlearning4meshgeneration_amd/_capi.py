@@ -1,5 +1,5 @@
 """ctypes binding of libmeshenv_hip.so (include/meshenv.h, meshenv_optim.h, meshenv_td3_actor_grad.h,
-meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h, meshenv_augment.h, meshenv_ddpg.h).  Fails loudly when the library is missing:
+meshenv_ppo_grad.h, meshenv_rollout.h, meshenv_onpolicy_train.h, meshenv_onpolicy_learn.h, meshenv_offpolicy_train.h, meshenv_offpolicy_learn.h, meshenv_eval_callback.h, meshenv_topology.h, meshenv_fnn.h, meshenv_fnn_train.h, meshenv_augment.h, meshenv_ddpg.h, meshenv_ddpg_grad.h).  Fails loudly when the library is missing:
 there is no CPU fallback anywhere in this package."""
 from __future__ import annotations
 
@@ -174,6 +174,13 @@ AUGMENT_MAX_POOL, AUGMENT_MAX_ROUND, AUGMENT_MAX_ROUNDS, AUGMENT_STATS = 1024, 2
 # every symbol include/meshenv_ddpg.h declares: the load of DDPG's [400, 300] actor into a MeshPolicy
 EXPORTS_DDPG = ["meshenv_policy_load_widths"]
 
+# every symbol include/meshenv_ddpg_grad.h declares: DDPG's two gradient statements at [400, 300]
+EXPORTS_DDPG_GRAD = [
+    "meshenv_ddpg_grad_create", "meshenv_ddpg_grad_destroy", "meshenv_ddpg_grad_set_stream", "meshenv_ddpg_grad_last_error",
+    "meshenv_ddpg_grad_bind", "meshenv_ddpg_grad_critic_backward", "meshenv_ddpg_grad_actor_backward",
+]
+DDPG_GRAD_ACTOR_FLOATS, DDPG_GRAD_CRITIC_FLOATS, DDPG_GRAD_MAX_ROWS = 128832, 129408, 65536
+
 
 class MeshKeepEntry(C.Structure):
     """include/meshenv_eval_callback.h MeshKeepEntry: one tensor of a meshenv_keep_best call."""
@@ -294,7 +301,7 @@ def load():
                                           ("meshenv_offpolicy_train", [], True),
                                           ("meshenv_episode_stats", [], True), ("meshenv_eval_callback", [], True),
                                           ("meshenv_fnn", [], True), ("meshenv_fnn_grad", [], True),
-                                          ("meshenv_augment", [], True)):
+                                          ("meshenv_augment", [], True), ("meshenv_ddpg_grad", [f32], True)):
         fn = lambda name: getattr(L, f"{prefix}_{name}")   # noqa: E731
         fn("create").argtypes, fn("create").restype = [C.c_int, vp] + extra + [C.POINTER(vp)], C.c_int
         fn("destroy").argtypes, fn("destroy").restype = [vp], None
@@ -332,6 +339,10 @@ def load():
     L.meshenv_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.meshenv_td3_actor_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int64]
     L.meshenv_td3_actor_grad_backward.argtypes = [vp, C.c_int, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    L.meshenv_ddpg_grad_bind.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int64]
+    L.meshenv_ddpg_grad_critic_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
+    L.meshenv_ddpg_grad_actor_backward.argtypes = [vp, C.c_int, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    L.meshenv_ddpg_grad_bind.restype = L.meshenv_ddpg_grad_critic_backward.restype = L.meshenv_ddpg_grad_actor_backward.restype = C.c_int
     L.meshenv_ppo_grad_bind.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int64]
     L.meshenv_ppo_grad_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_double, f32, f32, C.c_int, C.c_int, f32, vp,
                                             C.POINTER(vp), C.POINTER(vp)]

@@ -15,7 +15,7 @@ ARCH = "gfx950"
 PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h", "meshenv_td3_actor_grad.h", "meshenv_ppo_grad.h", "meshenv_rollout.h",
                   "meshenv_onpolicy_train.h", "meshenv_offpolicy_train.h", "meshenv_offpolicy_learn.h",
                   "meshenv_eval_callback.h", "meshenv_onpolicy_learn.h", "meshenv_topology.h", "meshenv_fnn.h", "meshenv_fnn_train.h",
-                  "meshenv_augment.h", "meshenv_ddpg.h"]     # include/: the C-ABI the translation unit implements
+                  "meshenv_augment.h", "meshenv_ddpg.h", "meshenv_ddpg_grad.h"]     # include/: the C-ABI the translation unit implements
 
 # -ffp-contract=off: the reference is CPython float arithmetic, which never fuses a*b+c.
 # -fhip-fp32-correctly-rounded-divide-sqrt: numpy's float32 round() divides in IEEE float32.

@@ -18,6 +18,7 @@
 #include "../../include/meshenv_fnn_train.h"
 #include "../../include/meshenv_augment.h"
 #include "../../include/meshenv_ddpg.h"
+#include "../../include/meshenv_ddpg_grad.h"
 
 #include <hip/hip_runtime.h>
 #include <link.h>
@@ -46,6 +47,7 @@
 #include "meshenv_critic_grad.h"
 #include "meshenv_actor_grad.h"
 #include "meshenv_td3_actor_grad.h"
+#include "meshenv_wide_grad.h"
 #include "meshenv_ppo_grad.h"
 #include "meshenv_optim.h"
 #include "meshenv_rollout.h"
@@ -349,6 +351,80 @@ int pack_refresh(H *h, const char *fn)
     return launch(h, guard, fn, [&] {
         hipLaunchKernelGGL(k_target_pack, dim3(pack_blocks(h->table, h->n_copies), h->n_copies), dim3(256), 0, h->stream, h->table);
     });
+}
+
+}  // namespace
+
+// ---- the handle of DDPG's gradient statements (include/meshenv_ddpg_grad.h) and what its entry points call under their guard
+struct MeshDdpgGrad : HandleBase {
+    WgNet a{}, c{};              // the live actor and critic
+    float *grad = nullptr;       // the caller's flat gradient buffer: the actor's set, then the critic's
+    float *space = nullptr;      // rows_cap rows of kWgRowFloats, then the partial tiles of the chunks
+    int rows_cap = 0;            // the largest n seen, rounded up to 16
+    float loss_scale = 1.0f;
+    bool bound = false;
+};
+
+namespace {
+
+int wg_rows16(int n) { return (n + kCgRows - 1) / kCgRows * kCgRows; }
+
+// the most chunks a call of at most rows16 rows has
+int wg_chunks_cap(int rows16)
+{
+    const int c = (rows16 / kCgRows + kWgMinChunkTiles - 1) / kWgMinChunkTiles;
+    return c < kWgMaxChunks ? c : kWgMaxChunks;
+}
+
+// The workspace for n rows: grows only, and waits for the handle's stream before the old one is freed
+int wg_reserve(MeshDdpgGrad *g, int n, const char *fn)
+{
+    const int rows16 = wg_rows16(n);
+    if (rows16 <= g->rows_cap) return MESHENV_OK;
+    if (hipStreamSynchronize(g->stream) != hipSuccess) return fail(g, MESHENV_E_HIP, std::string(fn) + ": hipStreamSynchronize failed");
+    if (g->space) (void)hipFree(g->space);
+    g->space = nullptr;
+    g->rows_cap = 0;
+    const size_t floats = (size_t)rows16 * kWgRowFloats + (size_t)wg_chunks_cap(rows16) * kWgJobs * 256;
+    if (hipMalloc((void **)&g->space, floats * sizeof(float)) != hipSuccess) {
+        g->space = nullptr;
+        return fail(g, MESHENV_E_HIP, std::string(fn) + ": allocation of the workspace failed");
+    }
+    g->rows_cap = rows16;
+    return MESHENV_OK;
+}
+
+// the matrices of a call of rows16 rows in the workspace (16-byte aligned: every stride is a multiple of 4 floats)
+WgSpace wg_space(const MeshDdpgGrad *g, int rows16, float **partial)
+{
+    WgSpace s;
+    float *p = g->space;
+    const size_t r = (size_t)rows16;
+    s.x0 = p;  p += r * kWgX0;
+    s.a1 = p;  p += r * kWgA1;
+    s.a2 = p;  p += r * kWgA2;
+    s.dz1 = p; p += r * kWgH1;
+    s.dz2 = p; p += r * kWgH2Pad;
+    s.dh = p;
+    *partial = g->space + (size_t)g->rows_cap * kWgRowFloats;
+    return s;
+}
+
+// phase B and the ordered reduction of either statement
+template <int KIN, int NOUT>
+int wg_weights(MeshDdpgGrad *g, const DeviceGuard &guard, const char *fn, const WgSpace &ws, float *partial, int n, float scale,
+               float *grad, float *loss_dev)
+{
+    const int rows16 = wg_rows16(n), chunk_rows = kCgRows * wg_chunk_tiles(n), chunks = (rows16 + chunk_rows - 1) / chunk_rows;
+    const int rc = launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(k_wgrad_weights, dim3(kWgJobs / kWgJobWaves, chunks), dim3(64 * kWgJobWaves), 0, g->stream, ws, rows16,
+                           chunk_rows, partial);
+    }, "weight phase launch");
+    if (rc != MESHENV_OK) return rc;
+    return launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL((k_wgrad_reduce<KIN, NOUT>), dim3(kWgJobs), dim3(256), 0, g->stream, (const float *)partial, chunks, n, scale,
+                           grad, loss_dev);
+    }, "reduction launch");
 }
 
 }  // namespace
@@ -3188,6 +3264,131 @@ int meshenv_td3_actor_grad_backward(MeshTd3ActorGrad *g, int n, const float *obs
         hipLaunchKernelGGL(k_td3_actor_grad_reduce, dim3((TaLayout::params + 255) / 256), dim3(256), 0, g->stream,
                            (const float *)g->partial, A.nwg, n, g->grad, loss_dev);
     }, "reduction launch");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ DDPG [400, 300] loss gradients
+static_assert(MESHENV_DDPG_GRAD_ACTOR_FLOATS == WgActor::stride && MESHENV_DDPG_GRAD_CRITIC_FLOATS == WgCritic::stride &&
+              MESHENV_DDPG_GRAD_MAX_ROWS == kWgMaxRows, "include/meshenv_ddpg_grad.h and csrc/meshenv_wide_grad.h disagree");
+
+// (MeshDdpgGrad and the helpers that run under its entry points' device guard stand with the shared handle code, above)
+extern "C" {
+
+int meshenv_ddpg_grad_create(int device, void *stream, float loss_scale, MeshDdpgGrad **out)
+{
+    const bool ok = loss_scale == 0.5f || loss_scale == 1.0f;
+    const int rc = create_handle("meshenv_ddpg_grad_create", device, stream, out,
+                                 ok ? std::string() : "loss_scale must be 0.5 or 1.0, got " + std::to_string(loss_scale));
+    if (rc == MESHENV_OK) (*out)->loss_scale = loss_scale;
+    return rc;
+}
+
+void meshenv_ddpg_grad_destroy(MeshDdpgGrad *g) { destroy_handle(g, g ? g->space : nullptr); }
+
+const char *meshenv_ddpg_grad_last_error(const MeshDdpgGrad *g) { return last_error(g); }
+
+int meshenv_ddpg_grad_set_stream(MeshDdpgGrad *g, void *stream) { return set_stream(g, stream); }
+
+int meshenv_ddpg_grad_bind(MeshDdpgGrad *g, const float *const *actor_dev, int n_actor, const float *const *q1_dev, int n_critic,
+                           float *grad_dev, int64_t n_grad)
+{
+    if (!g) return MESHENV_E_ARG;
+    if (!actor_dev || !q1_dev || n_actor != 6 || n_critic != 6)
+        return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: takes 6 actor tensors and 6 tensors of the critic (DDPG: actor ReLU "
+                       "[400, 300] with a Linear(300, 3) + Tanh head, critic ReLU [400, 300], float32)");
+    if (!grad_dev || n_grad != MESHENV_DDPG_GRAD_FLOATS)
+        return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: the gradient buffer has " + std::to_string(MESHENV_DDPG_GRAD_FLOATS) +
+                       " floats, got " + std::to_string((long long)n_grad));
+    for (int i = 0; i < 6; i++) {
+        if (!actor_dev[i] || !q1_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: null tensor");
+        // w2 [300][400], the head's [3][300] and the critic's output [1][300] weights are read 16 bytes at a time
+        if (i % 2 == 0 && i >= 2 && (((uintptr_t)actor_dev[i] | (uintptr_t)q1_dev[i]) & 15))
+            return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
+    }
+    if ((uintptr_t)grad_dev & 3) return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: the gradient buffer is not 4-byte aligned");
+    for (int l = 0; l < 3; l++) {
+        g->a.w[l] = actor_dev[2 * l];
+        g->a.b[l] = actor_dev[2 * l + 1];
+        g->c.w[l] = q1_dev[2 * l];
+        g->c.b[l] = q1_dev[2 * l + 1];
+    }
+    g->grad = grad_dev;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+int meshenv_ddpg_grad_critic_backward(MeshDdpgGrad *g, int n, const float *obs_dev, const float *actions_dev, const float *y_dev,
+                                      float *loss_dev, float *const *parts_dev)
+{
+    static const char *fn = "meshenv_ddpg_grad_critic_backward";
+    if (!g) return MESHENV_E_ARG;
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_ddpg_grad_bind)");
+    if (n <= 0 || n > kWgMaxRows)
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": 0 < n <= " + std::to_string(kWgMaxRows) + " (MESHENV_DDPG_GRAD_MAX_ROWS), got " +
+                       std::to_string(n));
+    if (!obs_dev || !actions_dev || !y_dev || !loss_dev)
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": obs_dev, actions_dev, y_dev and loss_dev are required");
+    WgCriticArgs A{};
+    A.n = n;
+    A.two_scale = 2.0f * g->loss_scale;
+    A.obs = obs_dev; A.actions = actions_dev; A.target = y_dev;
+    A.c = g->c;
+    if (parts_dev) {
+        for (int i = 0; i < 3; i++)
+            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, std::string(fn) + ": null per-sample output");
+        A.q = parts_dev[0]; A.acts[0] = parts_dev[1]; A.acts[1] = parts_dev[2];
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, std::string(fn) + ": hipSetDevice failed");
+    int rc = wg_reserve(g, n, fn);
+    if (rc != MESHENV_OK) return rc;
+    float *partial = nullptr;
+    A.ws = wg_space(g, wg_rows16(n), &partial);
+    rc = launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(k_wgrad_critic_rows, dim3(wg_rows16(n) / kCgRows), dim3(64 * kWideWaves), 0, g->stream, A);
+    }, "row phase launch");
+    if (rc != MESHENV_OK) return rc;
+    return wg_weights<kWgIn, 1>(g, guard, fn, A.ws, partial, n, g->loss_scale, g->grad + WgActor::stride, loss_dev);
+}
+
+int meshenv_ddpg_grad_actor_backward(MeshDdpgGrad *g, int n, const float *obs_dev, float *loss_dev, float *const *parts_dev,
+                                     float *const *acts_dev)
+{
+    static const char *fn = "meshenv_ddpg_grad_actor_backward";
+    if (!g) return MESHENV_E_ARG;
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_ddpg_grad_bind)");
+    if (n <= 0 || n > kWgMaxRows)
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": 0 < n <= " + std::to_string(kWgMaxRows) + " (MESHENV_DDPG_GRAD_MAX_ROWS), got " +
+                       std::to_string(n));
+    if (!obs_dev || !loss_dev) return fail(g, MESHENV_E_ARG, std::string(fn) + ": obs_dev and loss_dev are required");
+    WgActorArgs A{};
+    A.n = n;
+    A.obs = obs_dev;
+    A.a = g->a;
+    A.c = g->c;
+    if (parts_dev) {
+        for (int i = 0; i < kTaParts; i++)
+            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, std::string(fn) + ": null per-sample output");
+        A.actions = parts_dev[0]; A.q = parts_dev[1]; A.dq_da = parts_dev[2]; A.d_pre = parts_dev[3];
+    }
+    if (acts_dev) {
+        for (int i = 0; i < 4; i++) {
+            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, std::string(fn) + ": null activation output");
+            A.acts[i / 2][i % 2] = acts_dev[i];
+        }
+    }
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, std::string(fn) + ": hipSetDevice failed");
+    int rc = wg_reserve(g, n, fn);
+    if (rc != MESHENV_OK) return rc;
+    float *partial = nullptr;
+    A.ws = wg_space(g, wg_rows16(n), &partial);
+    rc = launch(g, guard, fn, [&] {
+        hipLaunchKernelGGL(k_wgrad_actor_rows, dim3(wg_rows16(n) / kCgRows), dim3(64 * kWideWaves), 0, g->stream, A);
+    }, "row phase launch");
+    if (rc != MESHENV_OK) return rc;
+    return wg_weights<kWgObs, 3>(g, guard, fn, A.ws, partial, n, -1.0f, g->grad, loss_dev);
 }
 
 }  // extern "C"

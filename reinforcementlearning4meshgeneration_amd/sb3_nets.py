@@ -13,7 +13,7 @@ Q_IN = OBS_DIM + ACT_DIM
 HIDDEN = {KIND_SAC: (128, 3), KIND_TD3: (256, 2)}     # width, hidden layers
 SUPPORTED = ("SAC: ReLU [128, 128, 128] actor (mu and log_std heads) with twin ReLU [128, 128, 128] critics and either the "
              "learned log_ent_coef tensor or a fixed ent_coef; TD3: ReLU [256, 256] tanh actor with twin ReLU [256, 256] "
-             "critics; DDPG (the forward classes FusedPolicy and FusedTDTarget only): ReLU [400, 300] tanh actor with one ReLU "
+             "critics; DDPG (FusedPolicy, FusedTDTarget and FusedDDPGGrad only): ReLU [400, 300] tanh actor with one ReLU "
              "[400, 300] critic (n_critics = 1); 18 observations, 3 actions, critic input cat(obs, action) = 21; float32 "
              "contiguous parameters")
 DDPG_WIDTHS = (400, 300)                              # SB3's TD3Policy default net_arch, what DDPG('MlpPolicy', env) builds

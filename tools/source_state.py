@@ -11,7 +11,7 @@ CSRC = os.path.join(PKG, "csrc")
 PUBLIC_HEADERS = ["meshenv.h", "meshenv_optim.h", "meshenv_td3_actor_grad.h", "meshenv_ppo_grad.h", "meshenv_rollout.h",
                   "meshenv_onpolicy_train.h", "meshenv_offpolicy_train.h", "meshenv_offpolicy_learn.h",
                   "meshenv_eval_callback.h", "meshenv_onpolicy_learn.h", "meshenv_topology.h", "meshenv_fnn.h", "meshenv_fnn_train.h",
-                  "meshenv_augment.h", "meshenv_ddpg.h"]      # build.py's list
+                  "meshenv_augment.h", "meshenv_ddpg.h", "meshenv_ddpg_grad.h"]      # build.py's list
 
 
 def source_files():
