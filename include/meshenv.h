@@ -168,26 +168,23 @@ int meshenv_max_ring(const MeshEnv *h);
 /* Environments per workgroup of the single-step kernel: 1 = k_step<false> (one wave per workgroup), 8 / 16 =
  * k_step_group<G> (chosen at creation from n_envs, see meshenv_create in csrc/meshenv_hip.hip). */
 int meshenv_group_size(const MeshEnv *h);
-/* Which single-step kernel meshenv_step launches: 0 = k_step<false> (one wave per workgroup), 1 = k_step_group<G>
- * (checks, workgroup barrier, updates dealt over the SIMDs).  2 is retired (it named a speculative CU-group kernel that
- * measured slower and was removed); the other codes keep their numbers.
- * 3 = k_step<false, ., true>: after a front smoothing (meshenv_smooth with interior = 0, or a meshenv_move that went through
- * smooth_pave) and until the next reset of ALL envs rings may hold vertices off the 1e-4 lattice, whose clockwise angles
- * can sit exactly on a rounding boundary; steps then run the one-wave-per-env kernel in the instantiation that decides
- * those like the reference's libm (meshenv_atan2_exact).
- * 4 = k_step_group<16, ., true>: the CU-group kernel with its LDS packed by each ring's own length (batches of mixed
- * domains whose sixteen longest rings would not fit one CU).  5 = k_step_group<G, ., false, true>: the CU-group kernel of
- * batches whose ring stride is at most 64 slots (every ring pass is one 64-lane pass, no chunk loops).
- * 6 = k_step<false, true, false, true>: the one-wave-per-env kernel of such batches (default geometry constants).
- * 7 / 8 = k_step<false, true, false, false | true, true>: the throughput-regime forms of 0 / 6 (batches staged record-first,
- * from 8192 envs): a rule-0 quad with a corner that cannot be valid is rejected before the point-in-polygon pass.
- * 9 / 10 = k_step<false, false> / k_step<false, false, true>: 0 / 3 of handles created with non-default geometry
- * constants (MeshEnvParams), which read them at run time. */
+/* Which kernel meshenv_step launches next, as a code.  csrc/meshenv_step_variant.h is the one table of the instantiations
+ * behind the codes, the rule that selects them and the names below; the codes keep their numbers (2 is retired).
+ *  0  k_step, one wave per env                      1  k_step_group<G>, G = meshenv_group_size envs per workgroup
+ *  3  k_step after a front smoothing (meshenv_smooth with interior = 0, or a meshenv_move through smooth_pave) and until
+ *     ALL envs are reset: rings may hold vertices off the 1e-4 lattice, the kernel breaks angle ties like the reference's libm
+ *  4  k_step_group<16>, LDS packed by each ring's own length (mixed domains whose sixteen longest rings exceed one CU)
+ *  5 / 6  1 / 0 for ring strides of at most 64 slots (every ring pass is one 64-lane pass)
+ *  7 / 8  0 / 6 in the throughput regime (record-first staging, from 8192 envs)
+ *  9 / 10  0 / 3 of handles with non-default geometry constants (MeshEnvParams), read at run time */
 int meshenv_step_kernel(const MeshEnv *h);
-/* Which kernel meshenv_rollout (n_steps > 1) launches: 0 = k_step<true, true>, 1 = k_step<true, true, false, true> (ring
- * stride <= 64), 2 = k_step<true, false> (non-default geometry constants), 3 / 4 = k_step<true, true | false, true> (after a
- * front smoothing, as meshenv_step_kernel's 3 / 10). */
+/* Which kernel meshenv_rollout (n_steps > 1) launches: 0 = k_step<true>, 1 = ring stride <= 64, 2 = non-default geometry
+ * constants, 3 / 4 = after a front smoothing with default / non-default constants. */
 int meshenv_rollout_kernel(const MeshEnv *h);
+/* The same two answers as the kernel's name, as rocprofv3 prints it ("meshenv::k_step<false, true, false, false, false>"):
+ * a static string, NULL for a NULL handle. */
+const char *meshenv_step_kernel_name(const MeshEnv *h);
+const char *meshenv_rollout_kernel_name(const MeshEnv *h);
 /* The smoothing kernels evaluate `x ** 2` like the reference's libm (CPython's float ** 2 is pow(x, 2.0), which glibc does
  * not round correctly: it differs from x * x in 0.085 % of the arguments) through a restatement of glibc's pow
  * (csrc/meshenv_libm.h) that the library validates against the libm of the running process at the first smoothing call.

@@ -67,6 +67,7 @@ EXPORTS = [
     "meshenv_critic_grad_last_error", "meshenv_critic_grad_bind", "meshenv_critic_grad_backward",
     "meshenv_actor_grad_create", "meshenv_actor_grad_destroy", "meshenv_actor_grad_set_stream",
     "meshenv_actor_grad_last_error", "meshenv_actor_grad_bind", "meshenv_actor_grad_backward",
+    "meshenv_step_kernel_name", "meshenv_rollout_kernel_name",
 ]
 
 # every symbol include/meshenv_optim.h declares (the optimiser step has a header of its own)
@@ -254,6 +255,10 @@ def load():
     L.meshenv_step_kernel.restype = C.c_int
     L.meshenv_rollout_kernel.argtypes = [vp]
     L.meshenv_rollout_kernel.restype = C.c_int
+    L.meshenv_step_kernel_name.argtypes = [vp]
+    L.meshenv_step_kernel_name.restype = C.c_char_p
+    L.meshenv_rollout_kernel_name.argtypes = [vp]
+    L.meshenv_rollout_kernel_name.restype = C.c_char_p
     L.meshenv_libm_exact.argtypes = [vp]
     L.meshenv_libm_exact.restype = C.c_int
     L.meshenv_atan2_exact.argtypes = []

@@ -59,6 +59,7 @@
 #include "meshenv_fnn.h"
 #include "meshenv_fnn_grad.h"
 #include "meshenv_augment.h"
+#include "meshenv_step_variant.h"
 
 using namespace meshenv;
 
@@ -258,6 +259,27 @@ int fail_arg(MeshEnv *h, const char *msg)
     if (h) h->err = msg;
     else g_create_error = msg;
     return MESHENV_E_ARG;
+}
+
+// ---- the step kernels, parallel to StepVariant (csrc/meshenv_step_variant.h): the group rows, then the one-wave-per-env rows
+using GroupKernel = void (*)(MESHENV_ENTRY_PARAMS GroupArgs);
+using WaveKernel = void (*)(KStepArgs);
+const GroupKernel kGroupKernels[] = {
+    k_step_group<16, true, true, false>, k_step_group<16, true, false, true>, k_step_group<8, true, false, true>,
+    k_step_group<16, true, false, false>, k_step_group<8, true, false, false>};
+const WaveKernel kWaveKernels[] = {
+    k_step<false, true, true, false, false>, k_step<false, false, true, false, false>, k_step<false, true, false, true, true>,
+    k_step<false, true, false, false, true>, k_step<false, true, false, true, false>, k_step<false, true, false, false, false>,
+    k_step<false, false, false, false, false>,
+    k_step<true, true, true, false, false>, k_step<true, false, true, false, false>, k_step<true, true, false, true, false>,
+    k_step<true, true, false, false, false>, k_step<true, false, false, false, false>};
+static_assert(sizeof(kGroupKernels) / sizeof(kGroupKernels[0]) == kStepGroupVariants &&
+                  sizeof(kWaveKernels) / sizeof(kWaveKernels[0]) == kStepWaveVariants,
+              "one kernel per StepVariant row");
+
+StepFacts step_facts(const MeshEnv *h, bool multi)
+{
+    return {multi, h->default_params, h->front_moved, h->group, h->env_lds != nullptr, h->cap, h->stage_bits};
 }
 
 // ---- what the handles of the fused networks share (MeshActor, MeshPolicy, MeshTarget, MeshCriticGrad, MeshActorGrad, MeshTd3ActorGrad,
@@ -572,15 +594,9 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
     // shorter rings cannot lower the cap under an earlier one.
     constexpr int kLdsCap = 160 * 1024;
     if (lds > 64 * 1024) {
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        CREATE_HIP(hipFuncSetAttribute((const void *)k_step<false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
+        for (int v = kStepGroupVariants; v < kStepVariantCount; v++)   // every k_step that can meet rings of more than 64 slots
+            if (!kStepVariants[v].small)
+                CREATE_HIP(hipFuncSetAttribute((const void *)kWaveKernels[v - kStepGroupVariants], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
         CREATE_HIP(hipFuncSetAttribute((const void *)k_reset, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
         CREATE_HIP(hipFuncSetAttribute((const void *)k_init_domains, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
     }
@@ -651,13 +667,6 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
             const bool light = lt ? atoi(lt) != 0 : (lazy && n_envs >= 16384);
             h->stage_bits = (lazy ? 2 : 0) | (light ? 4 : 0);
         }
-        if (G > 1 && h->group_lds > 64 * 1024) {
-            const bool ragged = !h->env_lds_host.empty();
-            const void *fn = ragged ? (const void *)k_step_group<16, true, true>
-                             : G == 16 ? (const void *)k_step_group<16, true> : (const void *)k_step_group<8, true>;
-            if (!ragged && cap <= 64) fn = G == 16 ? (const void *)k_step_group<16, true, false, true> : (const void *)k_step_group<8, true, false, true>;
-            CREATE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
-        }
     }
 
     DevState &S = h->S;
@@ -699,6 +708,8 @@ static int create_impl(int device, int n_domains, const int32_t *dom_offsets_hos
         CREATE_TRY(dev_alloc(h, &h->env_lds, (size_t)n_envs));
         CREATE_HIP(hipMemcpy(h->env_lds, h->env_lds_host.data(), sizeof(int2) * (size_t)n_envs, hipMemcpyHostToDevice));
     }
+    if (h->group > 1 && h->group_lds > 64 * 1024)   // the one CU-group kernel this handle steps with (env_lds decides ragged)
+        CREATE_HIP(hipFuncSetAttribute((const void *)kGroupKernels[select_step_variant(step_facts(h, false))], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap));
     if (prm.log_capacity > 0) {
         CREATE_TRY(dev_alloc(h, &K.log_quads, (size_t)n_envs * 2 * prm.log_capacity * 4));
         CREATE_TRY(dev_alloc(h, &K.log_vxy, (size_t)n_envs * 2 * prm.log_capacity));
@@ -1057,25 +1068,11 @@ int meshenv_set_packed_output(MeshEnv *h, float *msg_dev)
 int meshenv_num_envs(const MeshEnv *h) { return h ? h->n_envs : MESHENV_E_ARG; }
 int meshenv_max_ring(const MeshEnv *h) { return h ? h->max_ring : MESHENV_E_ARG; }
 int meshenv_group_size(const MeshEnv *h) { return h ? h->group : MESHENV_E_ARG; }
-int meshenv_step_kernel(const MeshEnv *h)
-{
-    if (!h) return MESHENV_E_ARG;
-    if (h->front_moved) return h->default_params ? 3 : 10;
-    if (h->group <= 1) {
-        if (!h->default_params) return 9;
-        const bool pre = h->default_params && (h->stage_bits & 2);
-        return h->default_params && h->cap <= 64 ? (pre ? 8 : 6) : (pre ? 7 : 0);
-    }
-    if (h->env_lds) return 4;
-    return h->cap <= 64 ? 5 : 1;
-}
-int meshenv_rollout_kernel(const MeshEnv *h)
-{
-    if (!h) return MESHENV_E_ARG;
-    if (h->front_moved) return h->default_params ? 3 : 4;
-    if (!h->default_params) return 2;
-    return h->cap <= 64 ? 1 : 0;
-}
+static const StepVariantRow &step_row(const MeshEnv *h, bool multi) { return kStepVariants[select_step_variant(step_facts(h, multi))]; }
+int meshenv_step_kernel(const MeshEnv *h) { return h ? step_row(h, false).code : MESHENV_E_ARG; }
+int meshenv_rollout_kernel(const MeshEnv *h) { return h ? step_row(h, true).code : MESHENV_E_ARG; }
+const char *meshenv_step_kernel_name(const MeshEnv *h) { return h ? step_row(h, false).name : nullptr; }
+const char *meshenv_rollout_kernel_name(const MeshEnv *h) { return h ? step_row(h, true).name : nullptr; }
 int meshenv_libm_exact(const MeshEnv *h) { return h ? h->libm_exact : MESHENV_E_ARG; }
 int meshenv_atan2_exact(void) { return atan_host().mode == 2 ? 1 : 0; }
 
@@ -1424,12 +1421,9 @@ static int launch_step(MeshEnv *h, int n_steps, const float *actions_dev, float 
     const size_t slot = (size_t)(h->ev_count % MESHENV_TIMING_POOL);
     const long long pos = h->timing > 0 ? (h->launch_count++ % (2LL * h->timing)) : -1;
     if (pos == 0) HIP_TRY(h, hipEventRecord(h->ev[2 * slot], h->stream));
-    // After a front smoothing (meshenv_smooth(interior = 0), or a meshenv_move that went through smooth_pave) a ring can hold
-    // vertices off the 1e-4 lattice, and with them clockwise angles that sit exactly on a rounding boundary: until every env
-    // has been reset, steps run the one-wave-per-env kernel in its tie-breaking instantiation (csrc/meshenv_geom.h).
-    if (n_steps == 1 && h->group > 1 && !h->front_moved) {
+    const StepVariant v = select_step_variant(step_facts(h, n_steps > 1));
+    if (v < kStepGroupVariants) {
         const int G = h->group;
-        const dim3 grid((h->n_envs + G - 1) / G), block(64 * G);
         GroupArgs A;
         A.S = h->S;
         A.outs.obs_out = obs_dev; A.outs.reward = reward_dev; A.outs.done = done_dev; A.outs.complete = complete_dev;
@@ -1441,37 +1435,15 @@ static int launch_step(MeshEnv *h, int n_steps, const float *actions_dev, float 
         A.env_lds = h->env_lds;
         A.ho_off = h->ho_off;
         A.pad = 0;
-        if (h->env_lds) hipLaunchKernelGGL((k_step_group<16, true, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);   // ragged: G == 16 only
-        else if (h->cap <= 64 && G == 16) hipLaunchKernelGGL((k_step_group<16, true, false, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
-        else if (h->cap <= 64) hipLaunchKernelGGL((k_step_group<8, true, false, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
-        else if (G == 16) hipLaunchKernelGGL((k_step_group<16, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
-        else hipLaunchKernelGGL((k_step_group<8, true>), grid, block, h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
+        hipLaunchKernelGGL(kGroupKernels[v], dim3((h->n_envs + G - 1) / G), dim3(64 * G), h->group_lds, h->stream, MESHENV_ENTRY_LAUNCH(A) A);
     } else {
-        const dim3 grid(h->n_envs), block(64);
-#define MESHENV_LAUNCH_STEP(MULTI, DEF)                                                                                      \
-    do {                                                                                                                     \
-        KStepArgs ka;                                                                                                        \
-        ka.S = h->S; ka.cap = h->cap; ka.n_steps = n_steps; ka.actions = actions_dev; ka.obs_out = obs_dev;                  \
-        ka.reward = reward_dev; ka.done = done_dev; ka.complete = complete_dev; ka.term_obs = terminal_obs_dev;              \
-        ka.auto_reset = auto_reset; ka.step0 = (unsigned long long)h->steps_done;                                            \
-        if (h->front_moved) hipLaunchKernelGGL((k_step<MULTI, DEF, true>), grid, block, h->lds, h->stream, ka);              \
-        else if (DEF && !MULTI && (h->stage_bits & 2) && h->cap <= 64)                                                       \
-            hipLaunchKernelGGL((k_step<false, DEF, false, DEF, DEF>), grid, block, h->lds, h->stream, ka);                   \
-        else if (DEF && !MULTI && (h->stage_bits & 2))                                                                       \
-            hipLaunchKernelGGL((k_step<false, DEF, false, false, DEF>), grid, block, h->lds, h->stream, ka);                 \
-        else if (DEF && h->cap <= 64) hipLaunchKernelGGL((k_step<MULTI, DEF, false, DEF>), grid, block, h->lds, h->stream, ka); \
-        else hipLaunchKernelGGL((k_step<MULTI, DEF>), grid, block, h->lds, h->stream, ka);                                   \
-    } while (0)
-        if (n_steps == 1) {
-            // bit 1: record-first staging, bit 2: key-less staging -- throughput regime only, decided in meshenv_create
-            auto_reset = (auto_reset ? 1 : 0) | h->stage_bits;
-            if (h->default_params) MESHENV_LAUNCH_STEP(false, true);
-            else MESHENV_LAUNCH_STEP(false, false);
-        } else {
-            if (h->default_params) MESHENV_LAUNCH_STEP(true, true);
-            else MESHENV_LAUNCH_STEP(true, false);
-        }
-#undef MESHENV_LAUNCH_STEP
+        // bit 1: record-first staging, bit 2: key-less staging -- throughput regime only, decided in meshenv_create
+        if (n_steps == 1) auto_reset = (auto_reset ? 1 : 0) | h->stage_bits;
+        KStepArgs ka;
+        ka.S = h->S; ka.cap = h->cap; ka.n_steps = n_steps; ka.actions = actions_dev; ka.obs_out = obs_dev;
+        ka.reward = reward_dev; ka.done = done_dev; ka.complete = complete_dev; ka.term_obs = terminal_obs_dev;
+        ka.auto_reset = auto_reset; ka.step0 = (unsigned long long)h->steps_done;
+        hipLaunchKernelGGL(kWaveKernels[v - kStepGroupVariants], dim3(h->n_envs), dim3(64), h->lds, h->stream, ka);
     }
     HIP_TRY(h, hipGetLastError());
     if (h->reselect_pending) {  // the step after a candidate rebuild: envs whose action was rejected take the parked selection
@@ -2071,7 +2043,7 @@ int meshenv_step_actor(MeshEnv *h, MeshActor *a, const float *actions_dev, float
     GA.eps_out = eps_out_dev;
     GA.seed = seed; GA.counter = counter;
     GA.sample = sample ? 1 : 0; GA.pad = 0;
-    if (h->cap <= 64) hipLaunchKernelGGL((k_step_group_actor<true, true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, MESHENV_ENTRY_LAUNCH(GA.g) GA);
+    if (step_small_ring(h->cap)) hipLaunchKernelGGL((k_step_group_actor<true, true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, MESHENV_ENTRY_LAUNCH(GA.g) GA);
     else hipLaunchKernelGGL((k_step_group_actor<true>), dim3((h->n_envs + 15) / 16), dim3(64 * 16), group_actor_lds_bytes(h->cap), h->stream, MESHENV_ENTRY_LAUNCH(GA.g) GA);
     HIP_TRY(h, hipGetLastError());
     h->steps_done += 1;

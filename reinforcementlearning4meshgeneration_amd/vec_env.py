@@ -455,22 +455,15 @@ class MeshVecEnv:
 
     @property
     def step_kernel(self) -> str:
-        """Name (as rocprofv3 prints it) of the kernel the next step() launches, from meshenv_step_kernel: the CU-group kernel
-        for batches of one workgroup per CU, the one-wave-per-env kernel otherwise -- in its tie-breaking instantiation
-        (`k_step<false, true, true>`) between a front smoothing and the next reset of all envs."""
-        return {0: "meshenv::k_step<false, true, false, false, false>", 6: "meshenv::k_step<false, true, false, true, false>",
-                7: "meshenv::k_step<false, true, false, false, true>", 8: "meshenv::k_step<false, true, false, true, true>", 1: f"meshenv::k_step_group<{self.group_size}, true, false, false>",
-                3: "meshenv::k_step<false, true, true, false, false>",
-                9: "meshenv::k_step<false, false, false, false, false>", 10: "meshenv::k_step<false, false, true, false, false>",
-                4: "meshenv::k_step_group<16, true, true, false>",
-                5: f"meshenv::k_step_group<{self.group_size}, true, false, true>"}[self._L.meshenv_step_kernel(self._handle)]
+        """Name (as rocprofv3 prints it) of the kernel the next step() launches, from meshenv_step_kernel_name: the CU-group
+        kernel for batches of one workgroup per CU, the one-wave-per-env kernel otherwise -- in its tie-breaking instantiation
+        between a front smoothing and the next reset of all envs (the table: csrc/meshenv_step_variant.h)."""
+        return self._L.meshenv_step_kernel_name(self._handle).decode()
 
     @property
     def rollout_kernel(self) -> str:
-        """Name of the kernel rollout() (T > 1 steps in one launch) launches, from meshenv_rollout_kernel."""
-        return {0: "meshenv::k_step<true, true, false, false, false>", 1: "meshenv::k_step<true, true, false, true, false>",
-                2: "meshenv::k_step<true, false, false, false, false>", 3: "meshenv::k_step<true, true, true, false, false>",
-                4: "meshenv::k_step<true, false, true, false, false>"}[self._L.meshenv_rollout_kernel(self._handle)]
+        """Name of the kernel rollout() (T > 1 steps in one launch) launches, from meshenv_rollout_kernel_name."""
+        return self._L.meshenv_rollout_kernel_name(self._handle).decode()
 
     @property
     def libm_exact(self) -> int:

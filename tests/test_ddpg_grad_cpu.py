@@ -254,4 +254,4 @@ def test_exported_lazily_declared_and_built():
         assert hasattr(L, name), name
         assert getattr(L, name).argtypes is not None or name.endswith("last_error"), name
     assert "meshenv_ddpg_grad.h" in build.PUBLIC_HEADERS
-    assert len(_capi.EXPORTS) == 80                                                  # meshenv.h is untouched
+    assert len(_capi.EXPORTS) == 82                                                  # meshenv.h is untouched

@@ -313,7 +313,7 @@ def test_exports_constants_and_header():
     others = set(_capi.EXPORTS) | set(_capi.EXPORTS_OPTIM) | set(_capi.EXPORTS_TD3_ACTOR_GRAD) | set(_capi.EXPORTS_PPO_GRAD) | \
         set(_capi.EXPORTS_ROLLOUT) | set(_capi.EXPORTS_ONPOLICY_TRAIN)
     assert not set(names) & others
-    assert len(_capi.EXPORTS) == 80
+    assert len(_capi.EXPORTS) == 82
     assert "meshenv_offpolicy_train.h" in build.PUBLIC_HEADERS
     header = open(os.path.join(ROOT, "include", "meshenv_offpolicy_train.h")).read()
     declared = set(re.findall(r"\b(meshenv_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))

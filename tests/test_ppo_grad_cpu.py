@@ -259,7 +259,7 @@ def test_exported_lazily_declared_and_built():
            ["meshenv_policy_bind", "meshenv_policy_refresh"]
     assert sorted(names) == sorted(want) and len(names) == 8
     assert not set(names) & (set(_capi.EXPORTS) | set(_capi.EXPORTS_OPTIM) | set(_capi.EXPORTS_TD3_ACTOR_GRAD))
-    assert len(_capi.EXPORTS) == 80
+    assert len(_capi.EXPORTS) == 82
     header = open(os.path.join(ROOT, "include", "meshenv_ppo_grad.h")).read()
     assert sorted(set(re.findall(r"\b(meshenv_[a-z0-9_]+)\s*\(", header))) == sorted(names)
     L = _capi.load()
