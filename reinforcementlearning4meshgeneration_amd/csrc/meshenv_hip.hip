@@ -60,6 +60,7 @@
 #include "meshenv_fnn_grad.h"
 #include "meshenv_augment.h"
 #include "meshenv_step_variant.h"
+#include "meshenv_grad_bind.h"
 
 using namespace meshenv;
 
@@ -282,8 +283,7 @@ StepFacts step_facts(const MeshEnv *h, bool multi)
     return {multi, h->default_params, h->front_moved, h->group, h->env_lds != nullptr, h->cap, h->stage_bits};
 }
 
-// ---- what the handles of the fused networks share (MeshActor, MeshPolicy, MeshTarget, MeshCriticGrad, MeshActorGrad, MeshTd3ActorGrad,
-// MeshOptim, MeshRolloutBuffer)
+// ---- what every handle but MeshEnv derives from: its device, its stream and the text of its *_last_error
 struct HandleBase {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -356,6 +356,45 @@ int launch(H *h, const DeviceGuard &guard, const char *fn, F &&enqueue, const ch
     enqueue();
     if (hipGetLastError() != hipSuccess) return fail(h, MESHENV_E_HIP, std::string(fn) + ": " + what + " failed");
     return MESHENV_OK;
+}
+
+// ---- what the loss-gradient handles share; csrc/meshenv_grad_bind.h describes their binds
+struct GradHandle : HandleBase {
+    float *grad = nullptr;      // the caller's flat gradient buffer (the layout's stride floats)
+    float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
+    bool bound = false;
+};
+
+// A bind behind its null-handle check: d's refusal of the arguments, then `partial_floats` zeroed floats on the handle's device,
+// then grad_dev committed.  The caller commits its tensors after MESHENV_OK: a refused bind leaves the handle as it was.
+int grad_bind(GradHandle *g, const GradBind &d, const float *const *const *nets, const int *counts, float *grad_dev, int64_t n_grad,
+              int64_t want, size_t partial_floats)
+{
+    const std::string refusal = grad_bind_refusal(d, nets, counts, grad_dev, n_grad, want);
+    if (!refusal.empty()) return fail(g, MESHENV_E_ARG, refusal);
+    DeviceGuard guard(g->device);
+    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, std::string(d.fn) + ": hipSetDevice failed");
+    if (!zeroed_once(g, &g->partial, partial_floats)) return fail(g, MESHENV_E_HIP, std::string(d.fn) + ": allocation failed");
+    g->grad = grad_dev;
+    g->bound = true;
+    return MESHENV_OK;
+}
+
+// An optional array of `count` outputs of one kind ("per-sample", "per-row", "activation"): absent, or every entry there.
+template <typename H>
+int outputs_ok(H *h, const char *fn, float *const *out, int count, const char *kind)
+{
+    for (int i = 0; out && i < count; i++)
+        if (!out[i]) return fail(h, MESHENV_E_ARG, std::string(fn) + ": null " + kind + " output");
+    return MESHENV_OK;
+}
+
+// The two launches of a backward under the caller's guard: the gradient kernel, then the reduction of its partial sets.
+template <typename H, typename F, typename R>
+int launch_reduced(H *h, const DeviceGuard &guard, const char *fn, F &&grad_kernel, R &&reduction)
+{
+    const int rc = launch(h, guard, fn, grad_kernel);
+    return rc != MESHENV_OK ? rc : launch(h, guard, fn, reduction, "reduction launch");
 }
 
 // The kernels' pointers into `buf`, from consecutive slots of the network's PackLayout (meshenv_pack.h).
@@ -2905,18 +2944,12 @@ int meshenv_target_forward(MeshTarget *t, int n, const float *next_obs_dev, cons
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ SAC / TD3 critic loss gradients
-struct MeshCriticGrad : HandleBase {
+struct MeshCriticGrad : GradHandle {
     int kind = -1;
     CgCritic c[2]{};
-    float *grad = nullptr;      // the caller's flat gradient buffer (CgLayout::grads floats)
-    float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
-    bool bound = false;
 };
 
 namespace {
-
-const char *kCriticGradKinds = "supported kinds: 0 (SAC: twin ReLU [128, 128, 128] critics) or 1 (TD3: twin ReLU [256, 256] critics); "
-                               "input cat(obs, action) = 21, float32";
 
 template <int H, int NL>
 void cg_sizes(int *grads, int *set) { *grads = CgLayout<H, NL>::grads; *set = CgLayout<H, NL>::set; }
@@ -2934,23 +2967,11 @@ int grad_groups(int n)
     return tiles <= 512 ? (tiles < 64 ? tiles : 64) : kCgMaxGroups;
 }
 
-// The twin critics' tensors (w1 b1 ... out_w out_b, `count` each) into c[2].  The hidden layers' [H][H] weights are read 16
-// bytes at a time.  Returns what is wrong, or nothing; `weight` names a tensor in the alignment refusal.
-std::string bind_critics(CgCritic c[2], const float *const *q1_dev, const float *const *q2_dev, int count, const char *weight)
+// The FNN's kernel strides over its tiles: one workgroup per tile up to kCgMaxGroups.
+int fnn_grad_groups(int n)
 {
-    for (int i = 0; i < count; i++) {
-        if (!q1_dev[i] || !q2_dev[i]) return "null critic tensor";
-        if (i % 2 == 0 && i >= 2 && (((uintptr_t)q1_dev[i] | (uintptr_t)q2_dev[i]) & 15))
-            return std::string(weight) + " tensor " + std::to_string(i) + " is not 16-byte aligned";
-    }
-    for (int k = 0; k < 2; k++) {
-        const float *const *p = k == 0 ? q1_dev : q2_dev;
-        for (int l = 0; l < count / 2; l++) {
-            c[k].w[l] = p[2 * l];
-            c[k].b[l] = p[2 * l + 1];
-        }
-    }
-    return std::string();
+    const int tiles = (n + kCgRows - 1) / kCgRows;
+    return tiles < kCgMaxGroups ? tiles : kCgMaxGroups;
 }
 
 }  // namespace
@@ -2976,38 +2997,30 @@ int meshenv_critic_grad_bind(MeshCriticGrad *g, const float *const *q1_dev, cons
                              float *grad_dev, int64_t n_grad)
 {
     if (!g) return MESHENV_E_ARG;
-    const int NL = g->kind == kTargetSAC ? 3 : 2, want = 2 * NL + 2;
+    const GradBind &d = kCriticGradBind[g->kind == kTargetSAC ? 0 : 1];
     int grads = 0, set = 0;
     cg_layout(g->kind, &grads, &set);
-    if (!q1_dev || !q2_dev || n_critic != want)
-        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: kind " + std::to_string(g->kind) + " takes " + std::to_string(want) +
-                       " tensors per critic; " + kCriticGradKinds);
-    if (!grad_dev || n_grad != grads)
-        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: the gradient buffer of kind " + std::to_string(g->kind) + " has " +
-                       std::to_string(grads) + " floats, got " + std::to_string((long long)n_grad));
-    CgCritic c[2]{};
-    const std::string refusal = bind_critics(c, q1_dev, q2_dev, want, "weight");
-    if (!refusal.empty()) return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_bind: " + refusal);
-    DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: hipSetDevice failed");
-    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * set))
-        return fail(g, MESHENV_E_HIP, "meshenv_critic_grad_bind: allocation failed");
-    g->c[0] = c[0]; g->c[1] = c[1];
-    g->grad = grad_dev;
-    g->bound = true;
+    const float *const *nets[] = {q1_dev, q2_dev};
+    const int counts[] = {n_critic, n_critic};
+    const int rc = grad_bind(g, d, nets, counts, grad_dev, n_grad, grads, (size_t)kCgMaxGroups * set);
+    if (rc != MESHENV_OK) return rc;
+    for (int k = 0; k < 2; k++) grad_bind_pairs(nets[k], n_critic / 2, g->c[k].w, g->c[k].b);
     return MESHENV_OK;
 }
 
 int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev, const float *actions_dev, const float *target_dev,
                                  float *loss_dev, float *q1_dev, float *q2_dev, float *const *acts1_dev, float *const *acts2_dev)
 {
+    static const char *fn = "meshenv_critic_grad_backward";
     if (!g) return MESHENV_E_ARG;
-    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_critic_grad_backward: no tensors bound (meshenv_critic_grad_bind)");
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_critic_grad_bind)");
     if (n <= 0 || !obs_dev || !actions_dev || !target_dev || !loss_dev)
-        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: n > 0, obs_dev, actions_dev, target_dev and loss_dev are required");
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": n > 0, obs_dev, actions_dev, target_dev and loss_dev are required");
     if ((acts1_dev == nullptr) != (acts2_dev == nullptr))
-        return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: acts1_dev and acts2_dev go together");
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": acts1_dev and acts2_dev go together");
     const int NL = g->kind == kTargetSAC ? 3 : 2;
+    for (float *const *acts : {acts1_dev, acts2_dev})
+        if (int rc = outputs_ok(g, fn, acts, NL, "activation")) return rc;
     int grads = 0, set = 0;
     cg_layout(g->kind, &grads, &set);
     CgArgs A{};
@@ -3020,32 +3033,25 @@ int meshenv_critic_grad_backward(MeshCriticGrad *g, int n, const float *obs_dev,
     for (int l = 0; l < NL; l++) {
         A.acts[0][l] = acts1_dev ? acts1_dev[l] : nullptr;
         A.acts[1][l] = acts2_dev ? acts2_dev[l] : nullptr;
-        if (acts1_dev && (!A.acts[0][l] || !A.acts[1][l]))
-            return fail(g, MESHENV_E_ARG, "meshenv_critic_grad_backward: null activation output");
     }
     DeviceGuard guard(g->device);
-    const int rc = launch(g, guard, "meshenv_critic_grad_backward", [&] {
+    return launch_reduced(g, guard, fn, [&] {
         if (g->kind == kTargetSAC) hipLaunchKernelGGL(k_critic_grad<kTargetSAC>, dim3(A.nwg, 2), dim3(512), 0, g->stream, A);
         else hipLaunchKernelGGL(k_critic_grad<kTargetTD3>, dim3(A.nwg, 2 * kCgSplitTD3), dim3(1024), 0, g->stream, A);
-    });
-    if (rc != MESHENV_OK) return rc;
-    return launch(g, guard, "meshenv_critic_grad_backward", [&] {
+    }, [&] {
         hipLaunchKernelGGL(k_critic_grad_reduce, dim3((grads + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial, A.nwg,
                            set, grads, n, g->grad, loss_dev);
-    }, "reduction launch");
+    });
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ SAC actor / ent_coef loss gradients
-struct MeshActorGrad : HandleBase {
+struct MeshActorGrad : GradHandle {
     float ent_coef = 0.0f, target_entropy = 0.0f;
     AgActor a{};
     CgCritic c[2]{};
     const float *log_ent_coef = nullptr;
-    float *grad = nullptr;      // the caller's flat gradient buffer (AgLayout::stride floats)
-    float *partial = nullptr;   // kCgMaxGroups partial sets, zeroed once
-    bool bound = false;
 };
 
 extern "C" {
@@ -3071,48 +3077,28 @@ int meshenv_actor_grad_bind(MeshActorGrad *g, const float *const *actor_dev, int
                             const float *const *q2_dev, int n_critic, const float *log_ent_coef_dev, float *grad_dev, int64_t n_grad)
 {
     if (!g) return MESHENV_E_ARG;
-    if (!actor_dev || !q1_dev || !q2_dev || n_actor != 10 || n_critic != 8)
-        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: takes 10 actor tensors and 8 tensors per critic (SAC: actor ReLU "
-                       "[128, 128, 128] with mu / log_std heads, twin ReLU [128, 128, 128] critics, float32)");
-    if (!grad_dev || n_grad != AgLayout::stride)
-        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: the gradient buffer has " + std::to_string(AgLayout::stride) +
-                       " floats, got " + std::to_string((long long)n_grad));
-    for (int i = 0; i < 10; i++) {
-        if (!actor_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: null actor tensor");
-        // the [H][H] weights and the heads' [3][H] weights are read 16 bytes at a time
-        if (i % 2 == 0 && i >= 2 && ((uintptr_t)actor_dev[i] & 15))
-            return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: actor weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
-    CgCritic c[2]{};
-    const std::string refusal = bind_critics(c, q1_dev, q2_dev, 8, "critic weight");
-    if (!refusal.empty()) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_bind: " + refusal);
-    DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: hipSetDevice failed");
-    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * AgLayout::set))
-        return fail(g, MESHENV_E_HIP, "meshenv_actor_grad_bind: allocation failed");
-    for (int l = 0; l < 3; l++) {
-        g->a.w[l] = actor_dev[2 * l];
-        g->a.b[l] = actor_dev[2 * l + 1];
-    }
+    const float *const *nets[] = {actor_dev, q1_dev, q2_dev};
+    const int counts[] = {n_actor, n_critic, n_critic};
+    const int rc = grad_bind(g, kActorGradBind, nets, counts, grad_dev, n_grad, AgLayout::stride, (size_t)kCgMaxGroups * AgLayout::set);
+    if (rc != MESHENV_OK) return rc;
+    grad_bind_pairs(actor_dev, 3, g->a.w, g->a.b);
     g->a.mu_w = actor_dev[6]; g->a.mu_b = actor_dev[7]; g->a.ls_w = actor_dev[8]; g->a.ls_b = actor_dev[9];
-    g->c[0] = c[0]; g->c[1] = c[1];
+    for (int k = 0; k < 2; k++) grad_bind_pairs(nets[1 + k], 4, g->c[k].w, g->c[k].b);
     g->log_ent_coef = log_ent_coef_dev;
-    g->grad = grad_dev;
-    g->bound = true;
     return MESHENV_OK;
 }
 
 int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, const float *noise_dev, int sample, uint64_t seed,
                                 uint64_t counter, float *losses_dev, float *eps_out_dev, float *const *parts_dev, float *const *acts_dev)
 {
+    static const char *fn = "meshenv_actor_grad_backward";
     if (!g) return MESHENV_E_ARG;
-    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_actor_grad_backward: no tensors bound (meshenv_actor_grad_bind)");
-    if (n <= 0 || !obs_dev || !losses_dev)
-        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: n > 0, obs_dev and losses_dev are required");
-    if (noise_dev && sample)
-        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: noise_dev and sample are exclusive");
-    if (eps_out_dev && !noise_dev && !sample)
-        return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: eps_out_dev needs noise_dev or sample");
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_actor_grad_bind)");
+    if (n <= 0 || !obs_dev || !losses_dev) return fail(g, MESHENV_E_ARG, std::string(fn) + ": n > 0, obs_dev and losses_dev are required");
+    if (noise_dev && sample) return fail(g, MESHENV_E_ARG, std::string(fn) + ": noise_dev and sample are exclusive");
+    if (eps_out_dev && !noise_dev && !sample) return fail(g, MESHENV_E_ARG, std::string(fn) + ": eps_out_dev needs noise_dev or sample");
+    if (int rc = outputs_ok(g, fn, parts_dev, kAgParts, "per-sample")) return rc;
+    if (int rc = outputs_ok(g, fn, acts_dev, 9, "activation")) return rc;
     AgArgs A{};
     A.n = n;
     A.nwg = grad_groups(n);
@@ -3122,24 +3108,15 @@ int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, c
     A.partial = g->partial;
     A.eps_out = eps_out_dev;
     if (parts_dev) {
-        for (int i = 0; i < kAgParts; i++)
-            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null per-sample output");
         A.actions = parts_dev[0]; A.log_prob = parts_dev[1]; A.q[0] = parts_dev[2]; A.q[1] = parts_dev[3];
         A.dq_da = parts_dev[4]; A.d_mu = parts_dev[5]; A.d_ls = parts_dev[6];
     }
-    if (acts_dev) {
-        for (int i = 0; i < 9; i++) {
-            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_actor_grad_backward: null activation output");
-            A.acts[i / 3][i % 3] = acts_dev[i];
-        }
-    }
+    for (int i = 0; acts_dev && i < 9; i++) A.acts[i / 3][i % 3] = acts_dev[i];
     DeviceGuard guard(g->device);
-    const int rc = launch(g, guard, "meshenv_actor_grad_backward", [&] { hipLaunchKernelGGL(k_actor_grad, dim3(A.nwg), dim3(512), 0, g->stream, A); });
-    if (rc != MESHENV_OK) return rc;
-    return launch(g, guard, "meshenv_actor_grad_backward", [&] {
+    return launch_reduced(g, guard, fn, [&] { hipLaunchKernelGGL(k_actor_grad, dim3(A.nwg), dim3(512), 0, g->stream, A); }, [&] {
         hipLaunchKernelGGL(k_actor_grad_reduce, dim3((AgLayout::ent + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial,
                            A.nwg, n, g->log_ent_coef, g->grad, losses_dev);
-    }, "reduction launch");
+    });
 }
 
 }  // extern "C"
@@ -3147,12 +3124,9 @@ int meshenv_actor_grad_backward(MeshActorGrad *g, int n, const float *obs_dev, c
 // ------------------------------------------------------------------------------------------ TD3 / DDPG actor loss gradients
 static_assert(MESHENV_TD3_ACTOR_GRAD_FLOATS == TaLayout::stride, "include/meshenv_td3_actor_grad.h and csrc/meshenv_td3_actor_grad.h disagree");
 
-struct MeshTd3ActorGrad : HandleBase {
+struct MeshTd3ActorGrad : GradHandle {
     const float *w[3]{}, *b[3]{};   // the actor
     CgCritic c{};                   // the first critic
-    float *grad = nullptr;          // the caller's flat gradient buffer (TaLayout::stride floats)
-    float *partial = nullptr;       // kCgMaxGroups partial sets, zeroed once
-    bool bound = false;
 };
 
 extern "C" {
@@ -3172,40 +3146,25 @@ int meshenv_td3_actor_grad_bind(MeshTd3ActorGrad *g, const float *const *actor_d
                                 int n_critic, float *grad_dev, int64_t n_grad)
 {
     if (!g) return MESHENV_E_ARG;
-    if (!actor_dev || !q1_dev || n_actor != 6 || n_critic != 6)
-        return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: takes 6 actor tensors and 6 tensors of the first critic (TD3 / "
-                       "DDPG: actor ReLU [256, 256] with a Linear(256, 3) + Tanh head, critic ReLU [256, 256], float32)");
-    if (!grad_dev || n_grad != TaLayout::stride)
-        return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: the gradient buffer has " + std::to_string(TaLayout::stride) +
-                       " floats, got " + std::to_string((long long)n_grad));
-    for (int i = 0; i < 6; i++) {
-        if (!actor_dev[i] || !q1_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: null tensor");
-        // the [H][H] weights, the head's [3][H] and the critic's output [1][H] weights are read 16 bytes at a time
-        if (i % 2 == 0 && i >= 2 && (((uintptr_t)actor_dev[i] | (uintptr_t)q1_dev[i]) & 15))
-            return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
-    DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_td3_actor_grad_bind: hipSetDevice failed");
-    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * TaLayout::set))
-        return fail(g, MESHENV_E_HIP, "meshenv_td3_actor_grad_bind: allocation failed");
-    for (int l = 0; l < 3; l++) {
-        g->w[l] = actor_dev[2 * l];
-        g->b[l] = actor_dev[2 * l + 1];
-        g->c.w[l] = q1_dev[2 * l];
-        g->c.b[l] = q1_dev[2 * l + 1];
-    }
-    g->grad = grad_dev;
-    g->bound = true;
+    const float *const *nets[] = {actor_dev, q1_dev};
+    const int counts[] = {n_actor, n_critic};
+    const int rc = grad_bind(g, kTd3ActorGradBind, nets, counts, grad_dev, n_grad, TaLayout::stride, (size_t)kCgMaxGroups * TaLayout::set);
+    if (rc != MESHENV_OK) return rc;
+    grad_bind_pairs(actor_dev, 3, g->w, g->b);
+    grad_bind_pairs(q1_dev, 3, g->c.w, g->c.b);
     return MESHENV_OK;
 }
 
 int meshenv_td3_actor_grad_backward(MeshTd3ActorGrad *g, int n, const float *obs_dev, float *loss_dev, float *const *parts_dev,
                                     float *const *acts_dev)
 {
+    static const char *fn = "meshenv_td3_actor_grad_backward";
     if (!g) return MESHENV_E_ARG;
-    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_td3_actor_grad_backward: no tensors bound (meshenv_td3_actor_grad_bind)");
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_td3_actor_grad_bind)");
     if (n <= 0 || n > (1 << 24) - 16 || !obs_dev || !loss_dev)   // the kernel's 32-bit offsets reach row * 256
-        return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_backward: 0 < n <= 2^24 - 16, obs_dev and loss_dev are required");
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": 0 < n <= 2^24 - 16, obs_dev and loss_dev are required");
+    if (int rc = outputs_ok(g, fn, parts_dev, kTaParts, "per-sample")) return rc;
+    if (int rc = outputs_ok(g, fn, acts_dev, 4, "activation")) return rc;
     TaArgs A{};
     A.n = n;
     A.nwg = grad_groups(n);
@@ -3217,25 +3176,14 @@ int meshenv_td3_actor_grad_backward(MeshTd3ActorGrad *g, int n, const float *obs
     A.c = g->c;
     A.partial = g->partial;
     if (parts_dev) {
-        for (int i = 0; i < kTaParts; i++)
-            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_backward: null per-sample output");
         A.actions = parts_dev[0]; A.q = parts_dev[1]; A.dq_da = parts_dev[2]; A.d_pre = parts_dev[3];
     }
-    if (acts_dev) {
-        for (int i = 0; i < 4; i++) {
-            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_td3_actor_grad_backward: null activation output");
-            A.acts[i / 2][i % 2] = acts_dev[i];
-        }
-    }
+    for (int i = 0; acts_dev && i < 4; i++) A.acts[i / 2][i % 2] = acts_dev[i];
     DeviceGuard guard(g->device);
-    const int rc = launch(g, guard, "meshenv_td3_actor_grad_backward", [&] {
-        hipLaunchKernelGGL(k_td3_actor_grad, dim3(A.nwg, kCgSplitTD3), dim3(1024), 0, g->stream, A);
-    });
-    if (rc != MESHENV_OK) return rc;
-    return launch(g, guard, "meshenv_td3_actor_grad_backward", [&] {
+    return launch_reduced(g, guard, fn, [&] { hipLaunchKernelGGL(k_td3_actor_grad, dim3(A.nwg, kCgSplitTD3), dim3(1024), 0, g->stream, A); }, [&] {
         hipLaunchKernelGGL(k_td3_actor_grad_reduce, dim3((TaLayout::params + 255) / 256), dim3(256), 0, g->stream,
                            (const float *)g->partial, A.nwg, n, g->grad, loss_dev);
-    }, "reduction launch");
+    });
 }
 
 }  // extern "C"
@@ -3266,25 +3214,12 @@ int meshenv_ddpg_grad_bind(MeshDdpgGrad *g, const float *const *actor_dev, int n
                            float *grad_dev, int64_t n_grad)
 {
     if (!g) return MESHENV_E_ARG;
-    if (!actor_dev || !q1_dev || n_actor != 6 || n_critic != 6)
-        return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: takes 6 actor tensors and 6 tensors of the critic (DDPG: actor ReLU "
-                       "[400, 300] with a Linear(300, 3) + Tanh head, critic ReLU [400, 300], float32)");
-    if (!grad_dev || n_grad != MESHENV_DDPG_GRAD_FLOATS)
-        return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: the gradient buffer has " + std::to_string(MESHENV_DDPG_GRAD_FLOATS) +
-                       " floats, got " + std::to_string((long long)n_grad));
-    for (int i = 0; i < 6; i++) {
-        if (!actor_dev[i] || !q1_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: null tensor");
-        // w2 [300][400], the head's [3][300] and the critic's output [1][300] weights are read 16 bytes at a time
-        if (i % 2 == 0 && i >= 2 && (((uintptr_t)actor_dev[i] | (uintptr_t)q1_dev[i]) & 15))
-            return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
-    if ((uintptr_t)grad_dev & 3) return fail(g, MESHENV_E_ARG, "meshenv_ddpg_grad_bind: the gradient buffer is not 4-byte aligned");
-    for (int l = 0; l < 3; l++) {
-        g->a.w[l] = actor_dev[2 * l];
-        g->a.b[l] = actor_dev[2 * l + 1];
-        g->c.w[l] = q1_dev[2 * l];
-        g->c.b[l] = q1_dev[2 * l + 1];
-    }
+    const float *const *nets[] = {actor_dev, q1_dev};
+    const int counts[] = {n_actor, n_critic};
+    const std::string refusal = grad_bind_refusal(kDdpgGradBind, nets, counts, grad_dev, n_grad, MESHENV_DDPG_GRAD_FLOATS);
+    if (!refusal.empty()) return fail(g, MESHENV_E_ARG, refusal);
+    grad_bind_pairs(actor_dev, 3, g->a.w, g->a.b);
+    grad_bind_pairs(q1_dev, 3, g->c.w, g->c.b);
     g->grad = grad_dev;
     g->bound = true;
     return MESHENV_OK;
@@ -3306,9 +3241,8 @@ int meshenv_ddpg_grad_critic_backward(MeshDdpgGrad *g, int n, const float *obs_d
     A.two_scale = 2.0f * g->loss_scale;
     A.obs = obs_dev; A.actions = actions_dev; A.target = y_dev;
     A.c = g->c;
+    if (int rc = outputs_ok(g, fn, parts_dev, 3, "per-sample")) return rc;
     if (parts_dev) {
-        for (int i = 0; i < 3; i++)
-            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, std::string(fn) + ": null per-sample output");
         A.q = parts_dev[0]; A.acts[0] = parts_dev[1]; A.acts[1] = parts_dev[2];
     }
     DeviceGuard guard(g->device);
@@ -3339,17 +3273,12 @@ int meshenv_ddpg_grad_actor_backward(MeshDdpgGrad *g, int n, const float *obs_de
     A.obs = obs_dev;
     A.a = g->a;
     A.c = g->c;
+    if (int rc = outputs_ok(g, fn, parts_dev, kTaParts, "per-sample")) return rc;
+    if (int rc = outputs_ok(g, fn, acts_dev, 4, "activation")) return rc;
     if (parts_dev) {
-        for (int i = 0; i < kTaParts; i++)
-            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, std::string(fn) + ": null per-sample output");
         A.actions = parts_dev[0]; A.q = parts_dev[1]; A.dq_da = parts_dev[2]; A.d_pre = parts_dev[3];
     }
-    if (acts_dev) {
-        for (int i = 0; i < 4; i++) {
-            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, std::string(fn) + ": null activation output");
-            A.acts[i / 2][i % 2] = acts_dev[i];
-        }
-    }
+    for (int i = 0; acts_dev && i < 4; i++) A.acts[i / 2][i % 2] = acts_dev[i];
     DeviceGuard guard(g->device);
     if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, std::string(fn) + ": hipSetDevice failed");
     int rc = wg_reserve(g, n, fn);
@@ -3370,13 +3299,10 @@ static_assert(MESHENV_PPO_GRAD_FLOATS_64 == PgLayout<64>::stride && MESHENV_PPO_
               "include/meshenv_ppo_grad.h and csrc/meshenv_ppo_grad.h disagree");
 static_assert(MESHENV_PPO_GRAD_OUTPUTS == kPgOut && MESHENV_PPO_GRAD_PARTS == kPgParts, "include/meshenv_ppo_grad.h and csrc/meshenv_ppo_grad.h disagree");
 
-struct MeshPpoGrad : HandleBase {
+struct MeshPpoGrad : GradHandle {   // partial: the sets of the widest layout, then the advantage statistics
     PgTower t[2]{};
     const float *log_std = nullptr;
-    float *grad = nullptr;          // the caller's flat gradient buffer (PgLayout::stride floats)
-    float *partial = nullptr;       // kCgMaxGroups partial sets of the widest layout, then the advantage statistics; zeroed once
     int hidden = 0, activation = 0;
-    bool bound = false;
 };
 
 namespace {
@@ -3390,9 +3316,6 @@ PpoGradKernel ppo_grad_kernel(int hidden, int activation)
                                               {k_ppo_grad<128, kPolicyReLU>, k_ppo_grad<128, kPolicyTanh>}};
     return table[hidden == 64 ? 0 : 1][activation];
 }
-
-const char *kPpoGradShapes = "supported: pi and vf towers of two hidden layers of the same width 64 or 128, activation 0 (ReLU) or 1 "
-                             "(Tanh), action_net [3], value_net [1], log_std [3], 18 observations, float32";
 
 }  // namespace
 
@@ -3418,32 +3341,15 @@ int meshenv_ppo_grad_bind(MeshPpoGrad *g, int hidden, int activation, const floa
                                                   "of the TD3 critic kernel); ") + kPpoGradShapes);
     if ((hidden != 64 && hidden != 128) || (activation != kPolicyReLU && activation != kPolicyTanh))
         return fail(g, MESHENV_E_ARG, std::string("meshenv_ppo_grad_bind: unsupported shape; ") + kPpoGradShapes);
-    if (!tensors_dev || n_tensors != kPgTensors)
-        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: takes 13 tensors: pi w1 b1 w2 b2 wh bh, vf w1 b1 w2 b2 wh bh, log_std");
+    // the description takes over behind the shape: a width picks its row
     const int want = hidden == 64 ? PgLayout<64>::stride : PgLayout<128>::stride;
-    if (!grad_dev || n_grad != want)
-        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: the gradient buffer has " + std::to_string(want) + " floats at width " +
-                       std::to_string(hidden) + ", got " + std::to_string((long long)n_grad));
-    for (int i = 0; i < kPgTensors; i++) {
-        if (!tensors_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: null tensor");
-        // the [H][H] weights and the heads' [n_out][H] weights are read 16 bytes at a time
-        if ((i == 2 || i == 4 || i == 8 || i == 10) && ((uintptr_t)tensors_dev[i] & 15))
-            return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
-    DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_ppo_grad_bind: hipSetDevice failed");
-    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * PgLayout<128>::set + 64))
-        return fail(g, MESHENV_E_HIP, "meshenv_ppo_grad_bind: allocation failed");
-    for (int tower = 0; tower < 2; tower++)
-        for (int l = 0; l < 3; l++) {
-            g->t[tower].w[l] = tensors_dev[6 * tower + 2 * l];
-            g->t[tower].b[l] = tensors_dev[6 * tower + 2 * l + 1];
-        }
+    const int rc = grad_bind(g, kPpoGradBind[hidden == 64 ? 0 : 1], &tensors_dev, &n_tensors, grad_dev, n_grad, want,
+                             (size_t)kCgMaxGroups * PgLayout<128>::set + 64);
+    if (rc != MESHENV_OK) return rc;
+    for (int tower = 0; tower < 2; tower++) grad_bind_pairs(tensors_dev + 6 * tower, 3, g->t[tower].w, g->t[tower].b);
     g->log_std = tensors_dev[12];
-    g->grad = grad_dev;
     g->hidden = hidden;
     g->activation = activation;
-    g->bound = true;
     return MESHENV_OK;
 }
 
@@ -3452,14 +3358,17 @@ int meshenv_ppo_grad_backward(MeshPpoGrad *g, int n, const float *obs_dev, const
                               float vf_coef, int normalize_advantage, int clip_grad, float max_grad_norm, float *out_dev,
                               float *const *parts_dev, float *const *acts_dev)
 {
+    static const char *fn = "meshenv_ppo_grad_backward";
     if (!g) return MESHENV_E_ARG;
-    if (!g->bound) return fail(g, MESHENV_E_STATE, "meshenv_ppo_grad_backward: no tensors bound (meshenv_ppo_grad_bind)");
+    if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_ppo_grad_bind)");
     if (n <= 0 || n > (1 << 24) - 16 || !obs_dev || !actions_dev || !advantages_dev || !returns_dev || !out_dev)   // 32-bit offsets reach row * 128
-        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: 0 < n <= 2^24 - 16 and obs, actions, advantages, returns and out are required");
-    if (!a2c && !old_log_prob_dev) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: PPO's loss needs old_log_prob_dev");
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": 0 < n <= 2^24 - 16 and obs, actions, advantages, returns and out are required");
+    if (!a2c && !old_log_prob_dev) return fail(g, MESHENV_E_ARG, std::string(fn) + ": PPO's loss needs old_log_prob_dev");
     if (!std::isfinite(clip_range) || !std::isfinite(ent_coef) || !std::isfinite(vf_coef) || !std::isfinite(max_grad_norm) ||
         (!a2c && !(clip_range > 0.0)) || (clip_grad && !(max_grad_norm > 0.0f)))
-        return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: clip_range and max_grad_norm must be finite and > 0, ent_coef and vf_coef finite");
+        return fail(g, MESHENV_E_ARG, std::string(fn) + ": clip_range and max_grad_norm must be finite and > 0, ent_coef and vf_coef finite");
+    if (int rc = outputs_ok(g, fn, parts_dev, kPgParts, "per-row")) return rc;
+    if (int rc = outputs_ok(g, fn, acts_dev, 4, "activation")) return rc;
     const int H = g->hidden;
     const int set = H == 64 ? PgLayout<64>::set : PgLayout<128>::set, stride = H == 64 ? PgLayout<64>::stride : PgLayout<128>::stride;
     const int params = H == 64 ? PgLayout<64>::params : PgLayout<128>::params;
@@ -3478,18 +3387,10 @@ int meshenv_ppo_grad_backward(MeshPpoGrad *g, int n, const float *obs_dev, const
     A.log_std = g->log_std;
     A.partial = g->partial;
     if (parts_dev) {
-        for (int i = 0; i < kPgParts; i++)
-            if (!parts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: null per-row output");
         A.log_prob = parts_dev[0]; A.ratio = parts_dev[1]; A.values = parts_dev[2]; A.advn = parts_dev[3]; A.pass = parts_dev[4];
     }
-    if (acts_dev) {
-        for (int i = 0; i < 4; i++) {
-            if (!acts_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_ppo_grad_backward: null activation output");
-            A.acts[i / 2][i % 2] = acts_dev[i];
-        }
-    }
+    for (int i = 0; acts_dev && i < 4; i++) A.acts[i / 2][i % 2] = acts_dev[i];
     DeviceGuard guard(g->device);
-    const char *fn = "meshenv_ppo_grad_backward";
     int rc = MESHENV_OK;
     if (A.normalize) {
         rc = launch(g, guard, fn, [&] {
@@ -4496,9 +4397,6 @@ namespace {
 static_assert(kFnnPackedFloats == MESHENV_FNN_PACKED_FLOATS, "csrc/meshenv_fnn.h and include/meshenv_fnn.h disagree");
 static_assert(kMoveSkipped == MESHENV_MOVE_SKIPPED, "csrc/meshenv_kernels.h and include/meshenv_fnn.h disagree");
 
-const char *kFnnShapes = "supported network: fc1 [64][18], fc2 [128][64], fc3 [64][128], fc4 [32][64], fc5 [16][32], action_head "
-                         "[2][16], type_head [3][16], each with a bias of its rows (general/EBRD.py Policy)";
-
 // rows of the seven layers, in MESHENV_FNN_TENSORS' order; the two heads are layer 5's rows 0-1 and 2-4
 const int kFnnRows[7] = {64, 128, 64, 32, 16, kFnnAction, kFnnTypes};
 
@@ -4666,11 +4564,8 @@ static_assert(MESHENV_FNN_GRAD_FLOATS == FgLayout::stride && MESHENV_FNN_GRAD_OU
               "include/meshenv_fnn_train.h and csrc/meshenv_fnn_grad.h disagree");
 static_assert(2 * kFgLayers == MESHENV_FNN_TENSORS && MESHENV_FNN_TENSORS <= kTgtMaxCopies, "the copy table holds the 14 sources");
 
-struct MeshFnnGrad : HandleBase {
+struct MeshFnnGrad : GradHandle {
     const float *w[kFgLayers]{}, *b[kFgLayers]{};
-    float *grad = nullptr;          // the caller's flat gradient buffer (FgLayout::stride floats)
-    float *partial = nullptr;       // kCgMaxGroups partial sets; zeroed once
-    bool bound = false;
 };
 
 extern "C" {
@@ -4689,41 +4584,24 @@ int meshenv_fnn_grad_set_stream(MeshFnnGrad *g, void *stream) { return set_strea
 int meshenv_fnn_grad_bind(MeshFnnGrad *g, const float *const *tensors_dev, float *grad_dev, int64_t n_grad)
 {
     if (!g) return MESHENV_E_ARG;
-    if (!tensors_dev) return fail(g, MESHENV_E_ARG, std::string("meshenv_fnn_grad_bind: takes 14 tensors; ") + kFnnShapes);
-    if (!grad_dev || n_grad != FgLayout::stride)
-        return fail(g, MESHENV_E_ARG, "meshenv_fnn_grad_bind: the gradient buffer has " + std::to_string(FgLayout::stride) + " floats, got " +
-                       std::to_string((long long)n_grad));
-    for (int i = 0; i < MESHENV_FNN_TENSORS; i++) {
-        if (!tensors_dev[i]) return fail(g, MESHENV_E_ARG, "meshenv_fnn_grad_bind: null tensor");
-        // the weights behind fc1 are read 16 bytes at a time
-        if (i % 2 == 0 && i >= 2 && ((uintptr_t)tensors_dev[i] & 15))
-            return fail(g, MESHENV_E_ARG, "meshenv_fnn_grad_bind: weight tensor " + std::to_string(i) + " is not 16-byte aligned");
-    }
-    DeviceGuard guard(g->device);
-    if (guard.err != hipSuccess) return fail(g, MESHENV_E_HIP, "meshenv_fnn_grad_bind: hipSetDevice failed");
-    if (!zeroed_once(g, &g->partial, (size_t)kCgMaxGroups * FgLayout::set))
-        return fail(g, MESHENV_E_HIP, "meshenv_fnn_grad_bind: allocation failed");
-    for (int l = 0; l < kFgLayers; l++) {
-        g->w[l] = tensors_dev[2 * l];
-        g->b[l] = tensors_dev[2 * l + 1];
-    }
-    g->grad = grad_dev;
-    g->bound = true;
+    const int count = MESHENV_FNN_TENSORS;   // (the entry point takes no count)
+    const int rc = grad_bind(g, kFnnGradBind, &tensors_dev, &count, grad_dev, n_grad, FgLayout::stride, (size_t)kCgMaxGroups * FgLayout::set);
+    if (rc != MESHENV_OK) return rc;
+    grad_bind_pairs(tensors_dev, kFgLayers, g->w, g->b);
     return MESHENV_OK;
 }
 
 int meshenv_fnn_grad_backward(MeshFnnGrad *g, int n, int N, const float *x_dev, const float *y_dev, const int32_t *rows_dev,
                               float *out_dev, float *accum_dev)
 {
+    static const char *fn = "meshenv_fnn_grad_backward";
     if (!g) return MESHENV_E_ARG;
-    const char *fn = "meshenv_fnn_grad_backward";
     if (!g->bound) return fail(g, MESHENV_E_STATE, std::string(fn) + ": no tensors bound (meshenv_fnn_grad_bind)");
     if (n <= 0 || N <= 0 || N > (1 << 24) || n > (1 << 24) || !x_dev || !y_dev || !out_dev || (!rows_dev && n > N))
         return fail(g, MESHENV_E_ARG, std::string(fn) + ": 0 < n, N <= 2^24, n <= N without rows_dev, and x, y and out are required");
     FgArgs A{};
     A.n = n; A.N = N;
-    const int tiles = (n + kCgRows - 1) / kCgRows;
-    A.nwg = tiles < kCgMaxGroups ? tiles : kCgMaxGroups;
+    A.nwg = fnn_grad_groups(n);
     A.x = x_dev; A.y = y_dev; A.rows = rows_dev;
     for (int l = 0; l < kFgLayers; l++) {
         A.w[l] = g->w[l];
@@ -4731,12 +4609,10 @@ int meshenv_fnn_grad_backward(MeshFnnGrad *g, int n, int N, const float *x_dev, 
     }
     A.partial = g->partial;
     DeviceGuard guard(g->device);
-    const int rc = launch(g, guard, fn, [&] { hipLaunchKernelGGL(k_fnn_grad, dim3(A.nwg), dim3(kFgThreads), 0, g->stream, A); });
-    if (rc != MESHENV_OK) return rc;
-    return launch(g, guard, fn, [&] {
+    return launch_reduced(g, guard, fn, [&] { hipLaunchKernelGGL(k_fnn_grad, dim3(A.nwg), dim3(kFgThreads), 0, g->stream, A); }, [&] {
         hipLaunchKernelGGL(k_fnn_grad_reduce, dim3((FgLayout::params + 255) / 256), dim3(256), 0, g->stream, (const float *)g->partial,
                            A.nwg, g->grad, out_dev, accum_dev);
-    }, "reduction launch");
+    });
 }
 
 // ---- live weights into a loaded FusedFNN (the twin of meshenv_policy_bind / meshenv_policy_refresh)
